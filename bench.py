@@ -592,6 +592,18 @@ def sharded_frames(device, rank, world, scene0, n_scenes, frames_per_scene, back
     }
 
 
+def dump_outputs(out_dir, arrays, limit_bytes=64 << 20):
+    """``--dump-outputs``: each device tensor as ``out_dir/<name>.npy`` in float32.  A frame is 20 B per pixel (12.8 MB
+    at 800x800, 51.2 MB at --up-sample 2), so the whole frame fits under the limit and is written, not a sample of it."""
+    total = sum(t.numel() * 4 for t in arrays.values())
+    if total > limit_bytes:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed {limit_bytes}")
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+    log(f"outputs of the last timed step written to {out_dir}: "
+        + ", ".join(f"{name} {list(t.shape)}" for name, t in arrays.items()))
+
+
 def launch_guard(args):
     """``--gpus N`` must run as N ranks or not at all -- never print a 1-rank line for an N-GPU request.
 
@@ -669,7 +681,13 @@ def main():
     ap.add_argument("--single-device", action="store_true", help="map every rank to cuda:0 (rehearsal only)")
     ap.add_argument("--intersector", default="raster", choices=["raster", "bvh"],
                     help="raster: camera-coherent intersector (BVH fallback on overflow); bvh: BVH traversal only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned on rank 0 -- rgb [H*W, 3], alpha "
+                         "[H*W, 1], depth [H*W, 1] of its frame, float32 -- as DIR/<name>.npy.  The inputs are seeded, so "
+                         "two builds run with the same arguments can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     launch_guard(args)                     # before anything touches a GPU
     torch.set_grad_enabled(False)          # inference: the fields take the fused kernels
     global W, H
@@ -686,6 +704,8 @@ def main():
         args.frame_gather = "none"
     if args.frame_gather is not None:
         parallel.FRAME_GATHER_MODE = args.frame_gather
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)      # an unusable DIR fails here, before any GPU work
     # N > 1: before anything is built or timed, every data-path collective runs once on ~1 KB of known data on device
     # tensors; the modes that deliver the right bytes on EVERY rank are selected (parallel.GATHER_MODE /
     # FRAME_GATHER_MODE), and the run stops with the backend's error text when none does
@@ -732,11 +752,11 @@ def main():
     nowait = not args.host_wait and args.intersector == "raster" and args.pipeline == 1
 
     def run(first, last, record):
-        """Frames [first, last); returns (last rgb, total points).  N > 1: every finished frame goes to rank 0 with one
-        ``dist.gather`` (``--frame-gather all``: to every rank with one all_gather_into_tensor); the collective of frame
-        i (RCCL's own stream) overlaps the render of frame i+1 and is waited for before frame i+1's exchange starts (two
-        receive buffers alternate)."""
-        pts, rgb, pending, prev = 0, None, None, None
+        """Frames [first, last); returns ((rgb, alpha, depth) of the last frame, total points).  N > 1: every finished
+        frame goes to rank 0 with one ``dist.gather`` (``--frame-gather all``: to every rank with one
+        all_gather_into_tensor); the collective of frame i (RCCL's own stream) overlaps the render of frame i+1 and is
+        waited for before frame i+1's exchange starts (two receive buffers alternate)."""
+        pts, out, pending, prev = 0, None, None, None
 
         def exchange(rgb, alpha, depth, i):
             nonlocal pending
@@ -746,8 +766,9 @@ def main():
             pending = parallel.gather_frames(mine, rank, world, mode=frame_mode, out=gather_bufs[i & 1], async_op=True)
 
         def complete(begun, i):
-            nonlocal pts, rgb
+            nonlocal pts, out
             rgb, alpha, depth, n_pts = stages.finish(begun)
+            out = (rgb, alpha, depth)
             if gather:
                 exchange(rgb, alpha, depth, i)
             pts += n_pts
@@ -755,6 +776,7 @@ def main():
         if args.pipeline == 1 and nowait:
             for i in range(first, last):
                 rgb, alpha, depth, _ = stages.frame_nowait(rays[i][0], rays[i][1], cameras[i], record)
+                out = (rgb, alpha, depth)
                 if gather:
                     exchange(rgb, alpha, depth, i)
         elif args.pipeline == 1:
@@ -775,7 +797,7 @@ def main():
             ri0.scratch_slot = 0
         if pending is not None:
             pending()
-        return rgb, pts
+        return out, pts
 
     # Device spin-up (untimed, before the W warm-up steps): the scene build leaves the GPU idle for seconds and its
     # clocks take tens of milliseconds of sustained work to come back -- longer than the whole default timed region.
@@ -792,7 +814,7 @@ def main():
         torch.distributed.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    rgb, pts = run(args.warmup, n_frames, "field")
+    last_frame, pts = run(args.warmup, n_frames, "field")
     if world > 1:
         torch.distributed.barrier()
     torch.cuda.synchronize()
@@ -964,6 +986,8 @@ def main():
         mse = float(((rgb0.double() - rgb_o.double()) ** 2).mean())
         base["psnr_hip_vs_oracle_db"] = float("inf") if mse == 0 else -10.0 * float(np.log10(mse))
         result["cpu_baseline"] = base
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(zip(("rgb", "alpha", "depth"), last_frame)))
     print(json.dumps(result), flush=True)
     parallel.shutdown()
 

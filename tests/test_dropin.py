@@ -139,6 +139,28 @@ def test_bench_refuses_a_world_it_was_not_launched_with():
     assert proc.returncode != 0 and '"metric"' not in proc.stdout
 
 
+def test_bench_refuses_fewer_than_one_timed_step():
+    """``ms_per_step`` divides by ``--steps``: zero timed steps is an argument error, before any GPU call."""
+    proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"],
+                          capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert proc.returncode == 2 and '"metric"' not in proc.stdout and "--steps" in proc.stderr
+
+
+def test_bench_dump_outputs_writes_float32_npy(tmp_path):
+    """``bench.py --dump-outputs DIR``: every array as DIR/<name>.npy in float32, values unchanged; a dump over the size
+    limit is refused instead of written."""
+    import numpy as np
+    import torch
+    import bench
+    arrays = {"rgb": torch.rand(6, 3), "alpha": torch.rand(6, 1, dtype=torch.float64), "depth": torch.rand(6, 1)}
+    bench.dump_outputs(str(tmp_path), arrays)
+    for name, t in arrays.items():
+        a = np.load(tmp_path / f"{name}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, t.float().numpy()), name
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path / "small"), arrays, limit_bytes=64)
+
+
 def test_non_unit_directions_on_the_host_are_called_out():
     """The multi-hit rule is stated for unit directions: host arrays are checked, once per intersector."""
     import warnings
