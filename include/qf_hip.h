@@ -143,9 +143,9 @@ int qf_field_forward(const qf_field_desc *desc /* host */, const float *table,
 
 /* bf16 variant (BASELINE config 3): hash tables as bf16x2 rows, MLP weights as bf16 (round-to-nearest-even copies of
  * the fp32 parameters, same layouts), activations rounded to bf16 between layers, fp32 accumulate on
- * v_mfma_f32_16x16x32_bf16.  tcnn itself runs these networks in fp16 (ngp.py:340-358), so this is the reduced
- * precision mode of the same calls.  Heads: QF_HEAD_NONE, QF_HEAD_NGP, QF_HEAD_SG.  SG biases b2 / bout stay fp32
- * (they initialise the accumulator); b1 rides in the first weight tile and is bf16.                              */
+ * v_mfma_f32_16x16x32_bf16.  tcnn itself runs these networks in fp16 (ngp.py:340-358): qf_field_forward_f16 below is
+ * that precision; bf16 carries ~8x its rounding error.  Heads: QF_HEAD_NONE, QF_HEAD_NGP, QF_HEAD_SG.  SG biases
+ * b2 / bout stay fp32 (they initialise the accumulator); b1 rides in the first weight tile and is bf16.           */
 typedef struct qf_sg_head_bf16 {
     const uint16_t *w1, *b1, *w2;
     const float *b2;
@@ -157,6 +157,20 @@ int qf_field_forward_bf16(const qf_field_desc *desc /* host */, const uint16_t *
                           const qf_sg_head_bf16 *head_sg /* host */, const float *xyz, const float *dirs,
                           int64_t n, const int64_t *n_device, const int32_t *order, float *rgb, float *sigma, float *geo,
                           void *stream);
+
+/* fp16 variant: the precision tcnn stores the reference's hash grid and fully fused MLPs in (ngp.py:709-746,
+ * field.py:157-171).  Same arguments, heads and error rules as qf_field_forward_bf16, with every 16-bit array in IEEE
+ * binary16: table [rows,2] fp16 (low half = feature 0), base_w / head_ngp_w and the SG head's w1, b1, w2, wout fp16;
+ * b2 / bout stay fp32.  Numerical contract: the table rows are converted to fp32 exactly and blended in fp32; the 8
+ * blended features, every activation after a ReLU and the head input (SH | geo features | the constant 1) are rounded
+ * to fp16 round-to-nearest-even, overflow to +-inf (torch's .half()); products accumulate in fp32 on
+ * v_mfma_f32_16x16x32_f16.  fp16 subnormals are kept everywhere (tcnn initialises the grid at +-1e-4).          */
+typedef qf_sg_head_bf16 qf_sg_head_f16;     /* same six pointers; the 16-bit ones point to fp16 here */
+int qf_field_forward_f16(const qf_field_desc *desc /* host */, const uint16_t *table /* [rows,2] fp16 */,
+                         const uint16_t *base_w, const uint16_t *head_ngp_w,
+                         const qf_sg_head_f16 *head_sg /* host */, const float *xyz, const float *dirs,
+                         int64_t n, const int64_t *n_device, const int32_t *order, float *rgb, float *sigma, float *geo,
+                         void *stream);
 
 /* Backward of the two MLPs of NGPRadianceField (ngp.py:757-809), fused: recomputes the forward pass from the grid
  * encodings, back-propagates dL/drgb [n,3] and dL/ddensity [n] to dL/denc [n,32] (-> qf_grid_encode_backward) and
@@ -604,12 +618,16 @@ int qf_row_sample_counts(const int32_t *hit_count, int32_t max_hits, int32_t wid
  * examples/utils.py:510-620, scaling = 0), as a fixed sequence of this library's own launches:
  *   qf_raster_intersect (arrival order) -> qf_bvh_repair_overflow (no masks) -> qf_tile_offsets (zero_word = dropped)
  *   -> qf_pack_tiles (re-origin rule on the sorted lists; the dropped-hit count stays in *dropped)
- *   -> [field != NULL] qf_field_forward over min(*total, n_rays * max_hits) points -> qf_composite_tiles.
+ *   -> [field != NULL] qf_field_forward (or, by field_precision, qf_field_forward_bf16 / qf_field_forward_f16) over
+ *      min(*total, n_rays * max_hits) points -> qf_composite_tiles.
  * Nothing in between returns to the host: the sample count lives in total[0] (device), and its copy + the raster
  * overflow count travel to host_block[0..1] (pinned, device-writable; may be NULL) on their own.  Every pointer is
  * caller-owned device memory of the stated size; the results are those of the separate calls, bit for bit (the
  * function only composes them -- a row band of a frame sharded over 8 GPUs is ~0.3 ms of kernels, and a dozen
  * separately bound calls per band kept the host behind the GPU).  No reference counterpart.                       */
+#define QF_FIELD_FP32 0   /* qf_field_forward: fp32 table and weights (every zero-initialised job) */
+#define QF_FIELD_BF16 1   /* qf_field_forward_bf16 */
+#define QF_FIELD_FP16 2   /* qf_field_forward_f16 */
 typedef struct qf_frame_job {
     const qf_camera *camera;            /* host; the rays are its pixel grid, row-major */
     const float *rays_o, *rays_d;       /* [n_rays,3] */
@@ -619,7 +637,7 @@ typedef struct qf_frame_job {
     float min_separation;               /* the tile pack's re-origin rule (0 = off) */
     int32_t bg_mode;                    /* QF_BG_* */
     float delta_const;                  /* render_step_size */
-    int32_t reserved_;
+    int32_t field_precision;            /* QF_FIELD_*: which qf_field_forward* evaluates the field (0 = fp32) */
     /* scratch */
     int32_t *hit_tri;                   /* [n_rays, K] */
     float *hit_t;                       /* [n_rays, K] */
@@ -634,8 +652,8 @@ typedef struct qf_frame_job {
     int32_t *tri_c;                     /* or NULL */
     /* the field (NULL: stop after the samples) and its outputs at the same capacity */
     const qf_field_desc *field;         /* host */
-    const float *table, *base_w, *head_ngp_w;
-    const qf_sg_head *head_sg;          /* host, or NULL */
+    const void *table, *base_w, *head_ngp_w;   /* fp32, or 16-bit at a QF_FIELD_BF16 / QF_FIELD_FP16 precision */
+    const void *head_sg;                /* host, or NULL: qf_sg_head (fp32), qf_sg_head_bf16 / qf_sg_head_f16 */
     float *rgb_c, *sigma_c;
     /* the image: three arrays or one packed [n_rays,5] (rgb | alpha | depth), as qf_composite_tiles */
     const float *bkgd;

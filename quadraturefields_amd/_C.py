@@ -21,6 +21,7 @@ QF_BVH_MAX_HITS = 64
 QF_TEXEL_RECORD_BYTES = 64
 QF_TEXEL_TRIANGLE_RECORD_BYTES = 128
 HEAD_NONE, HEAD_NGP, HEAD_SG, HEAD_SG_FEATURES = 0, 1, 2, 3
+FIELD_FP32, FIELD_BF16, FIELD_FP16 = 0, 1, 2          # qf_frame_job.field_precision
 BG_WHITE, BG_BLACK, BG_CUSTOM, BG_NONE = 0, 1, 2, 3
 
 
@@ -51,7 +52,7 @@ class FrameJob(Structure):
     """qf_frame_job (include/qf_hip.h): one render-only camera frame as one host call."""
     _fields_ = [("camera", c_void_p), ("rays_o", c_void_p), ("rays_d", c_void_p), ("n_rays", c_int64),
                 ("max_hits", c_int32), ("cull_chunks", c_int32), ("min_separation", c_float), ("bg_mode", c_int32),
-                ("delta_const", c_float), ("reserved_", c_int32),
+                ("delta_const", c_float), ("field_precision", c_int32),
                 ("hit_tri", c_void_p), ("hit_t", c_void_p), ("hit_count", c_void_p), ("final_count", c_void_p),
                 ("tile_base", c_void_p), ("total", c_void_p), ("host_block", c_void_p), ("dropped", c_void_p),
                 ("xyz_c", c_void_p), ("dirs_c", c_void_p), ("depth_c", c_void_p), ("tri_c", c_void_p),
@@ -82,6 +83,7 @@ _SIGNATURES = {
     "qf_grid_mlp_forward": (c_int, [POINTER(GridDesc), _P, _P, _P, c_int64, _P, _P]),
     "qf_field_forward": (c_int, [POINTER(FieldDesc), _P, _P, _P, POINTER(SGHead), _P, _P, c_int64, _P, _P, _P, _P, _P, _P, _P, _P]),
     "qf_field_forward_bf16": (c_int, [POINTER(FieldDesc), _P, _P, _P, POINTER(SGHead), _P, _P, c_int64, _P, _P, _P, _P, _P, _P]),
+    "qf_field_forward_f16": (c_int, [POINTER(FieldDesc), _P, _P, _P, POINTER(SGHead), _P, _P, c_int64, _P, _P, _P, _P, _P, _P]),
     "qf_ngp_mlp_backward": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int64, _P, _P, _P, _P]),
     "qf_sg_mlp_backward": (c_int, [_P, _P, _P, c_int64, _P, _P, POINTER(SGHead), c_int32, c_int64, _P, _P, POINTER(SGHead), _P]),
     "qf_sg_features_to_rgb": (c_int, [_P, c_int64, _P, c_int64, c_int32, _P, _P]),

@@ -1,17 +1,23 @@
-// bf16 variant of the fused field evaluation (BASELINE config 3: bf16 tables and MLPs, fp32 accumulate).
+// 16-bit variants of the fused field evaluation: bf16 (BASELINE config 3) and fp16 (tcnn's own precision: the reference
+// keeps its hash grid and fully fused MLPs in fp16, ngp.py:709-746 / field.py:157-171).  Tables and MLPs in 16 bits,
+// fp32 accumulate.
 //
 // Same wave mapping as field_eval.hip -- lane (p = l & 15, g = l >> 4): point p of a 16-point group, level quartet
-// g -- but the hash tables hold bf16x2 rows (4 B gathers) and every layer is ONE OR TWO v_mfma_f32_16x16x32_bf16:
+// g -- but the hash tables hold 16-bit x2 rows (4 B gathers) and every layer is ONE OR TWO v_mfma_f32_16x16x32_{bf16,f16}:
 // the B operand of that instruction is 8 consecutive k per lane quartet, which is exactly the 8 grid features
 // (4 levels x 2) a lane has just blended, or 8 of the 16 hidden activations it holds after the previous layer
 // (C/D layout: register r of lane (g,p) = neuron 16*mt + 4g + r of point p).  So, as in the fp32 kernel, activations
-// go from accumulator to next operand without leaving the lane; they are rounded to bf16 (RNE) on the way.
-// 20 MFMAs per 16 points instead of 160.  Weights: bf16 copies of the reference's fp32 parameters, re-laid once per
-// workgroup into per-lane operand order in LDS (20 KB).
+// go from accumulator to next operand without leaving the lane; they are rounded to 16 bits (RNE) on the way.
+// 20 MFMAs per 16 points instead of 160.  Weights: 16-bit copies of the reference's fp32 parameters, re-laid once per
+// workgroup into per-lane operand order in LDS (20 KB).  The two element types share every line below except the four
+// members of their trait (operand vector, fp32 -> 16-bit packing, row unpacking, the MFMA); both MFMAs have the same
+// shape, lane maps and C/D layout.
 #include "field_common.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
 
@@ -21,10 +27,10 @@ struct FieldArgsB {
     GridArgs grid;
     float aabb_lo[3];
     float aabb_hi[3];
-    const uint32_t *table;      // [rows] bf16x2: low half = feature 0
-    const uint16_t *base_w;     // bf16 [64*32 | 16*64]
-    const uint16_t *head_w;     // bf16 NGP head [64*32 | 64*64 | 16*64]
-    const uint16_t *sg_w1, *sg_b1, *sg_w2, *sg_wout;   // bf16
+    const uint32_t *table;      // [rows] 16-bit x2: low half = feature 0
+    const uint16_t *base_w;     // 16-bit [64*32 | 16*64]
+    const uint16_t *head_w;     // 16-bit NGP head [64*32 | 64*64 | 16*64]
+    const uint16_t *sg_w1, *sg_b1, *sg_w2, *sg_wout;   // 16-bit
     const float *sg_b2, *sg_bout;                      // fp32 (accumulator init)
     const float *xyz;
     const float *dirs;
@@ -43,23 +49,55 @@ __device__ __forceinline__ uint32_t f32_to_bf16_bits(float f)
     return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;       // round to nearest even (finite inputs)
 }
 
-__device__ __forceinline__ uint32_t pack2(float lo, float hi) { return f32_to_bf16_bits(lo) | (f32_to_bf16_bits(hi) << 16); }
+// bf16: integer RNE, a table row unpacks by shifting each half into the top of an fp32
+struct Bf16Elem {
+    typedef bf16x8 vec8;
+    static __device__ __forceinline__ uint32_t pack2(float lo, float hi)
+    {
+        return f32_to_bf16_bits(lo) | (f32_to_bf16_bits(hi) << 16);
+    }
+    static __device__ __forceinline__ float2 unpack2(uint32_t raw)
+    {
+        return make_float2(__uint_as_float(raw << 16), __uint_as_float(raw & 0xffff0000u));
+    }
+    static __device__ __forceinline__ f32x4 mfma(uint4 a, vec8 b, f32x4 c)
+    {
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), b, c, 0, 0, 0);
+    }
+};
 
-__device__ __forceinline__ bf16x8 pack8(const float v[8])
-{
-    const uint4 u = {pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7])};
-    return __builtin_bit_cast(bf16x8, u);
-}
+// fp16: the plain (_Float16) cast is RNE (v_cvt_pk_f16_f32; overflow -> +-inf, as torch's .half()), never the
+// round-toward-zero cvt_pkrtz; v_cvt_f32_f16 is exact.  fp16 denormals are on (float_denorm_mode_16_64), so subnormal
+// table entries and activations survive the conversions and the MFMA.
+struct F16Elem {
+    typedef f16x8 vec8;
+    static __device__ __forceinline__ uint32_t pack2(float lo, float hi)
+    {
+        const f16x2 h = {(_Float16)lo, (_Float16)hi};
+        return __builtin_bit_cast(uint32_t, h);
+    }
+    static __device__ __forceinline__ float2 unpack2(uint32_t raw)
+    {
+        const f16x2 h = __builtin_bit_cast(f16x2, raw);
+        return make_float2((float)h.x, (float)h.y);
+    }
+    static __device__ __forceinline__ f32x4 mfma(uint4 a, vec8 b, f32x4 c)
+    {
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), b, c, 0, 0, 0);
+    }
+};
 
-__device__ __forceinline__ f32x4 mfma_bf16(uint4 a, bf16x8 b, f32x4 c)
+template <class E>
+__device__ __forceinline__ typename E::vec8 pack8(const float v[8])
 {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), b, c, 0, 0, 0);
+    const uint4 u = {E::pack2(v[0], v[1]), E::pack2(v[2], v[3]), E::pack2(v[4], v[5]), E::pack2(v[6], v[7])};
+    return __builtin_bit_cast(typename E::vec8, u);
 }
 
 // column of a 64-wide hidden input fed as element j of lane quartet kq at k-step s (s = 0, 1)
 __device__ __forceinline__ int hidden_col_b(int s, int kq, int j) { return 16 * (2 * s + (j >> 2)) + 4 * kq + (j & 3); }
 
-// bf16 bits of the weight that lane `lane` feeds as element j of the A operand of MFMA number m
+// 16-bit pattern of the weight that lane `lane` feeds as element j of the A operand of MFMA number m
 template <int HEAD>
 __device__ uint32_t weight_for_b(const FieldArgsB &a, int m, int lane, int j)
 {
@@ -104,13 +142,15 @@ __device__ __forceinline__ void relu8(const f32x4 &a, const f32x4 &b, float out[
     for (int r = 0; r < 4; ++r) { out[r] = fmaxf(a[r], 0.0f); out[4 + r] = fmaxf(b[r], 0.0f); }
 }
 
-template <int HEAD>
-__global__ __launch_bounds__(kBlockB, 4) void field_kernel_bf16(const FieldArgsB a)
+// E = Bf16Elem: the bf16 kernel (BASELINE config 3), E = F16Elem: the fp16 one.  The kernel itself is the template
+// (not a __global__ wrapper around an inlined body): that is what keeps the bf16 instantiation's code what it was.
+template <class E, int HEAD>
+__global__ __launch_bounds__(kBlockB, 4) void field_kernel_16(const FieldArgsB a)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t ldsb[];
     const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, p = lane & 15;
 
-    // A-operand images: [m][lane] uint4 (8 bf16), then fp32 biases (SG), then the level table
+    // A-operand images: [m][lane] uint4 (8 x 16 bit), then fp32 biases (SG), then the level table
     const int n_m = n_mfma_b<HEAD>(a);
     for (int e = tid; e < n_m * 64 * 4; e += kBlockB) {
         const int m = e >> 8, l = (e >> 2) & 63, w = e & 3;
@@ -181,24 +221,21 @@ __global__ __launch_bounds__(kBlockB, 4) void field_kernel_bf16(const FieldArgsB
         for (int j = 0; j < 4; ++j) {
             float2 val[8];
 #pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                val[c].x = __uint_as_float(raw[j][c] << 16);
-                val[c].y = __uint_as_float(raw[j][c] & 0xffff0000u);
-            }
+            for (int c = 0; c < 8; ++c) val[c] = E::unpack2(raw[j][c]);
             level_blend(val, frac[j], &feat[2 * j], &feat[2 * j + 1]);
         }
 
         // ---- base MLP
-        const bf16x8 xb = pack8(feat);
+        const typename E::vec8 xb = pack8<E>(feat);
         f32x4 h[4];
 #pragma unroll
-        for (int mt = 0; mt < 4; ++mt) h[mt] = mfma_bf16(img[mt * 64], xb, (f32x4){0.f, 0.f, 0.f, 0.f});
+        for (int mt = 0; mt < 4; ++mt) h[mt] = E::mfma(img[mt * 64], xb, (f32x4){0.f, 0.f, 0.f, 0.f});
         float hv[8];
         f32x4 bo = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
             relu8(h[2 * s], h[2 * s + 1], hv);
-            bo = mfma_bf16(img[(4 + s) * 64], pack8(hv), bo);
+            bo = E::mfma(img[(4 + s) * 64], pack8<E>(hv), bo);
         }
         const float density = selector ? expf(bo[0] - 1.0f) : 0.0f;
         if (g == 0 && valid && a.sigma) a.sigma[pt] = density;
@@ -220,25 +257,25 @@ __global__ __launch_bounds__(kBlockB, 4) void field_kernel_bf16(const FieldArgsB
 #pragma unroll
             for (int r = 0; r < 4; ++r) in[4 + r] = bo[r];
             if (g == 0) in[4] = 1.0f;
-            const bf16x8 ib = pack8(in);
+            const typename E::vec8 ib = pack8<E>(in);
             f32x4 h1[4], h2[4];
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt) {
-                h1[mt] = mfma_bf16(img[(6 + mt) * 64], ib, (f32x4){0.f, 0.f, 0.f, 0.f});
+                h1[mt] = E::mfma(img[(6 + mt) * 64], ib, (f32x4){0.f, 0.f, 0.f, 0.f});
                 h2[mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
             }
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
                 relu8(h1[2 * s], h1[2 * s + 1], hv);
-                const bf16x8 hb = pack8(hv);
+                const typename E::vec8 hb = pack8<E>(hv);
 #pragma unroll
-                for (int mt = 0; mt < 4; ++mt) h2[mt] = mfma_bf16(img[(10 + 4 * s + mt) * 64], hb, h2[mt]);
+                for (int mt = 0; mt < 4; ++mt) h2[mt] = E::mfma(img[(10 + 4 * s + mt) * 64], hb, h2[mt]);
             }
             f32x4 c = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
                 relu8(h2[2 * s], h2[2 * s + 1], hv);
-                c = mfma_bf16(img[(18 + s) * 64], pack8(hv), c);
+                c = E::mfma(img[(18 + s) * 64], pack8<E>(hv), c);
             }
             if (g == 0 && valid) {
                 a.rgb[pt * 3 + 0] = sigmoidf(c[0]);
@@ -252,33 +289,33 @@ __global__ __launch_bounds__(kBlockB, 4) void field_kernel_bf16(const FieldArgsB
 #pragma unroll
             for (int r = 0; r < 4; ++r) { in[r] = bo[r]; in[4 + r] = 0.0f; }
             if (g == 0) in[0] = 1.0f;
-            const bf16x8 ib = pack8(in);
+            const typename E::vec8 ib = pack8<E>(in);
             const f32x4 *b2v = reinterpret_cast<const f32x4 *>(bias_lds);
             const f32x4 *bov = reinterpret_cast<const f32x4 *>(bias_lds + 64);
             f32x4 h1[4], h2[4];
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt) {
-                h1[mt] = mfma_bf16(img[(6 + mt) * 64], ib, (f32x4){0.f, 0.f, 0.f, 0.f});
+                h1[mt] = E::mfma(img[(6 + mt) * 64], ib, (f32x4){0.f, 0.f, 0.f, 0.f});
                 h2[mt] = b2v[4 * mt + g];
             }
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
                 relu8(h1[2 * s], h1[2 * s + 1], hv);
-                const bf16x8 hb = pack8(hv);
+                const typename E::vec8 hb = pack8<E>(hv);
 #pragma unroll
-                for (int mt = 0; mt < 4; ++mt) h2[mt] = mfma_bf16(img[(10 + 4 * s + mt) * 64], hb, h2[mt]);
+                for (int mt = 0; mt < 4; ++mt) h2[mt] = E::mfma(img[(10 + 4 * s + mt) * 64], hb, h2[mt]);
             }
             float hv0[8], hv1[8];
             relu8(h2[0], h2[1], hv0);
             relu8(h2[2], h2[3], hv1);
-            const bf16x8 hb0 = pack8(hv0), hb1 = pack8(hv1);
+            const typename E::vec8 hb0 = pack8<E>(hv0), hb1 = pack8<E>(hv1);
             f32x4 out[4];
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt) {
                 out[mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
                 if (mt < a.nt_out) {
-                    out[mt] = mfma_bf16(img[(18 + 2 * mt) * 64], hb0, bov[4 * mt + g]);
-                    out[mt] = mfma_bf16(img[(19 + 2 * mt) * 64], hb1, out[mt]);
+                    out[mt] = E::mfma(img[(18 + 2 * mt) * 64], hb0, bov[4 * mt + g]);
+                    out[mt] = E::mfma(img[(19 + 2 * mt) * 64], hb1, out[mt]);
                 }
             }
             const float dx = a.dirs[pt * 3 + 0], dy = a.dirs[pt * 3 + 1], dz = a.dirs[pt * 3 + 2];
@@ -309,7 +346,7 @@ __global__ __launch_bounds__(kBlockB, 4) void field_kernel_bf16(const FieldArgsB
     }
 }
 
-template <int HEAD>
+template <class E, int HEAD>
 int launch_field_b(const FieldArgsB &a, hipStream_t st)
 {
     int n_m = 6;
@@ -320,17 +357,16 @@ int launch_field_b(const FieldArgsB &a, hipStream_t st)
     const int64_t cap = (int64_t)qf_cu_count_cached();   // one workgroup per CU, see launch_field in field_eval.hip
     if (blocks > cap) blocks = cap;
     if (blocks >= 64) blocks &= ~(int64_t)7;
-    hipLaunchKernelGGL(field_kernel_bf16<HEAD>, dim3((unsigned)blocks), dim3(kBlockB), lds_bytes, st, a);
+    hipLaunchKernelGGL((field_kernel_16<E, HEAD>), dim3((unsigned)blocks), dim3(kBlockB), lds_bytes, st, a);
     QF_LAUNCH_CHECK();
     return QF_OK;
 }
 
-}  // namespace
-
-extern "C" int qf_field_forward_bf16(const qf_field_desc *desc, const uint16_t *table, const uint16_t *base_w,
-                                     const uint16_t *head_ngp_w, const qf_sg_head_bf16 *head_sg, const float *xyz,
-                                     const float *dirs, int64_t n, const int64_t *n_device, const int32_t *order,
-                                     float *rgb, float *sigma, float *geo, void *stream)
+// the two entry points' shared argument handling (same rules for both element types)
+template <class E, class SgHead>
+int field_forward_16(const qf_field_desc *desc, const uint16_t *table, const uint16_t *base_w, const uint16_t *head_ngp_w,
+                     const SgHead *head_sg, const float *xyz, const float *dirs, int64_t n, const int64_t *n_device,
+                     const int32_t *order, float *rgb, float *sigma, float *geo, void *stream)
 {
     if (!desc || !table || !base_w || n < 0 || n > 0x7fffffff) return QF_ERR_INVALID_ARGUMENT;
     FieldArgsB a = {};
@@ -357,11 +393,11 @@ extern "C" int qf_field_forward_bf16(const qf_field_desc *desc, const uint16_t *
     switch (desc->head) {
     case QF_HEAD_NONE:
         if (!sigma && !geo) return QF_ERR_INVALID_ARGUMENT;
-        return launch_field_b<QF_HEAD_NONE>(a, st);
+        return launch_field_b<E, QF_HEAD_NONE>(a, st);
     case QF_HEAD_NGP:
         if (!head_ngp_w || !dirs || !rgb) return QF_ERR_INVALID_ARGUMENT;
         a.head_w = head_ngp_w;
-        return launch_field_b<QF_HEAD_NGP>(a, st);
+        return launch_field_b<E, QF_HEAD_NGP>(a, st);
     case QF_HEAD_SG:
         if (!head_sg || !head_sg->w1 || !head_sg->b1 || !head_sg->w2 || !head_sg->b2 || !head_sg->wout ||
             !head_sg->bout || !dirs || !rgb)
@@ -372,8 +408,28 @@ extern "C" int qf_field_forward_bf16(const qf_field_desc *desc, const uint16_t *
         a.n_lobes = desc->n_lobes;
         a.n_out = 3 + 7 * desc->n_lobes;
         a.nt_out = (a.n_out + 15) / 16;
-        return launch_field_b<QF_HEAD_SG>(a, st);
+        return launch_field_b<E, QF_HEAD_SG>(a, st);
     default:
         return QF_ERR_UNSUPPORTED;
     }
+}
+
+}  // namespace
+
+extern "C" int qf_field_forward_bf16(const qf_field_desc *desc, const uint16_t *table, const uint16_t *base_w,
+                                     const uint16_t *head_ngp_w, const qf_sg_head_bf16 *head_sg, const float *xyz,
+                                     const float *dirs, int64_t n, const int64_t *n_device, const int32_t *order,
+                                     float *rgb, float *sigma, float *geo, void *stream)
+{
+    return field_forward_16<Bf16Elem>(desc, table, base_w, head_ngp_w, head_sg, xyz, dirs, n, n_device, order, rgb, sigma,
+                                      geo, stream);
+}
+
+extern "C" int qf_field_forward_f16(const qf_field_desc *desc, const uint16_t *table, const uint16_t *base_w,
+                                    const uint16_t *head_ngp_w, const qf_sg_head_f16 *head_sg, const float *xyz,
+                                    const float *dirs, int64_t n, const int64_t *n_device, const int32_t *order,
+                                    float *rgb, float *sigma, float *geo, void *stream)
+{
+    return field_forward_16<F16Elem>(desc, table, base_w, head_ngp_w, head_sg, xyz, dirs, n, n_device, order, rgb, sigma,
+                                     geo, stream);
 }

@@ -12,6 +12,7 @@ extern "C" int qf_frame_render(qf_bvh *bvh, const qf_frame_job *job, void *strea
     if (!j.rays_o || !j.rays_d || !j.hit_tri || !j.hit_t || !j.hit_count || !j.final_count || !j.tile_base || !j.total ||
         !j.dropped || !j.xyz_c || !j.dirs_c || !j.depth_c)
         return QF_ERR_INVALID_ARGUMENT;
+    if (j.field_precision < QF_FIELD_FP32 || j.field_precision > QF_FIELD_FP16) return QF_ERR_INVALID_ARGUMENT;
     // The whole job is checked BEFORE the first launch: the entry points below repeat these tests, but by the
     // time qf_field_forward or qf_composite_tiles would refuse, four kernels have run, the handle's cull parity has
     // flipped and the pinned block has been written -- a C caller would get INVALID_ARGUMENT for a half-executed frame.
@@ -22,8 +23,15 @@ extern "C" int qf_frame_render(qf_bvh *bvh, const qf_frame_job *job, void *strea
         if (f.head == QF_HEAD_NGP) {
             if (!j.head_ngp_w) return QF_ERR_INVALID_ARGUMENT;
         } else if (f.head == QF_HEAD_SG) {
-            const qf_sg_head *s = j.head_sg;
-            if (!s || !s->w1 || !s->b1 || !s->w2 || !s->b2 || !s->wout || !s->bout) return QF_ERR_INVALID_ARGUMENT;
+            // six pointers in every precision (qf_sg_head / qf_sg_head_bf16 / qf_sg_head_f16): all must be set
+            if (!j.head_sg) return QF_ERR_INVALID_ARGUMENT;
+            if (j.field_precision == QF_FIELD_FP32) {
+                const qf_sg_head *s = static_cast<const qf_sg_head *>(j.head_sg);
+                if (!s->w1 || !s->b1 || !s->w2 || !s->b2 || !s->wout || !s->bout) return QF_ERR_INVALID_ARGUMENT;
+            } else {
+                const qf_sg_head_bf16 *s = static_cast<const qf_sg_head_bf16 *>(j.head_sg);
+                if (!s->w1 || !s->b1 || !s->w2 || !s->b2 || !s->wout || !s->bout) return QF_ERR_INVALID_ARGUMENT;
+            }
             if (f.n_lobes < 1 || f.n_lobes > QF_MAX_LOBES) return QF_ERR_UNSUPPORTED;
         } else {
             return QF_ERR_INVALID_ARGUMENT;       // QF_HEAD_NONE / QF_HEAD_SG_FEATURES give the compositor no rgb
@@ -56,9 +64,18 @@ extern "C" int qf_frame_render(qf_bvh *bvh, const qf_frame_job *job, void *strea
                        stream);
     if (rc != QF_OK) return rc;
     if (!j.field) return QF_OK;                 // sampling only
-    // 5. the field over min(*total, cap) points, 6. the tile compositor
-    rc = qf_field_forward(j.field, j.table, j.base_w, j.head_ngp_w, j.head_sg, j.xyz_c, j.dirs_c, cap, j.total, nullptr,
-                          j.rgb_c, j.sigma_c, nullptr, nullptr, nullptr, stream);
+    // 5. the field over min(*total, cap) points, in the job's precision, 6. the tile compositor
+    if (j.field_precision == QF_FIELD_FP32) {
+        rc = qf_field_forward(j.field, static_cast<const float *>(j.table), static_cast<const float *>(j.base_w),
+                              static_cast<const float *>(j.head_ngp_w), static_cast<const qf_sg_head *>(j.head_sg),
+                              j.xyz_c, j.dirs_c, cap, j.total, nullptr, j.rgb_c, j.sigma_c, nullptr, nullptr, nullptr,
+                              stream);
+    } else {
+        auto fwd = j.field_precision == QF_FIELD_BF16 ? qf_field_forward_bf16 : qf_field_forward_f16;
+        rc = fwd(j.field, static_cast<const uint16_t *>(j.table), static_cast<const uint16_t *>(j.base_w),
+                 static_cast<const uint16_t *>(j.head_ngp_w), static_cast<const qf_sg_head_bf16 *>(j.head_sg), j.xyz_c,
+                 j.dirs_c, cap, j.total, nullptr, j.rgb_c, j.sigma_c, nullptr, stream);
+    }
     if (rc != QF_OK) return rc;
     return qf_composite_tiles(j.rgb_c, j.sigma_c, j.depth_c, j.delta_const, j.final_count, j.max_hits, j.tile_base, w, h,
                               j.bg_mode, j.bkgd, j.out_rgb, j.out_alpha, j.out_depth, nullptr, j.out_packed, stream);

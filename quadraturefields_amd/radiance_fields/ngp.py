@@ -159,25 +159,38 @@ class _FusedFieldBase(nn.Module):
         d.head, d.n_lobes = head, n_lobes
         return d
 
-    #: "fp32" (default; parity with the fp32 oracle to ~1e-6) or "bf16" (bf16 tables + MLPs, fp32 accumulate --
-    #: BASELINE config 3; tcnn runs the same networks in fp16).  ``features()`` always evaluates in fp32.
+    #: Precision of the fused inference kernel: "fp32" (default; parity with the fp32 oracle to ~1e-6), "fp16" (fp16
+    #: tables + MLPs, fp32 accumulate on v_mfma_f32_16x16x32_f16 -- the precision tcnn stores the reference's networks
+    #: in) or "bf16" (bf16 tables + MLPs, fp32 accumulate -- BASELINE config 3; ~8x fp16's rounding error).  Any other
+    #: value raises ValueError at the first evaluation.  fp16 and bf16 are inference modes: ``features()`` and the
+    #: training routes (autograd recording) always evaluate in fp32.
     compute_dtype = "fp32"
+    COMPUTE_DTYPES = ("fp32", "bf16", "fp16")
+    _HALF = {"bf16": torch.bfloat16, "fp16": torch.float16}
 
-    def _bf16_copies(self, head_ngp, head_sg):
-        """Round-to-nearest-even bf16 copies of the fp32 master parameters, refreshed when a parameter changes."""
+    def _half_copies(self, dtype, head_ngp, head_sg):
+        """Round-to-nearest-even 16-bit copies (``dtype``: torch.bfloat16 or torch.float16) of the fp32 master
+        parameters, refreshed when a parameter changes.  ONE copy set is kept -- the T = 2^21 table alone is 90 MB --
+        keyed by the dtype too: switching between fp16 and bf16 rebuilds it, a kernel never reads the other format."""
         params = [self.mlp_base.params] + ([head_ngp] if head_ngp is not None else []) + list(head_sg or [])
-        key = tuple((t.data_ptr(), t._version) for t in params)
-        cache = getattr(self, "_bf16_cache", None)
+        key = (dtype,) + tuple((t.data_ptr(), t._version) for t in params)
+        cache = getattr(self, "_half_cache", None)
         if cache is None or cache[0] != key:
-            bf = lambda t: t.detach().to(torch.bfloat16).contiguous()
-            c = {"base": bf(self.mlp_base.network_params()), "table": bf(self.mlp_base.grid_params())}
+            self._half_cache = cache = None    # the old set goes before the new one is allocated
+            cv = lambda t: t.detach().to(dtype).contiguous()
+            c = {"base": cv(self.mlp_base.network_params()), "table": cv(self.mlp_base.grid_params())}
             if head_ngp is not None:
-                c["head"] = bf(head_ngp)
+                c["head"] = cv(head_ngp)
             if head_sg is not None:
-                c["sg"] = [bf(head_sg[0]), bf(head_sg[1]), bf(head_sg[2]), bf(head_sg[4])]
+                c["sg"] = [cv(head_sg[0]), cv(head_sg[1]), cv(head_sg[2]), cv(head_sg[4])]
             cache = (key, c)
-            self._bf16_cache = cache
+            self._half_cache = cache
         return cache[1]
+
+    def _half_sg_head(self, c, head_sg) -> _C.SGHead:
+        """qf_sg_head_bf16 / _f16 of the copies: w1, b1, w2 16-bit | b2 fp32 | wout 16-bit | bout fp32."""
+        return _C.SGHead(_C.ptr(c["sg"][0]), _C.ptr(c["sg"][1]), _C.ptr(c["sg"][2]), _C.ptr(head_sg[3]),
+                         _C.ptr(c["sg"][3]), _C.ptr(head_sg[5]))
 
     def normalize(self, x):
         """(selector, x01) -- ngp.py:748-755; elementwise, kept in torch."""
@@ -188,6 +201,9 @@ class _FusedFieldBase(nn.Module):
 
     def _launch(self, head, n_lobes, xyz, dirs, want_rgb=False, want_sigma=False, want_geo=False, want_features=0,
                 head_ngp=None, head_sg=None, order=None, enc_out=None, n_device=None):
+        if self.compute_dtype not in self.COMPUTE_DTYPES:
+            raise ValueError(f"compute_dtype must be one of {', '.join(map(repr, self.COMPUTE_DTYPES))}, "
+                             f"got {self.compute_dtype!r}")
         xyz = _C.f32c(xyz.reshape(-1, 3))
         n = xyz.shape[0]
         dev = xyz.device
@@ -206,15 +222,16 @@ class _FusedFieldBase(nn.Module):
         feats = torch.empty((n, want_features), dtype=torch.float32, device=dev) if want_features else None
         desc = self._field_desc(head, n_lobes)
         sg = None
-        if self.compute_dtype == "bf16" and head in (_C.HEAD_NONE, _C.HEAD_NGP, _C.HEAD_SG):
-            c = self._bf16_copies(head_ngp, head_sg)
-            if head_sg is not None:   # w1, b1, w2 bf16 | b2 fp32 | wout bf16 | bout fp32
-                sg = _C.SGHead(_C.ptr(c["sg"][0]), _C.ptr(c["sg"][1]), _C.ptr(c["sg"][2]), _C.ptr(head_sg[3]),
-                               _C.ptr(c["sg"][3]), _C.ptr(head_sg[5]))
-            _C.check(_C.lib().qf_field_forward_bf16(
+        half = self._HALF.get(self.compute_dtype)
+        if half is not None and head in (_C.HEAD_NONE, _C.HEAD_NGP, _C.HEAD_SG):
+            c = self._half_copies(half, head_ngp, head_sg)
+            if head_sg is not None:
+                sg = self._half_sg_head(c, head_sg)
+            name = "qf_field_forward_bf16" if half is torch.bfloat16 else "qf_field_forward_f16"
+            _C.check(getattr(_C.lib(), name)(
                 ctypes.byref(desc), _C.ptr(c["table"]), _C.ptr(c["base"]), _C.ptr(c.get("head")),
                 ctypes.byref(sg) if sg is not None else None, _C.ptr(xyz), _C.ptr(dirs), n, _C.ptr(n_device, torch.int64),
-                _C.ptr(order, torch.int32), _C.ptr(rgb), _C.ptr(sigma), _C.ptr(geo), _C.stream()), "qf_field_forward_bf16")
+                _C.ptr(order, torch.int32), _C.ptr(rgb), _C.ptr(sigma), _C.ptr(geo), _C.stream()), name)
             return rgb, sigma, geo, feats
         if head_sg is not None:
             sg = _C.SGHead(*[_C.ptr(t) for t in head_sg])

@@ -136,7 +136,7 @@ class FrameRenderer:
         k = self.mesh_intersect.num_intersections
         deform = self.field_net is not None and scaling != 0
         if (not deform and type(self.radiance_field) in (NGPRadianceField, NGPRadianceFieldSGNew)
-                and self.radiance_field.compute_dtype == "fp32" and ri.fused_frame_ready(camera, k)):
+                and self.radiance_field.compute_dtype in ("fp32", "fp16") and ri.fused_frame_ready(camera, k)):
             return self._render_async_one_call(origins, viewdirs, camera, k, render_bkgd, packed)
         frame = ri.sample_frame_device(origins, viewdirs, k, camera)
         _, xyz_c, dirs_c = ri.last_layout
@@ -158,7 +158,8 @@ class FrameRenderer:
         repair, tile offsets, tile pack, the field -- NGP or spherical-Gaussian head --, tile compositor): the buffers are allocated here, the launches are
         enqueued by ONE bound call instead of six -- the host cost of a frame drops from ~0.28 ms to what the
         allocations take, which is what a 0.3 ms row band of a frame sharded over 8 GPUs needs.  Same kernels, same
-        arguments, same pixels."""
+        arguments, same pixels.  An fp16 field passes its fp16 copies and ``field_precision`` = fp16 (the job's field
+        step is then qf_field_forward_f16)."""
         ri = self.mesh_intersect.rayintersector
         rf = self.radiance_field
         # launch on the intersector's device (its index is resolved at construction, _C.resolve_device; one switch at most)
@@ -174,7 +175,7 @@ class FrameRenderer:
         rgbs = torch.empty((cap, 3), dtype=torch.float32, device=dev)
         sigmas = torch.empty((cap,), dtype=torch.float32, device=dev)
         table, base_w = rf.mlp_base.grid_params(), rf.mlp_base.network_params()
-        head_w = sg = sg_params = None
+        head_w = sg = sg_params = half = None
         if type(rf) is NGPRadianceFieldSGNew:         # spherical-Gaussian head: six parameter tensors behind a host struct
             desc = rf._field_desc(_C.HEAD_SG, rf.num_g_lobes)
             sg_params = rf._sg_params()
@@ -182,6 +183,14 @@ class FrameRenderer:
         else:
             desc = rf._field_desc(_C.HEAD_NGP, 0)
             head_w = rf.mlp_head.params.detach()
+        if rf.compute_dtype == "fp16":                 # the same job on the field's fp16 copies
+            half = rf._half_copies(torch.float16, head_w, sg_params)
+            table, base_w = half["table"], half["base"]
+            if sg is not None:
+                sg = rf._half_sg_head(half, sg_params)
+            else:
+                head_w = half["head"]
+            job.field_precision = _C.FIELD_FP16
         mode = utils._BG.get(self.bg_color, _C.BG_CUSTOM)
         bk = _C.f32c(render_bkgd.detach().reshape(3).to(dev)) if mode == _C.BG_CUSTOM else None
         rgb = alpha = depth = out5 = None
@@ -202,7 +211,7 @@ class FrameRenderer:
         job.bkgd = bk.data_ptr() if bk is not None else None
         _C.check(_C.lib().qf_frame_render(ri._handle, ctypes.byref(job), _C.stream()), "qf_frame_render")
         ri.fused_frame_done(frame, token)
-        frame._keep = frame._keep + (rgbs, sigmas, table, base_w, head_w, sg_params, bk)   # referenced until their readers ran
+        frame._keep = frame._keep + (rgbs, sigmas, table, base_w, head_w, sg_params, half, bk)   # referenced until their readers ran
         return (out5, None, None, frame) if packed else (rgb, alpha, depth, frame)
 
     @torch.no_grad()

@@ -2,7 +2,7 @@
 concentric shells (most object rays collect more than K = 25 candidates), bf16 tables + MLPs with fp32 accumulate.
 A parity/scale exercise beside bench.py (whose line stays config 2): prints one JSON object with stage times.
 
-    python tools/config3_bench.py --steps 5 --warmup 2 [--dtype fp32] [--intersector bvh]
+    python tools/config3_bench.py --steps 5 --warmup 2 [--dtype fp16|fp32] [--intersector bvh]
 """
 import argparse
 import json
@@ -23,7 +23,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
+    ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16", "fp32"])
     ap.add_argument("--intersector", default="raster", choices=["raster", "bvh"])
     ap.add_argument("--shells", type=int, default=36)
     ap.add_argument("--subdiv", type=int, default=6)

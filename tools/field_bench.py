@@ -1,5 +1,5 @@
 """Field-kernel microbenchmark on the real quadrature points of bench frame 0 (used under rocprofv3 --pmc).
-    python tools/field_bench.py [--iters N] [--order ray|tile]"""
+    python tools/field_bench.py [--iters N] [--order ray|tile] [--dtype bf16|fp16]"""
 import argparse
 import os
 import sys
@@ -15,7 +15,7 @@ import bench
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=10)
-    ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16"])
+    ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16", "fp16"])
     ap.add_argument("--order", default="coherent", choices=["ray", "tile", "tile4", "random", "coherent"])
     ap.add_argument("--physical", action="store_true", help="permute the inputs into the processing order instead of indexing through it")
     ap.add_argument("--deform-log2-t", type=int, default=24)
