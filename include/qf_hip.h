@@ -214,6 +214,18 @@ int qf_deform_field_forward(const qf_grid_desc *grid /* host */, const float *ta
                             const int32_t *order, float *out /* [n] */, float *enc_out /* [n,32] or NULL */,
                             void *stream);
 
+/* fp16 variant: the precision the reference builds this field in (field.py:135-138,157-171: an fp16 tcnn Encoding,
+ * whose fp16 output torch.cat promotes back to fp32 for the fp32 BasicDecoder).  Same arguments and error rules as
+ * qf_deform_field_forward, except table: [rows,2] IEEE binary16 (low half = feature 0).  Numerical contract: rows
+ * converted to fp32 exactly and blended in fp32 as in the fp32 entry; each of the 32 blended features rounded once to
+ * fp16, round-to-nearest-even, overflow to +-inf (torch's .half()), subnormals kept; x01, the constant 1 that carries b1,
+ * every weight and bias and the whole MLP stay fp32.  enc_out receives the rounded features as fp32.               */
+int qf_deform_field_forward_f16(const qf_grid_desc *grid /* host */, const uint16_t *table /* [rows,2] fp16 */,
+                                float scale, int32_t hidden, const float *w1, const float *b1, const float *w2,
+                                const float *b2, const float *wout, const float *bout,
+                                const float *xyz, int64_t n, const int64_t *n_device, const int32_t *order,
+                                float *out /* [n] */, float *enc_out /* [n,32] or NULL */, void *stream);
+
 /* Backward of the decoder of qf_deform_field_forward, fused (training: the deformation field of
  * train_finetune.py:387-399 is optimised together with the radiance field).  enc [n,32] = grid encoding of x01 [n,3],
  * d_out [n] = dL/dfield.  d_enc [n,32] -> qf_grid_encode_backward; d_x01 (optional) = the part of dL/dx01 that enters

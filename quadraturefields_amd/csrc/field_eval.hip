@@ -20,6 +20,7 @@
 #include "field_common.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
@@ -458,7 +459,7 @@ __global__ void sg_features_to_rgb_kernel(const float *features, int64_t stride,
 // step 8: lane quartets 0..2 feed x01.{x,y,z}, quartet 3 feeds the constant 1 that carries b1.
 struct DeformArgs {
     GridArgs grid;
-    const float2 *table;
+    const void *table;      // [rows] of the kernel's row type (DeformRowF32 / DeformRowF16)
     float scale;
     const float *w1, *b1, *w2, *b2, *wout, *bout;
     const float *xyz;
@@ -487,6 +488,37 @@ __device__ float deform_weight_for(const DeformArgs &a, int m, int lane)
     return i == 0 ? a.wout[hidden_col(s, kq)] : 0.0f;
 }
 
+// Table row types of deform_kernel.  fp32 (float2 rows) is the default; fp16 is the reference's own precision
+// (field.py:157-171 builds the tcnn Encoding with dtype=torch.float16 and returns its output as fp16, while x01 and the
+// BasicDecoder stay fp32): half2 rows (low half = feature 0, 4 B gathers) converted to fp32 exactly (v_cvt_f32_f16),
+// blended in fp32 by level_blend, and the 8 blended features rounded ONCE to fp16, round-to-nearest-even (overflow to
+// +-inf, as torch's .half()), before they enter the fp32 MLP and enc_out.  fp16 denormals are kept: the kernel
+// descriptor's float_denorm_mode_16_64 is 3 (flush nothing), as for field_kernel_16.
+struct DeformRowF32 {
+    typedef float2 row;
+    static constexpr bool kRoundF16 = false;
+    static __device__ __forceinline__ float2 unpack(float2 r) { return r; }
+};
+
+struct DeformRowF16 {
+    typedef uint32_t row;
+    static constexpr bool kRoundF16 = true;
+    static __device__ __forceinline__ float2 unpack(uint32_t raw)
+    {
+        const f16x2 h = __builtin_bit_cast(f16x2, raw);
+        return make_float2((float)h.x, (float)h.y);
+    }
+};
+
+// fp32 -> fp16 (RNE) -> fp32 of a feature pair: v_cvt_pk_f16_f32 + 2 x v_cvt_f32_f16
+__device__ __forceinline__ void round_f16_pair(float *f0, float *f1)
+{
+    const f16x2 h = {(_Float16)*f0, (_Float16)*f1};
+    *f0 = (float)h.x;
+    *f1 = (float)h.y;
+}
+
+template <class R>
 __global__ __launch_bounds__(kBlock, 4) void deform_kernel(const DeformArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -554,10 +586,13 @@ __global__ __launch_bounds__(kBlock, 4) void deform_kernel(const DeformArgs a)
             uint32_t idx[8];
             level_indices(lc, x01, y01, z01, idx, frac[j]);
 #pragma unroll
-            for (int c = 0; c < 8; ++c) val[j][c] = a.table[idx[c]];
+            for (int c = 0; c < 8; ++c) val[j][c] = R::unpack(static_cast<const typename R::row *>(a.table)[idx[c]]);
         }
 #pragma unroll
-        for (int j = 0; j < 4; ++j) level_blend(val[j], frac[j], &in[2 * j], &in[2 * j + 1]);
+        for (int j = 0; j < 4; ++j) {
+            level_blend(val[j], frac[j], &in[2 * j], &in[2 * j + 1]);
+            if (R::kRoundF16) round_f16_pair(&in[2 * j], &in[2 * j + 1]);   // the fp16 Encoding output
+        }
         if (a.enc_out && valid) {
 #pragma unroll
             for (int j = 0; j < 4; ++j)
@@ -703,11 +738,14 @@ extern "C" int qf_sg_features_to_rgb(const float *features, int64_t feat_stride,
     return QF_OK;
 }
 
-extern "C" int qf_deform_field_forward(const qf_grid_desc *grid, const float *table, float scale, int32_t hidden,
-                                       const float *w1, const float *b1, const float *w2, const float *b2,
-                                       const float *wout, const float *bout, const float *xyz, int64_t n,
-                                       const int64_t *n_device, const int32_t *order, float *out, float *enc_out,
-                                       void *stream)
+namespace {
+
+// the argument handling and launch of both deformation entry points (same rules for both row types)
+template <class R>
+int deform_forward(const qf_grid_desc *grid, const void *table, float scale, int32_t hidden, const float *w1,
+                   const float *b1, const float *w2, const float *b2, const float *wout, const float *bout,
+                   const float *xyz, int64_t n, const int64_t *n_device, const int32_t *order, float *out,
+                   float *enc_out, void *stream)
 {
     if (!grid || !table || n < 0 || !(scale > 0.0f)) return QF_ERR_INVALID_ARGUMENT;
     if (hidden != 32) return QF_ERR_UNSUPPORTED;
@@ -717,7 +755,7 @@ extern "C" int qf_deform_field_forward(const qf_grid_desc *grid, const float *ta
     if (rc != QF_OK) return rc;
     if (n == 0) return QF_OK;
     if (!xyz || !out) return QF_ERR_INVALID_ARGUMENT;
-    a.table = reinterpret_cast<const float2 *>(table);
+    a.table = table;
     a.scale = scale;
     a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2; a.wout = wout; a.bout = bout;
     a.xyz = xyz;
@@ -731,9 +769,31 @@ extern "C" int qf_deform_field_forward(const qf_grid_desc *grid, const float *ta
     const int64_t cap = (int64_t)qf_cu_count_cached();     // one workgroup per CU, see launch_field
     if (blocks > cap) blocks = cap;
     if (blocks >= 64) blocks &= ~(int64_t)7;
-    hipLaunchKernelGGL(deform_kernel, dim3((unsigned)blocks), dim3(kBlock), lds_bytes, qf_stream(stream), a);
+    hipLaunchKernelGGL(deform_kernel<R>, dim3((unsigned)blocks), dim3(kBlock), lds_bytes, qf_stream(stream), a);
     QF_LAUNCH_CHECK();
     return QF_OK;
+}
+
+}  // namespace
+
+extern "C" int qf_deform_field_forward(const qf_grid_desc *grid, const float *table, float scale, int32_t hidden,
+                                       const float *w1, const float *b1, const float *w2, const float *b2,
+                                       const float *wout, const float *bout, const float *xyz, int64_t n,
+                                       const int64_t *n_device, const int32_t *order, float *out, float *enc_out,
+                                       void *stream)
+{
+    return deform_forward<DeformRowF32>(grid, table, scale, hidden, w1, b1, w2, b2, wout, bout, xyz, n, n_device,
+                                        order, out, enc_out, stream);
+}
+
+extern "C" int qf_deform_field_forward_f16(const qf_grid_desc *grid, const uint16_t *table, float scale,
+                                           int32_t hidden, const float *w1, const float *b1, const float *w2,
+                                           const float *b2, const float *wout, const float *bout, const float *xyz,
+                                           int64_t n, const int64_t *n_device, const int32_t *order, float *out,
+                                           float *enc_out, void *stream)
+{
+    return deform_forward<DeformRowF16>(grid, table, scale, hidden, w1, b1, w2, b2, wout, bout, xyz, n, n_device,
+                                        order, out, enc_out, stream);
 }
 
 extern "C" int qf_grid_mlp_forward(const qf_grid_desc *grid, const float *table, const float *base_w, const float *x01,

@@ -41,7 +41,7 @@ class _DeformTrainFn(torch.autograd.Function):
     def forward(ctx, x, table, w1, b1, w2, b2, wout, bout, module):
         x = _C.f32c(x.detach().reshape(-1, 3))
         enc = torch.empty((x.shape[0], 32), dtype=torch.float32, device=x.device)     # kept for the backward
-        out = module._density_fused(x, None, enc_out=enc)
+        out = module._density_fused(x, None, enc_out=enc, compute_dtype="fp32")      # training is fp32 (class doc)
         ctx.save_for_backward(x, table, w1, b1, w2, b2, wout, bout, enc)
         ctx.module = module
         return out
@@ -77,7 +77,8 @@ class Field(nn.Module):
             raise NotImplementedError("the fused kernel implements the finetune configuration of "
                                       "train_finetune.py:387-399 (relu, hidden 32, output 1, biases)")
         self.output_dim = output_dim
-        self.dtype = torch.float16 if precision == 16 else torch.float32   # kept for API parity; compute is fp32
+        # kept for API parity: ``precision`` selects nothing, ``compute_dtype`` (below) does
+        self.dtype = torch.float16 if precision == 16 else torch.float32
         self.scale = scale
         self.register_buffer("center", torch.zeros(1, 3))
         self.register_buffer("xyz_min", -torch.ones(1, 3) * scale)
@@ -95,9 +96,48 @@ class Field(nn.Module):
                                           activation=torch.nn.ReLU(), bias=bias, num_layers=2,
                                           hidden_dim=hidden_size, skip=[], bias_last=bias_last)
 
+    #: Precision of the fused inference kernel: "fp32" (default; parity with the fp32 oracle to ~1e-6) or "fp16", the
+    #: precision the reference builds this field in (``Field(precision=16)``, field.py:135-138,157-171: an fp16 tcnn
+    #: ``Encoding`` whose fp16 output ``torch.cat`` promotes to fp32 for the fp32 ``BasicDecoder``): fp16 table, the 32
+    #: encoding outputs rounded to fp16, x01 and the whole MLP fp32 (``qf_deform_field_forward_f16``).  ``precision=``
+    #: does not select it -- a drop-in script that wants the reference's numbers sets ``Field.compute_dtype = "fp16"``
+    #: once, before it builds its field.  Any other value raises ValueError at the first evaluation.  Only inference
+    #: (autograd not recording) honours "fp16"; the training routes and ``field_grad`` are fp32 whatever it says.  The
+    #: fp16 table is a copy of the fp32 master ``xyz_encoder.params``, kept while "fp16" is in use and rebuilt when the
+    #: parameters change (an optimiser step -- torch's or ``optim.Adam`` -- or ``load_state_dict``): 0.41 GB more resident
+    #: at the scripts' log2_T = 24.  Setting the instance's ``compute_dtype`` to anything else releases it at once; a
+    #: class-level switch (``Field.compute_dtype = "fp32"``) releases it at the field's next evaluation.
+    compute_dtype = "fp32"
+    COMPUTE_DTYPES = ("fp32", "fp16")
+
+    def __setattr__(self, name, value):
+        if name == "compute_dtype" and value != "fp16":
+            self.__dict__.pop("_half_cache", None)          # the fp16 table goes now, not at the next evaluation
+        super().__setattr__(name, value)
+
+    def _check_compute_dtype(self):
+        if self.compute_dtype not in self.COMPUTE_DTYPES:
+            raise ValueError(f"compute_dtype must be one of {', '.join(map(repr, self.COMPUTE_DTYPES))}, "
+                             f"got {self.compute_dtype!r}")
+        if self.compute_dtype == "fp32":
+            self._half_cache = None
+
+    def _half_table(self):
+        """fp16 (round-to-nearest-even) copy of the fp32 table, keyed by the parameter's storage and version: built
+        once per parameter change, never per call (203 M values at log2_T = 24)."""
+        p = self.xyz_encoder.params
+        key = (p.data_ptr(), p._version)
+        cache = getattr(self, "_half_cache", None)
+        if cache is None or cache[0] != key:
+            self._half_cache = cache = None    # the old copy goes before the new one is allocated
+            cache = (key, p.detach().to(torch.float16).contiguous())
+            self._half_cache = cache
+        return cache[1]
+
     def density(self, x, order=None, n_device=None):
         """[N,3] in [-scale, scale] -> [N,1].  field.py:186-203, one fused launch.  ``order`` (extension): int32
         processing permutation (``RayIntersector.coherent_order``), cache locality only."""
+        self._check_compute_dtype()
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
             if self.fused_backward and not x.requires_grad:
                 d = self.decoder_field       # parameters train, the input is data: fused first-order backward
@@ -112,18 +152,23 @@ class Field(nn.Module):
     #: (``_DeformTrainFn``); the input-gradient / second-order route always goes through the hash-grid autograd Function.
     fused_backward = True
 
-    def _density_fused(self, x, order=None, enc_out=None, n_device=None):
+    def _density_fused(self, x, order=None, enc_out=None, n_device=None, compute_dtype=None):
+        """The inference kernel; ``compute_dtype`` None = the field's own."""
         x = _C.f32c(x.reshape(-1, 3))
         n = x.shape[0]
         out = torch.empty((n,), dtype=torch.float32, device=x.device)
         d = self.decoder_field
         w = [_C.f32c(t.detach()) for t in (d.layers[0].weight, d.layers[0].bias, d.layers[1].weight,
                                            d.layers[1].bias, d.lout.weight, d.lout.bias)]
-        _C.check(_C.lib().qf_deform_field_forward(
-            self.xyz_encoder.grid.desc, _C.ptr(self.xyz_encoder.params.detach()), float(self.scale), 32,
+        if (compute_dtype or self.compute_dtype) == "fp16":
+            name, table = "qf_deform_field_forward_f16", self._half_table()
+        else:
+            name, table = "qf_deform_field_forward", self.xyz_encoder.params.detach()
+        _C.check(getattr(_C.lib(), name)(
+            self.xyz_encoder.grid.desc, _C.ptr(table), float(self.scale), 32,
             *[_C.ptr(t) for t in w], _C.ptr(x), n, _C.ptr(n_device, torch.int64),
             _C.ptr(order, torch.int32) if order is not None and order.shape[0] == n else None,
-            _C.ptr(out), _C.ptr(enc_out), _C.stream()), "qf_deform_field_forward")
+            _C.ptr(out), _C.ptr(enc_out), _C.stream()), name)
         return out[:, None]
 
     def field(self, x, order=None, n_device=None):

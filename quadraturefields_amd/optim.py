@@ -51,4 +51,7 @@ class Adam(torch.optim.Optimizer):
                         _C.ptr(p.data), _C.ptr(g), _C.ptr(state["exp_avg"]), _C.ptr(state["exp_avg_sq"]), p.numel(),
                         float(group["lr"]), float(beta1), float(beta2), float(group["eps"]), float(group["weight_decay"]),
                         1 if group["maximize"] else 0, int(state["step"]), _C.stream()), "qf_adam_step")
+                # the kernel wrote through raw pointers: move the version counters as torch's in-place update does, so
+                # that caches keyed by (data_ptr, _version) -- the fields' 16-bit parameter copies -- see the step
+                torch.autograd.graph.increment_version([p, state["exp_avg"], state["exp_avg_sq"]])
         return loss

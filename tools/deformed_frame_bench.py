@@ -5,6 +5,7 @@ fp32 table, + 35-32-32-1 MLP), re-sorted per ray, shaded and composited -- throu
 evaluation): prints one JSON object.
 
     python tools/deformed_frame_bench.py --steps 10 --warmup 2 [--scaling 0.0434] [--deform-log2-t 24]
+        [--deform-dtype fp32|fp16]
 """
 import argparse
 import json
@@ -26,6 +27,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--scaling", type=float, default=0.0434)
     ap.add_argument("--deform-log2-t", type=int, default=24)
+    ap.add_argument("--deform-dtype", default="fp32", choices=["fp32", "fp16"], help="Field.compute_dtype")
     args = ap.parse_args()
     torch.set_grad_enabled(False)
     from quadraturefields_amd import synthetic
@@ -38,6 +40,7 @@ def main():
                 hidden_size=32, num_features=2, back_prop=False, nl="relu")
     net.load_state_dict(synthetic.seeded_deform_state(net.xyz_encoder.grid.n_params), strict=False)
     net = net.to(device)
+    net.compute_dtype = args.deform_dtype
     fr = FrameRenderer(mi, field, field_net=net)
     n_frames = args.steps + args.warmup
     cams = synthetic.orbit_cameras(n_frames, seed=42)
@@ -59,7 +62,8 @@ def main():
                     f"scaling {args.scaling}",
         "rays_per_s": n_rays * args.steps / el, "ms_per_frame": el / args.steps * 1e3,
         "points_per_frame": pts / args.steps,
-        "deform_table_gb": net.xyz_encoder.grid.n_params * 4 / 1e9}))
+        "deform_dtype": args.deform_dtype,
+        "deform_table_gb": net.xyz_encoder.grid.n_params * (2 if args.deform_dtype == "fp16" else 4) / 1e9}))
 
 
 if __name__ == "__main__":

@@ -1,5 +1,6 @@
 """Field-kernel microbenchmark on the real quadrature points of bench frame 0 (used under rocprofv3 --pmc).
-    python tools/field_bench.py [--iters N] [--order ray|tile] [--dtype bf16|fp16]"""
+    python tools/field_bench.py [--iters N] [--order ray|tile] [--dtype bf16|fp16]
+    python tools/field_bench.py --stage deform [--deform-log2-t 24] [--dtype fp16]   (the deformation field: fp32 | fp16)"""
 import argparse
 import os
 import sys
@@ -21,6 +22,8 @@ def main():
     ap.add_argument("--deform-log2-t", type=int, default=24)
     ap.add_argument("--stage", default="field", choices=["field", "traverse", "raster", "pack", "composite", "frame", "deform"])
     args = ap.parse_args()
+    if args.stage == "deform" and args.dtype not in ("fp32", "fp16"):
+        ap.error(f"--stage deform has no {args.dtype} mode (Field.COMPUTE_DTYPES: fp32, fp16)")
     torch.set_grad_enabled(False)
     dev = torch.device("cuda:0")
     from quadraturefields_amd import synthetic
@@ -64,6 +67,7 @@ def main():
                     hidden_size=32, num_features=2, back_prop=False, nl="relu")
         net.load_state_dict(synthetic.seeded_deform_state(net.xyz_encoder.grid.n_params), strict=False)
         net = net.to(dev)
+        net.compute_dtype = args.dtype
 
     def run():
         if args.stage == "deform":
@@ -91,7 +95,7 @@ def main():
     b.record()
     torch.cuda.synchronize()
     ms = a.elapsed_time(b) / args.iters
-    print(f"stage={args.stage} n_points={n} rays={o.shape[0]} ms={ms:.4f} points/s={n / ms * 1e3:.4e} rays/s={o.shape[0] / ms * 1e3:.4e}")
+    print(f"stage={args.stage} dtype={args.dtype} n_points={n} rays={o.shape[0]} ms={ms:.4f} points/s={n / ms * 1e3:.4e} rays/s={o.shape[0] / ms * 1e3:.4e}")
 
 
 if __name__ == "__main__":
