@@ -497,6 +497,24 @@ int qf_generate_rays(const qf_camera *cam /* host */, int32_t opengl, float *ori
  * torch_scatter.scatter_max as used for triangle pruning (prune_mesh_after_finetuning.py:355-357).              */
 int qf_scatter_max(const float *values, const int64_t *index, int64_t n, int64_t n_out, float *out, void *stream);
 
+/* Texel-position map of a UV-mapped mesh (the fill of the reference's UV stage, parameterization_utils.py:97-153;
+ * rules in DESIGN.md section 3.6): out [height, width, 3] fp32 = the 3-D point of the mesh each texel stands for, and
+ * tri_size [n_faces] = the number of texels each face's cover holds.  Inputs are device arrays: vertices [n_vertices,3]
+ * fp64, faces [n_faces,3] int64, uv [n_vertices,2] fp64 (uv[:,0] selects the row).  A texel no face covers and no
+ * edge touches gets face n_faces-1's centroid (QF_UNTOUCHED_LAST_FACE, the reference's) or 0 (QF_UNTOUCHED_ZERO).
+ * Deterministic: the result is bit-identical run to run.
+ * workspace: device scratch of at least qf_texel_positions_workspace_bytes(n_faces, height, width) bytes (that
+ * function returns -1 for sizes qf_texel_positions refuses).
+ * QF_ERR_INVALID_ARGUMENT before any launch for: height or width outside [1, 16384], height*width >= 2^31,
+ * n_faces < 1, n_vertices < 1, an unknown untouched mode, a NULL pointer, a short workspace.
+ * The CALLER must guarantee 0 <= faces < n_vertices and finite uv: they live in device memory and are not checked. */
+#define QF_UNTOUCHED_LAST_FACE 0
+#define QF_UNTOUCHED_ZERO 1
+int64_t qf_texel_positions_workspace_bytes(int64_t n_faces, int32_t height, int32_t width);
+int qf_texel_positions(const double *vertices, int64_t n_vertices, const int64_t *faces, int64_t n_faces,
+                       const double *uv, int32_t height, int32_t width, int32_t untouched, float *out,
+                       int64_t *tri_size, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* Offsets of the packed samples: ray_offset[r] = sum_{q<r} min(hit_count[q], max_hits) for r = 0..n_rays, i.e.
  * ray_offset[n_rays] is the total sample count (left in device memory, so the caller can start qf_pack_samples before
  * reading it back).  Replaces the index bookkeeping of mesh_utils.py:359-366 (np.argsort / boolean masks on the host).

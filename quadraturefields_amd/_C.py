@@ -22,6 +22,7 @@ QF_TEXEL_RECORD_BYTES = 64
 QF_TEXEL_TRIANGLE_RECORD_BYTES = 128
 HEAD_NONE, HEAD_NGP, HEAD_SG, HEAD_SG_FEATURES = 0, 1, 2, 3
 FIELD_FP32, FIELD_BF16, FIELD_FP16 = 0, 1, 2          # qf_frame_job.field_precision
+UNTOUCHED_LAST_FACE, UNTOUCHED_ZERO = 0, 1            # qf_texel_positions
 BG_WHITE, BG_BLACK, BG_CUSTOM, BG_NONE = 0, 1, 2, 3
 
 
@@ -134,6 +135,8 @@ _SIGNATURES = {
                                     c_float, _P, _P, _P, _P, _P]),
     "qf_generate_rays": (c_int, [POINTER(Camera), c_int32, _P, _P, _P]),
     "qf_scatter_max": (c_int, [_P, _P, c_int64, c_int64, _P, _P]),
+    "qf_texel_positions_workspace_bytes": (c_int64, [c_int64, c_int32, c_int32]),
+    "qf_texel_positions": (c_int, [_P, c_int64, _P, c_int64, _P, c_int32, c_int32, c_int32, _P, _P, _P, c_int64, _P]),
     "qf_sample_offsets_temp_bytes": (c_int64, [c_int64]),
     "qf_sample_offsets": (c_int, [_P, c_int64, c_int32, _P, _P, c_int64, _P]),
     "qf_frame_offsets_temp_bytes": (c_int64, [c_int64]),

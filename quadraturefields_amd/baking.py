@@ -3,6 +3,8 @@
 * ``bake_texture_images``: ``examples/bake_texture_images_shelly.py:270-294`` -- evaluate the SG field's features
   and the density field at every valid texel of ``V`` (texel -> 3-D point, all-zero rows are empty), quantise with
   the reference's codecs and scatter into the uint8 texture set.
+* ``texel_positions``: the texel-position map ``V`` itself from a UV-mapped mesh -- the fill of the reference's UV stage
+  (``examples/parameterization_utils.py:97-153``), one HIP call (``qf_texel_positions``).
 * ``triangle_max_weights`` / ``prune_faces``: ``examples/prune_mesh_after_finetuning.py:323-373`` -- per-triangle
   maximum compositing weight over the training views, faces below 1e-3 dropped.
 """
@@ -13,9 +15,63 @@ from . import _C
 from .mesh_io import TriMesh
 
 
+UNTOUCHED_MODES = {"last_face": _C.UNTOUCHED_LAST_FACE, "zero": _C.UNTOUCHED_ZERO}
+MAX_TEXTURE_SIDE = 16384
+
+
+@torch.no_grad()
+def texel_positions(mesh: TriMesh, height: int, width: int = None, untouched: str = "last_face", device=None):
+    """Texel-position map of a UV-mapped mesh: ``(V, tri_size)`` with V a device float32 tensor [height, width, 3] (the
+    3-D point each texel stands for, what the reference saves as ``V_{size}.npy``) and tri_size a device int64 tensor
+    [F] (texels in each face's cover).  ``uv[:,0]`` selects the row.  ``untouched``: what a texel no face covers and no
+    edge touches gets -- "last_face" (the reference: the centroid of face F-1) or "zero" (left empty, so that
+    ``bake_texture_images`` skips it).  The host only validates and uploads; the map is computed on the device."""
+    width = height if width is None else width
+    uv = getattr(getattr(mesh, "visual", None), "uv", None)
+    if uv is None:
+        raise ValueError("texel_positions needs a mesh with per-vertex UVs (mesh.visual.uv)")
+    if untouched not in UNTOUCHED_MODES:
+        raise ValueError(f"untouched must be one of {sorted(UNTOUCHED_MODES)}, got {untouched!r}")
+    for name, n in (("height", height), ("width", width)):
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= n <= MAX_TEXTURE_SIDE:
+            raise ValueError(f"{name} must be an integer in [1, {MAX_TEXTURE_SIDE}], got {n!r}")
+    height, width = int(height), int(width)
+    if height * width >= 1 << 31:
+        raise ValueError(f"height * width must be below 2^31, got {height} x {width}")
+    vertices = np.ascontiguousarray(mesh.vertices, dtype=np.float64).reshape(-1, 3)
+    faces = np.ascontiguousarray(mesh.faces, dtype=np.int64).reshape(-1, 3)
+    uv = np.ascontiguousarray(uv, dtype=np.float64)
+    if uv.shape != (vertices.shape[0], 2):
+        raise ValueError(f"uv must be [V, 2] = [{vertices.shape[0]}, 2], got {list(uv.shape)}")
+    if faces.shape[0] < 1:
+        raise ValueError("texel_positions needs at least one face")
+    if faces.min() < 0 or faces.max() >= vertices.shape[0]:           # the C entry cannot check device indices
+        raise ValueError(f"face indices must lie in [0, {vertices.shape[0]})")
+    if not np.isfinite(uv).all():
+        raise ValueError("uv must be finite")
+    dev = _C.resolve_device(device if device is not None else "cuda")
+    n_faces = faces.shape[0]
+    ws_bytes = int(_C.lib().qf_texel_positions_workspace_bytes(n_faces, height, width))
+    v_d = torch.from_numpy(vertices).to(dev)
+    f_d = torch.from_numpy(faces).to(dev)
+    uv_d = torch.from_numpy(uv).to(dev)
+    out = torch.empty((height, width, 3), dtype=torch.float32, device=dev)
+    tri_size = torch.empty((n_faces,), dtype=torch.int64, device=dev)
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _C.check(_C.lib().qf_texel_positions(_C.ptr(v_d), vertices.shape[0], _C.ptr(f_d), n_faces, _C.ptr(uv_d),
+                                             height, width, UNTOUCHED_MODES[untouched], _C.ptr(out), _C.ptr(tri_size),
+                                             _C.ptr(ws), ws_bytes, _C.stream()), "qf_texel_positions")
+    return out, tri_size
+
+
 @torch.no_grad()
 def bake_texture_images(radiance_field_sg, radiance_field, V, compressor, batch_size: int = 100000):
-    """Fill ``compressor``'s texture maps in place; returns the boolean texel mask (V.sum(-1) != 0)."""
+    """Fill ``compressor``'s texture maps in place; returns the boolean texel mask (V.sum(-1) != 0).  ``V`` is a numpy
+    array (or anything ``np.asarray`` takes) or a device tensor -- ``texel_positions``' output -- which then stays on
+    the device: the mask comes back as a device tensor."""
+    if isinstance(V, torch.Tensor) and V.is_cuda:
+        return _bake_device(radiance_field_sg, radiance_field, V, compressor, batch_size)
     V = np.asarray(V, dtype=np.float32)
     mask = ~(V.sum(-1) == 0)
     ind = np.argwhere(mask)
@@ -27,6 +83,20 @@ def bake_texture_images(radiance_field_sg, radiance_field, V, compressor, batch_
         density = radiance_field.query_density(pts)
         features[..., -1] = density.flatten()
         compressor.load_features_into_maps(features, torch.from_numpy(rows).to(dev))
+    return mask
+
+
+def _bake_device(radiance_field_sg, radiance_field, V, compressor, batch_size):
+    V = V.to(compressor.device, torch.float32)
+    mask = ((V[..., 0] + V[..., 1]) + V[..., 2]) != 0                  # numpy's float32 sum order
+    ind = torch.nonzero(mask)                                           # row-major, as np.argwhere
+    for b in range(0, ind.shape[0], batch_size):
+        rows = ind[b:b + batch_size]
+        pts = V[rows[:, 0], rows[:, 1]].contiguous()
+        features = radiance_field_sg.features(pts)
+        density = radiance_field.query_density(pts)
+        features[..., -1] = density.flatten()
+        compressor.load_features_into_maps(features, rows)
     return mask
 
 

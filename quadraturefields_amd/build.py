@@ -16,7 +16,8 @@ OBJ_DIR = os.path.join(CSRC, "_obj")
 LIB_PATH = os.path.join(PKG_DIR, "libqf_hip.so")
 ARCH = "gfx950"
 
-# (source, extra flags).  exact.hip carries every integer-deciding comparison: no FMA contraction.
+# (source, extra flags).  exact.hip carries every integer-deciding comparison and texel_fill.hip the fp64 rules of the
+# texel-position map: no FMA contraction.
 SOURCES = [
     ("field_eval.hip", []),
     ("field_eval_bf16.hip", []),
@@ -26,6 +27,7 @@ SOURCES = [
     ("composite.hip", []),
     ("optim.hip", []),
     ("exact.hip", ["-ffp-contract=off"]),
+    ("texel_fill.hip", ["-ffp-contract=off"]),
     ("bvh_build.cpp", ["-x", "hip"]),
     ("misc.cpp", ["-x", "hip"]),
     ("frame.cpp", ["-x", "hip"]),
