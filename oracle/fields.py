@@ -181,13 +181,31 @@ class NGPWeights:
     n_lobes: int = 0
 
 
+class _TruncExp(torch.autograd.Function):
+    """ngp.py:145-159: forward exp(x), unclamped; gradient g * exp(min(x, 15)) (a NaN stays NaN)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        ctx.save_for_backward(x)
+        return torch.exp(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, = ctx.saved_tensors
+        return g * torch.exp(torch.clamp(x, max=15.0))
+
+
+def trunc_exp(x: Tensor) -> Tensor:
+    return _TruncExp.apply(x)
+
+
 def query_density(x: Tensor, wts: NGPWeights, return_feat: bool = False):
-    """ngp.py:757-779 / 404-426.  density = exp(raw - 1) * selector (B-6)."""
+    """ngp.py:757-779 / 404-426.  density = trunc_exp(raw - 1) * selector (B-6)."""
     selector, x01 = normalize_to_aabb(x, wts.aabb)
     enc = hash_encode(x01.reshape(-1, 3), wts.table, wts.levels)
     out = mlp_nobias(enc, wts.base)
     raw, feat = out[:, :1], out[:, 1:16]
-    density = torch.exp(raw - 1.0) * selector[:, None]
+    density = trunc_exp(raw - 1.0) * selector[:, None]
     return (density, feat) if return_feat else density
 
 

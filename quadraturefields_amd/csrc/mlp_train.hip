@@ -35,6 +35,10 @@ struct TrainArgs {
 
 __device__ __forceinline__ f32x4 mfma(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
+// Derivative of the density activation trunc_exp: the forward is exp(x), unclamped, but the
+// gradient is exp(min(x, 15)), so it stays finite where the forward overflows.  A NaN stays NaN, as torch.clamp keeps it.
+__device__ __forceinline__ float dtrunc_exp(float x) { return expf(x > 15.0f ? 15.0f : x); }
+
 __device__ __forceinline__ int img_index(int m, int lane) { return ((((m >> 2) << 6) + lane) << 2) + (m & 3); }
 
 // column of the head's first layer fed by register 4+r of lane quartet kq: [geo | 1] part of [SH16 | geo15 | 1]
@@ -171,7 +175,7 @@ __global__ __launch_bounds__(kTrainBlock, 1) void ngp_mlp_backward_kernel(const 
             ob = mfma(w4[3], h[q][3], ob);
         }
         const f32x4 base_out = oa + ob;
-        const float density = a.sel[pt] ? expf(base_out[0] - 1.0f) : 0.0f;
+        const float ddensity = a.sel[pt] ? dtrunc_exp(base_out[0] - 1.0f) : 0.0f;
         const float dx = a.dirs[pt * 3 + 0], dy = a.dirs[pt * 3 + 1], dzv = a.dirs[pt * 3 + 2];
         const float ux = ((dx + 1.0f) / 2.0f) * 2.0f - 1.0f, uy = ((dy + 1.0f) / 2.0f) * 2.0f - 1.0f,
                     uz = ((dzv + 1.0f) / 2.0f) * 2.0f - 1.0f;
@@ -254,7 +258,7 @@ __global__ __launch_bounds__(kTrainBlock, 1) void ngp_mlp_backward_kernel(const 
             db = mfma(w4[3], dz1[q][3], db);
         }
         f32x4 dout = da + db;
-        if (g == 0) dout[0] = valid ? a.d_sigma[pt] * density : 0.0f;   // d exp(raw - 1) * selector
+        if (g == 0) dout[0] = valid ? a.d_sigma[pt] * ddensity : 0.0f;   // d trunc_exp(raw - 1) * selector
         if (!valid) dout = zero;
 
         // ---------------------------------------------------------------- head weight gradients
@@ -476,7 +480,7 @@ __global__ __launch_bounds__(kTrainBlock, 1) void sg_mlp_backward_kernel(const S
             ob = mfma(w4[3], h[q][3], ob);
         }
         const f32x4 base_out = oa + ob;
-        const float density = a.sel[pt] ? expf(base_out[0] - 1.0f) : 0.0f;
+        const float ddensity = a.sel[pt] ? dtrunc_exp(base_out[0] - 1.0f) : 0.0f;
         f32x4 in = base_out;
         if (g == 0) in[0] = 1.0f;                  // bias slot
         f32x4 h1[4] = {zero, zero, zero, zero};
@@ -554,7 +558,7 @@ __global__ __launch_bounds__(kTrainBlock, 1) void sg_mlp_backward_kernel(const S
             db = mfma(w4[3], dz1[q][3], db);
         }
         f32x4 dout = da + db;                      // d out16 rows 4g + r (row 0: see below)
-        if (g == 0) dout[0] = valid ? a.d_sigma[pt] * density : 0.0f;
+        if (g == 0) dout[0] = valid ? a.d_sigma[pt] * ddensity : 0.0f;
         if (!valid) dout = zero;
 
         // ---------------------------------------------------------------- decoder weight / bias gradients

@@ -21,9 +21,25 @@ from .. import _C
 from .. import tinycudann as tcnn
 
 
+class _TruncExp(torch.autograd.Function):
+    """The reference's density activation (ngp.py:145-159): the forward is a plain exp, unclamped; the gradient is
+    g * exp(min(x, 15)), so it stays finite where the forward overflows.  The backward is built from torch ops, so a
+    graph of it can be recorded (``create_graph``); its own derivative w.r.t. x is 0 above the clamp."""
+
+    @staticmethod
+    def forward(ctx, x):
+        ctx.save_for_backward(x)
+        return torch.exp(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, = ctx.saved_tensors
+        return g * torch.exp(torch.clamp(x, max=15.0))
+
+
 def trunc_exp(x):
-    """Forward of the reference's _TruncExp (ngp.py:146-153): a plain exp."""
-    return torch.exp(x)
+    """exp(x) forward, exp(min(x, 15)) gradient: the reference's ``trunc_exp``."""
+    return _TruncExp.apply(x)
 
 
 class BasicDecoder(nn.Module):
@@ -253,11 +269,11 @@ class _FusedFieldBase(nn.Module):
         selector, x01 = self.normalize(x)
         out = self.mlp_base(x01.reshape(-1, self.num_dim))
         raw, feat = out[:, :1], out[:, 1:1 + self.geo_feat_dim]
-        density = torch.exp(raw - 1.0) * selector.reshape(-1, 1)
+        density = trunc_exp(raw - 1.0) * selector.reshape(-1, 1)
         return density, feat
 
     def query_density(self, x, return_feat: bool = False):
-        """density = exp(raw - 1) * selector, [..,1] (+ the 15 geometry features).  ngp.py:757-779."""
+        """density = trunc_exp(raw - 1) * selector, [..,1] (+ the 15 geometry features).  ngp.py:757-779."""
         lead = list(x.shape[:-1])
         if self._recording(x):
             density, feat = self._query_density_train(x)
