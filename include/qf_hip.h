@@ -515,6 +515,25 @@ int qf_texel_positions(const double *vertices, int64_t n_vertices, const int64_t
                        const double *uv, int32_t height, int32_t width, int32_t untouched, float *out,
                        int64_t *tri_size, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* Marching cubes over a dense fp32 volume [n0, n1, n2] in C order (axis 2 fastest): the mesh extraction of the
+ * reference's examples/marching_cubes.py (scikit-image's marching_cubes on the host there; rules in DESIGN.md
+ * section 3.8).  Vertices are fp32 [V,3] in array-index coordinates (verts[:,0] is the axis-0 index), faces int32
+ * [F,3]; (v1 - v0) x (v2 - v0) points from inside (v - level > 0) to outside.  Deterministic: bit-identical run to run.
+ * Two calls, so that the caller allocates once: qf_marching_cubes_count writes counts[3] (device int64) = vertices,
+ * faces and grid points whose v - level is not finite; after reading them back, qf_marching_cubes_emit with the same
+ * volume, level and workspace writes at most n_verts vertices and n_faces faces (pass the counts).  A volume with a
+ * non-finite sample gives an unspecified mesh.
+ * workspace: device scratch of at least qf_marching_cubes_workspace_bytes(n0, n1, n2) bytes, 4 per grid point plus
+ * 24 per 4096 points (that function returns -1 for sizes the entries refuse).
+ * QF_ERR_INVALID_ARGUMENT before any launch for: a dimension outside [2, 2^24], n0 n1 n2 >= 2^31, a non-finite
+ * level, a NULL pointer, a short workspace, n_verts or n_faces outside [0, 2^31).                                */
+int64_t qf_marching_cubes_workspace_bytes(int64_t n0, int64_t n1, int64_t n2);
+int qf_marching_cubes_count(const float *volume, int64_t n0, int64_t n1, int64_t n2, float level, void *workspace,
+                            int64_t workspace_bytes, int64_t *counts, void *stream);
+int qf_marching_cubes_emit(const float *volume, int64_t n0, int64_t n1, int64_t n2, float level,
+                           const void *workspace, int64_t workspace_bytes, float *verts, int64_t n_verts,
+                           int32_t *faces, int64_t n_faces, void *stream);
+
 /* Offsets of the packed samples: ray_offset[r] = sum_{q<r} min(hit_count[q], max_hits) for r = 0..n_rays, i.e.
  * ray_offset[n_rays] is the total sample count (left in device memory, so the caller can start qf_pack_samples before
  * reading it back).  Replaces the index bookkeeping of mesh_utils.py:359-366 (np.argsort / boolean masks on the host).

@@ -137,6 +137,9 @@ _SIGNATURES = {
     "qf_scatter_max": (c_int, [_P, _P, c_int64, c_int64, _P, _P]),
     "qf_texel_positions_workspace_bytes": (c_int64, [c_int64, c_int32, c_int32]),
     "qf_texel_positions": (c_int, [_P, c_int64, _P, c_int64, _P, c_int32, c_int32, c_int32, _P, _P, _P, c_int64, _P]),
+    "qf_marching_cubes_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64]),
+    "qf_marching_cubes_count": (c_int, [_P, c_int64, c_int64, c_int64, c_float, _P, c_int64, _P, _P]),
+    "qf_marching_cubes_emit": (c_int, [_P, c_int64, c_int64, c_int64, c_float, _P, c_int64, _P, c_int64, _P, c_int64, _P]),
     "qf_sample_offsets_temp_bytes": (c_int64, [c_int64]),
     "qf_sample_offsets": (c_int, [_P, c_int64, c_int32, _P, _P, c_int64, _P]),
     "qf_frame_offsets_temp_bytes": (c_int64, [c_int64]),

@@ -17,7 +17,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libqf_hip.so")
 ARCH = "gfx950"
 
 # (source, extra flags).  exact.hip carries every integer-deciding comparison and texel_fill.hip the fp64 rules of the
-# texel-position map: no FMA contraction.
+# texel-position map, marching_cubes.hip the fp32 vertex rule and the fp64 face decider: no FMA contraction.
 SOURCES = [
     ("field_eval.hip", []),
     ("field_eval_bf16.hip", []),
@@ -28,6 +28,7 @@ SOURCES = [
     ("optim.hip", []),
     ("exact.hip", ["-ffp-contract=off"]),
     ("texel_fill.hip", ["-ffp-contract=off"]),
+    ("marching_cubes.hip", ["-ffp-contract=off"]),
     ("bvh_build.cpp", ["-x", "hip"]),
     ("misc.cpp", ["-x", "hip"]),
     ("frame.cpp", ["-x", "hip"]),

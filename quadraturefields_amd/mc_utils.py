@@ -1,0 +1,145 @@
+"""Mesh extraction of the reference's ``examples/marching_cubes.py`` on the device.
+
+The reference smooths and normalises its saved grids on the GPU, copies the 1024^3 volume to the host and runs
+scikit-image's marching cubes there, twice: over ``sin(omega * q)`` for the nested quadrature surfaces and over the NeRF
+density.  Here the marching cubes is the HIP kernel of ``csrc/marching_cubes.hip`` (``qf_marching_cubes_count`` /
+``qf_marching_cubes_emit``, rules in DESIGN.md section 3.8); the steps around it stay torch ops on the device.
+"""
+import math
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from . import _C
+from .mesh_io import TriMesh
+from .parameterization_utils import concatenate_meshes
+
+
+def marching_cubes(volume: torch.Tensor, level: float):
+    """``(verts, faces)``: device fp32 [V,3] in array-index coordinates (``verts[:,0]`` is the axis-0 index) and int32
+    [F,3], faces wound from inside (``volume > level``) to outside.  ``volume`` is a device fp32 or fp16 [n0,n1,n2]
+    tensor (fp16 is widened exactly).  Raises ValueError for a host tensor, a shape that is not 3-D with every
+    dimension >= 2 (or is too large), a non-finite level, a non-finite sample, or totals that do not fit int32."""
+    if not isinstance(volume, torch.Tensor):
+        raise TypeError("volume must be a torch.Tensor")
+    if not volume.is_cuda:
+        raise ValueError("marching_cubes needs a device tensor (quadraturefields_amd has no CPU fallback)")
+    if volume.ndim != 3 or min(volume.shape) < 2:
+        raise ValueError(f"volume must be 3-D with every dimension >= 2, got shape {tuple(volume.shape)}")
+    if volume.dtype not in (torch.float32, torch.float16):
+        raise TypeError(f"volume must be float32 or float16, got {volume.dtype}")
+    level32 = float(np.float32(level))
+    if not math.isfinite(level32):
+        raise ValueError(f"level must be finite in fp32, got {level}")
+    vol = volume.to(torch.float32).contiguous()
+    n0, n1, n2 = vol.shape
+    lib = _C.lib()
+    ws_bytes = int(lib.qf_marching_cubes_workspace_bytes(n0, n1, n2))
+    if ws_bytes < 0:
+        raise ValueError(f"volume shape {tuple(vol.shape)} is refused (each dimension <= 2^24, n0 n1 n2 < 2^31)")
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=vol.device)
+    counts = torch.empty((3,), dtype=torch.int64, device=vol.device)
+    with torch.cuda.device(vol.device):
+        _C.check(lib.qf_marching_cubes_count(_C.ptr(vol), n0, n1, n2, level32, _C.ptr(ws), ws_bytes, _C.ptr(counts),
+                                             _C.stream()), "qf_marching_cubes_count")
+        n_verts, n_faces, n_bad = counts.tolist()
+        if n_bad:
+            raise ValueError(f"volume has {n_bad} samples whose difference from the level is not finite")
+        if n_verts >= 2 ** 31 or n_faces >= 2 ** 31:
+            raise ValueError(f"the mesh has {n_verts} vertices and {n_faces} faces; both must be < 2^31")
+        verts = torch.empty((n_verts, 3), dtype=torch.float32, device=vol.device)
+        faces = torch.empty((n_faces, 3), dtype=torch.int32, device=vol.device)
+        _C.check(lib.qf_marching_cubes_emit(_C.ptr(vol), n0, n1, n2, level32, _C.ptr(ws), ws_bytes, _C.ptr(verts),
+                                            n_verts, _C.ptr(faces), n_faces, _C.stream()), "qf_marching_cubes_emit")
+    return verts, faces
+
+
+def _to_device(x, device) -> torch.Tensor:
+    t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.asarray(x))
+    return t.to(device=device, dtype=torch.float32)
+
+
+def gaussian_kernel_1d(sigma: float, size: int = 5) -> torch.Tensor:
+    """The normalised 1-D factor of ``field_utils.GaussianSmoothing``'s product kernel (fp32, as it is built there):
+    the normalised 3-D kernel is the product of three of these."""
+    x = torch.arange(size, dtype=torch.float32)
+    g = 1 / (sigma * math.sqrt(2 * math.pi)) * torch.exp(-((x - (size - 1) / 2) / sigma) ** 2 / 2)
+    return g / g.sum()
+
+
+def smooth(grid: torch.Tensor, sigma: float) -> torch.Tensor:
+    """``GaussianSmoothing(1, 5, sigma, dim=3)`` with ``padding="same"`` (zero padding) as three 1-D passes."""
+    w = gaussian_kernel_1d(sigma).tolist()
+    x = grid
+    for axis in range(3):
+        n = x.shape[axis]
+        out = torch.zeros_like(x)
+        for k, wk in enumerate(w):
+            off = k - 2                                        # out[i] += w[k] * x[i + off]
+            m = n - abs(off)
+            if m <= 0:
+                continue
+            out.narrow(axis, max(-off, 0), m).add_(x.narrow(axis, max(off, 0), m), alpha=wk)
+        x = out
+    return x
+
+
+def quadrature_quantity(grid, grads, binaries, *, sigma=100.0, include_grad=True, grad_thres=0.01,
+                        device="cuda") -> torch.Tensor:
+    """The masked, normalised field ``q`` whose ``sin(omega * q)`` is meshed (marching_cubes.py:30-58), on the device:
+    smoothing, the occupancy ``binaries[0]`` upsampled trilinearly (align_corners) to the grid's shape, min / max
+    normalisation to [-1, 1] over ``grid * d``, and the mask ``grads > grad_thres``."""
+    dev = _C.resolve_device(device)
+    g = _to_device(grid, dev)
+    if g.ndim != 3:
+        raise ValueError(f"grid must be 3-D, got shape {tuple(g.shape)}")
+    g = smooth(g, sigma)
+    b = _to_device(binaries[0], dev)
+    d = F.interpolate(b[None, None], size=tuple(g.shape), mode="trilinear", align_corners=True)[0, 0]
+    mn = (g * d).min()
+    g.sub_(mn)
+    mx = (g * d).max()
+    g.div_(mx + 1e-6)
+    g.sub_(0.5).mul_(2)
+    q = g * d
+    del g, d
+    if include_grad:
+        q = q * (_to_device(grads, dev) > grad_thres)
+    return q
+
+
+def _normalised_mesh(verts: torch.Tensor, faces: torch.Tensor, n: int) -> TriMesh:
+    """``v / (N - 1)`` then ``(v - 0.5) * 2``, in float64 as the reference's trimesh vertices are."""
+    v = verts.to(torch.float64) / (n - 1)
+    v = (v - 0.5) * 2
+    return TriMesh(v.cpu().numpy(), faces.cpu().numpy())
+
+
+def quadrature_surface_mesh(grid, grads, binaries, *, sigma=100.0, include_grad=True, omega=100.0, thres=0.0,
+                            grad_thres=0.01, device="cuda") -> TriMesh:
+    """The nested quadrature surfaces: marching cubes of ``sin(omega * q)`` at ``thres`` (marching_cubes.py:30-82)."""
+    q = quadrature_quantity(grid, grads, binaries, sigma=sigma, include_grad=include_grad, grad_thres=grad_thres,
+                            device=device)
+    n = q.shape[0]
+    vol = torch.sin(omega * q)
+    del q
+    verts, faces = marching_cubes(vol, thres)
+    return _normalised_mesh(verts, faces, n)
+
+
+def density_surface_mesh(density_grid, density_thres=10.0, device="cuda") -> TriMesh:
+    """The ``mesh_nerf.ply`` half: marching cubes of the NeRF density grid at ``density_thres``, normalised by the
+    density grid's own ``N - 1`` (marching_cubes.py:61-69).  fp16 grids (as the reference saves them) are widened."""
+    dev = _C.resolve_device(device)
+    d = density_grid if isinstance(density_grid, torch.Tensor) else torch.from_numpy(np.asarray(density_grid))
+    if d.dtype not in (torch.float16, torch.float32):
+        d = d.to(torch.float32)
+    d = d.to(dev)
+    verts, faces = marching_cubes(d, density_thres)
+    return _normalised_mesh(verts, faces, d.shape[0])
+
+
+def combined_mesh(quadrature: TriMesh, density: TriMesh) -> TriMesh:
+    """``mesh.ply``: the quadrature surfaces, then the density mesh (the reference's concatenation order)."""
+    return concatenate_meshes([quadrature, density])
