@@ -534,6 +534,33 @@ int qf_marching_cubes_emit(const float *volume, int64_t n0, int64_t n1, int64_t 
                            const void *workspace, int64_t workspace_bytes, float *verts, int64_t n_verts,
                            int32_t *faces, int64_t n_faces, void *stream);
 
+/* Vertex-clustering simplification of a mesh: open3d's simplify_vertex_clustering(voxel_size, contraction), which the
+ * reference runs on the host in examples/downsample_mesh.py and examples/mc_utils.py:203 (rules in DESIGN.md section
+ * 3.9).  vertices fp64 [V,3], faces int64 [F,3]; output vertices fp64 [cells,3] (one per occupied cell, numbered by
+ * first appearance), faces int64 [F',3] (cell ids, smallest first, winding kept, duplicates once).  All arithmetic is
+ * fp64 without FMA contraction; bit-identical run to run.
+ * Two calls, so that the caller allocates once: qf_vertex_clustering_count writes counts[5] (device int64) = cells,
+ * output faces, non-finite vertices, faces with an index outside [0, V), and the most cells any axis needs (the input
+ * is refused, with cells = faces = 0, when one of the middle two is nonzero or the last exceeds 2^21).  After reading
+ * them back, qf_vertex_clustering_emit with the same mesh, voxel size and workspace writes at most n_out_vertices
+ * vertices and n_out_faces faces (pass the counts); n_fallback (device int64, may be NULL) receives the number of
+ * quadric cells whose vertex fell back to the mean.  emit reuses the workspace as scratch.
+ * workspace: device scratch of at least qf_vertex_clustering_workspace_bytes(V, F) bytes, about 72 V + 132 F bytes
+ * plus the sort scratch (that function returns -1 for sizes the entries refuse).
+ * QF_ERR_INVALID_ARGUMENT before any launch for: V outside [1, 2^31), F outside [0, 2^31), a voxel size that is not
+ * positive and finite, an unknown contraction, a NULL pointer, a short workspace, output capacities outside
+ * [0, V] / [0, F].                                                                                                   */
+#define QF_CLUSTER_AVERAGE 0
+#define QF_CLUSTER_QUADRIC 1
+int64_t qf_vertex_clustering_workspace_bytes(int64_t n_vertices, int64_t n_faces);
+int qf_vertex_clustering_count(const double *vertices, int64_t n_vertices, const int64_t *faces, int64_t n_faces,
+                               double voxel_size, void *workspace, int64_t workspace_bytes, int64_t *counts,
+                               void *stream);
+int qf_vertex_clustering_emit(const double *vertices, int64_t n_vertices, const int64_t *faces, int64_t n_faces,
+                              double voxel_size, int contraction, void *workspace, int64_t workspace_bytes,
+                              double *out_vertices, int64_t n_out_vertices, int64_t *out_faces, int64_t n_out_faces,
+                              int64_t *n_fallback, void *stream);
+
 /* Offsets of the packed samples: ray_offset[r] = sum_{q<r} min(hit_count[q], max_hits) for r = 0..n_rays, i.e.
  * ray_offset[n_rays] is the total sample count (left in device memory, so the caller can start qf_pack_samples before
  * reading it back).  Replaces the index bookkeeping of mesh_utils.py:359-366 (np.argsort / boolean masks on the host).

@@ -140,6 +140,10 @@ _SIGNATURES = {
     "qf_marching_cubes_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64]),
     "qf_marching_cubes_count": (c_int, [_P, c_int64, c_int64, c_int64, c_float, _P, c_int64, _P, _P]),
     "qf_marching_cubes_emit": (c_int, [_P, c_int64, c_int64, c_int64, c_float, _P, c_int64, _P, c_int64, _P, c_int64, _P]),
+    "qf_vertex_clustering_workspace_bytes": (c_int64, [c_int64, c_int64]),
+    "qf_vertex_clustering_count": (c_int, [_P, c_int64, _P, c_int64, c_double, _P, c_int64, _P, _P]),
+    "qf_vertex_clustering_emit": (c_int, [_P, c_int64, _P, c_int64, c_double, c_int, _P, c_int64, _P, c_int64, _P, c_int64,
+                                          _P, _P]),
     "qf_sample_offsets_temp_bytes": (c_int64, [c_int64]),
     "qf_sample_offsets": (c_int, [_P, c_int64, c_int32, _P, _P, c_int64, _P]),
     "qf_frame_offsets_temp_bytes": (c_int64, [c_int64]),

@@ -17,7 +17,8 @@ LIB_PATH = os.path.join(PKG_DIR, "libqf_hip.so")
 ARCH = "gfx950"
 
 # (source, extra flags).  exact.hip carries every integer-deciding comparison and texel_fill.hip the fp64 rules of the
-# texel-position map, marching_cubes.hip the fp32 vertex rule and the fp64 face decider: no FMA contraction.
+# texel-position map, marching_cubes.hip the fp32 vertex rule and the fp64 face decider, vertex_clustering.hip the fp64
+# cell, mean and quadric rules: no FMA contraction.
 SOURCES = [
     ("field_eval.hip", []),
     ("field_eval_bf16.hip", []),
@@ -29,6 +30,7 @@ SOURCES = [
     ("exact.hip", ["-ffp-contract=off"]),
     ("texel_fill.hip", ["-ffp-contract=off"]),
     ("marching_cubes.hip", ["-ffp-contract=off"]),
+    ("vertex_clustering.hip", ["-ffp-contract=off"]),
     ("bvh_build.cpp", ["-x", "hip"]),
     ("misc.cpp", ["-x", "hip"]),
     ("frame.cpp", ["-x", "hip"]),

@@ -109,11 +109,14 @@ def quadrature_quantity(grid, grads, binaries, *, sigma=100.0, include_grad=True
     return q
 
 
-def _normalised_mesh(verts: torch.Tensor, faces: torch.Tensor, n: int) -> TriMesh:
-    """``v / (N - 1)`` then ``(v - 0.5) * 2``, in float64 as the reference's trimesh vertices are."""
+def normalise_vertices(verts: torch.Tensor, n: int) -> torch.Tensor:
+    """``v / (N - 1)`` then ``(v - 0.5) * 2``, in float64 as the reference's trimesh vertices are (on verts' device)."""
     v = verts.to(torch.float64) / (n - 1)
-    v = (v - 0.5) * 2
-    return TriMesh(v.cpu().numpy(), faces.cpu().numpy())
+    return (v - 0.5) * 2
+
+
+def _normalised_mesh(verts: torch.Tensor, faces: torch.Tensor, n: int) -> TriMesh:
+    return TriMesh(normalise_vertices(verts, n).cpu().numpy(), faces.cpu().numpy())
 
 
 def quadrature_surface_mesh(grid, grads, binaries, *, sigma=100.0, include_grad=True, omega=100.0, thres=0.0,
@@ -143,3 +146,78 @@ def density_surface_mesh(density_grid, density_thres=10.0, device="cuda") -> Tri
 def combined_mesh(quadrature: TriMesh, density: TriMesh) -> TriMesh:
     """``mesh.ply``: the quadrature surfaces, then the density mesh (the reference's concatenation order)."""
     return concatenate_meshes([quadrature, density])
+
+
+CONTRACTIONS = {"average": 0, "quadric": 1}
+
+
+def simplify_vertex_clustering(vertices: torch.Tensor, faces: torch.Tensor, voxel_size: float,
+                               contraction: str = "quadric", return_fallbacks: bool = False):
+    """open3d's ``simplify_vertex_clustering(voxel_size, contraction)`` on the device, under the rules of DESIGN.md
+    section 3.9: ``(vertices, faces)`` as device fp64 [cells,3] and int64 [F',3].  ``vertices`` is a device float
+    tensor [V,3] (fp32 is widened exactly), ``faces`` a device int64 or int32 tensor [F,3].  With
+    ``return_fallbacks=True`` the number of quadric cells whose vertex fell back to the mean is returned third.
+    Raises ValueError for host tensors, a voxel size that is not positive and finite, non-finite vertices, face indices
+    outside [0, V), V or F of 2^31 or more, or more than 2^21 cells along an axis."""
+    if not isinstance(vertices, torch.Tensor) or not isinstance(faces, torch.Tensor):
+        raise TypeError("vertices and faces must be torch.Tensors")
+    if not vertices.is_cuda or not faces.is_cuda:
+        raise ValueError("simplify_vertex_clustering needs device tensors (quadraturefields_amd has no CPU fallback)")
+    if vertices.device != faces.device:
+        raise ValueError(f"vertices on {vertices.device} and faces on {faces.device}")
+    if vertices.ndim != 2 or vertices.shape[1] != 3 or faces.ndim != 2 or faces.shape[1] != 3:
+        raise ValueError(f"vertices and faces must be [N,3], got {tuple(vertices.shape)} and {tuple(faces.shape)}")
+    if not vertices.is_floating_point():
+        raise TypeError(f"vertices must be floating point, got {vertices.dtype}")
+    if faces.dtype not in (torch.int64, torch.int32):
+        raise TypeError(f"faces must be int64 or int32, got {faces.dtype}")
+    if contraction not in CONTRACTIONS:
+        raise ValueError(f"contraction must be one of {sorted(CONTRACTIONS)}, got {contraction!r}")
+    s = float(voxel_size)
+    if not (math.isfinite(s) and s > 0):
+        raise ValueError(f"voxel_size must be positive and finite, got {voxel_size}")
+    n_v, n_f = vertices.shape[0], faces.shape[0]
+    if n_v >= 2 ** 31 or n_f >= 2 ** 31:
+        raise ValueError(f"the mesh has {n_v} vertices and {n_f} faces; both must be < 2^31")
+    dev = vertices.device
+    if n_v == 0:
+        if n_f:
+            raise ValueError(f"{n_f} faces index an empty vertex set")
+        out = (torch.empty((0, 3), dtype=torch.float64, device=dev), torch.empty((0, 3), dtype=torch.int64, device=dev))
+        return out + (0,) if return_fallbacks else out
+    v = vertices.to(torch.float64).contiguous()
+    f = faces.to(torch.int64).contiguous()
+    lib = _C.lib()
+    with torch.cuda.device(dev):
+        ws_bytes = int(lib.qf_vertex_clustering_workspace_bytes(n_v, n_f))
+        if ws_bytes < 0:
+            raise RuntimeError(f"qf_vertex_clustering_workspace_bytes refused V={n_v}, F={n_f}")
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+        counts = torch.empty((5,), dtype=torch.int64, device=dev)
+        _C.check(lib.qf_vertex_clustering_count(_C.ptr(v), n_v, _C.ptr(f), n_f, s, _C.ptr(ws), ws_bytes,
+                                                _C.ptr(counts), _C.stream()), "qf_vertex_clustering_count")
+        n_cells, n_out, bad_v, bad_f, axis_cells = counts.tolist()
+        if bad_v or bad_f:
+            raise ValueError(f"{bad_v} vertices are not finite and {bad_f} faces have an index outside [0, {n_v})")
+        if axis_cells > 2 ** 21:
+            raise ValueError(f"voxel size {s} needs {axis_cells} cells along an axis; at most 2^21 are allowed")
+        out_v = torch.empty((n_cells, 3), dtype=torch.float64, device=dev)
+        out_f = torch.empty((n_out, 3), dtype=torch.int64, device=dev)
+        fallbacks = torch.zeros((1,), dtype=torch.int64, device=dev)
+        _C.check(lib.qf_vertex_clustering_emit(_C.ptr(v), n_v, _C.ptr(f), n_f, s, CONTRACTIONS[contraction],
+                                               _C.ptr(ws), ws_bytes, _C.ptr(out_v), n_cells, _C.ptr(out_f), n_out,
+                                               _C.ptr(fallbacks), _C.stream()), "qf_vertex_clustering_emit")
+    if return_fallbacks:
+        return out_v, out_f, int(fallbacks.item())
+    return out_v, out_f
+
+
+def downsample_mesh(mesh: TriMesh, vx=0, device="cuda") -> TriMesh:
+    """The reference's ``mc_utils.downsample_mesh(mesh, vx)``: with ``vx > 0`` the mesh clustered with quadric
+    contraction at voxel size ``1 / vx`` (on the device), else ``mesh`` unchanged."""
+    if not vx > 0:
+        return mesh
+    dev = _C.resolve_device(device)
+    v, f = simplify_vertex_clustering(torch.from_numpy(np.asarray(mesh.vertices, np.float64)).to(dev),
+                                      torch.from_numpy(np.asarray(mesh.faces, np.int64)).to(dev), 1 / vx, "quadric")
+    return TriMesh(v.cpu().numpy(), f.cpu().numpy())
