@@ -28,7 +28,7 @@ extern "C" {
 #define QF_ERR_UNSUPPORTED (-3)
 #define QF_ERR_NO_DEVICE (-4)
 
-#define QF_ABI_VERSION 5
+#define QF_ABI_VERSION 6
 #define QF_MAX_LEVELS 16
 #define QF_MAX_LOBES 8
 
@@ -131,7 +131,7 @@ typedef struct qf_sg_head {
  * fixed sequence of launches into worst-case buffers (capturable as a HIP graph).
  * order: NULL, or a permutation of [0,n) giving the order in which points are PROCESSED
  * (16 consecutive slots share a wave pass; spatially coherent groups hit the caches better, see
- * qf_coherent_order); outputs are indexed by point, so results do not depend on it.
+ * qf_coherent_layout); outputs are indexed by point, so results do not depend on it.
  * Outputs (any may be NULL when not produced by the head):
  *   rgb [n,3]; sigma [n] (density after exp(x-1)*selector); geo [n,15]; features [n,3+7L+1]. */
 int qf_field_forward(const qf_field_desc *desc /* host */, const float *table,
@@ -561,17 +561,13 @@ int qf_vertex_clustering_emit(const double *vertices, int64_t n_vertices, const 
                               double *out_vertices, int64_t n_out_vertices, int64_t *out_faces, int64_t n_out_faces,
                               int64_t *n_fallback, void *stream);
 
-/* Offsets of the packed samples: ray_offset[r] = sum_{q<r} min(hit_count[q], max_hits) for r = 0..n_rays, i.e.
- * ray_offset[n_rays] is the total sample count (left in device memory, so the caller can start qf_pack_samples before
- * reading it back).  Replaces the index bookkeeping of mesh_utils.py:359-366 (np.argsort / boolean masks on the host).
- * temp: caller-provided device scratch of at least qf_sample_offsets_temp_bytes(n_rays) bytes.     */
-int64_t qf_sample_offsets_temp_bytes(int64_t n_rays);
-int qf_sample_offsets(const int32_t *hit_count, int64_t n_rays, int32_t max_hits,
-                      int64_t *ray_offset /* [n_rays+1] */, void *temp, int64_t temp_bytes, void *stream);
-
-/* One frame's offsets in three small launches: ray_offset [n_rays+1] exactly as qf_sample_offsets, and -- when
- * tile_base is not NULL (rays = a row-major width x height image) -- tile_base [ceil(w/8)*ceil(h/8)] = the exclusive
- * scan of the 8x8-tile sample totals that qf_coherent_layout takes (round 1: qf_tile_totals + a host-side cumsum).
+/* One frame's offsets in three small launches.  ray_offset [n_rays+1]: the offsets of the packed samples,
+ * ray_offset[r] = sum_{q<r} min(hit_count[q], max_hits) for r = 0..n_rays, i.e. ray_offset[n_rays] is the total sample
+ * count (left in device memory, so the caller can start qf_pack_samples before reading it back); replaces the index
+ * bookkeeping of mesh_utils.py:359-366 (np.argsort / boolean masks on the host).  With tile_base = NULL (width and
+ * height may then be 0) that is all it computes.  When tile_base is not NULL (rays = a row-major width x height
+ * image), also tile_base [ceil(w/8)*ceil(h/8)] = the exclusive scan of the 8x8-tile sample totals that
+ * qf_coherent_layout takes (round 1: qf_tile_totals + a host-side cumsum).
  * temp: qf_frame_offsets_temp_bytes(n_rays) bytes of device scratch.
  * host_out (or NULL): device-accessible PINNED HOST memory, int64[4]; the scan writes [0] = total, [1] = *overflow_in,
  * [3] = *ray_flag_in there itself ([2] is the pack's), so the frame's readback needs no copy kernel -- the host waits
@@ -656,15 +652,13 @@ int qf_pack_tiles(const float *rays_o, const float *rays_d, int32_t width, int32
 
 /* Spatially coherent PROCESSING order for qf_field_forward when the rays are a row-major width x height image:
  * (8x8 pixel tile, hit rank, pixel in tile).  Two steps around one exclusive scan the caller does:
- *   qf_tile_totals    : tile_total[tile] = sum of hit_count over the tile's pixels (tiles row-major, ceil(w/8) per row)
- *   qf_coherent_order : order[tile_base[tile] + slot] = ray_offset[ray] + k   (tile_base = exclusive scan of totals)
+ *   qf_tile_totals     : tile_total[tile] = sum of hit_count over the tile's pixels (row-major tiles, ceil(w/8) a row)
+ *   qf_coherent_layout : order[tile_base[tile] + slot] = ray_offset[ray] + k   (tile_base = exclusive scan of totals)
+ *                        and its inverse, inverse[sample] = position (see qf_pack_samples)
  * order is a permutation of [0, sum(hit_count)).  New on this platform (no reference counterpart): it only
- * changes which samples share a wave pass, never a result.                                                    */
+ * changes which samples share a wave pass, never a result.  order may be NULL (a render-only frame streams the
+ * coherent copies and only needs the inverse).                                                    */
 int qf_tile_totals(const int32_t *hit_count, int32_t width, int32_t height, int64_t *tile_total, void *stream);
-int qf_coherent_order(const int32_t *hit_count, const int64_t *ray_offset, const int64_t *tile_base,
-                      int32_t width, int32_t height, int32_t *order, void *stream);
-/* Same order together with its inverse: inverse[sample] = position (see qf_pack_samples).  order may be NULL
- * (a render-only frame streams the coherent copies and only needs the inverse).                  */
 int qf_coherent_layout(const int32_t *hit_count, const int64_t *ray_offset, const int64_t *tile_base,
                        int32_t width, int32_t height, int32_t *order, int32_t *inverse,
                        int32_t band_rows /* as qf_frame_offsets' */, void *stream);
@@ -806,15 +800,13 @@ typedef struct qf_texture_set {
     float lambda_thres;
 } qf_texture_set;
 
-/* vertices: float64 [V,3] (trimesh keeps float64); faces int64 [F,3]; uv fp32 [V,2] pre-scaled
- * by T as at test_baking_texture_images.py:325-328.  texel [n,2] int64 (row, col).           */
-int qf_texel_indices(const double *vertices, const int64_t *faces, const float *uv,
-                     const float *points, const int64_t *index_tri, int64_t n,
-                     int32_t texture_size, int64_t *texel, void *stream);
-/* The same lookup from a per-mesh table of 128-byte TRIANGLE RECORDS (corner, edges, their dot products and reciprocal
- * determinant in float64, the three corners' uv): qf_texel_records_pack builds records [n_faces * 128 bytes] once per
- * (mesh, uv); qf_texel_indices_packed then reads one line per sample instead of faces -> 3 vertices -> 3 uv.  Same
- * texels (the per-triangle values are the ones qf_texel_indices recomputes for every sample).             */
+/* Nearest-texel lookup of utils.py:1055-1063: float64 Cramer barycentrics of the sample in its triangle, clamped to
+ * [0,1] and renormalised in fp32, the fp32 uv blend, floor, clip to [0, T-1].  It reads a per-mesh table of 128-byte
+ * TRIANGLE RECORDS (corner, edges, their dot products and reciprocal determinant in float64, the three corners' uv):
+ * qf_texel_records_pack builds records [n_faces * 128 bytes] once per (mesh, uv); qf_texel_indices_packed then reads
+ * one line per sample instead of faces -> 3 vertices -> 3 uv.
+ * vertices: float64 [V,3] (trimesh keeps float64); faces int64 [F,3]; uv fp32 [V,2] pre-scaled by T as at
+ * test_baking_texture_images.py:325-328.  texel [n,2] int64 (row, col).                                    */
 #define QF_TEXEL_TRIANGLE_RECORD_BYTES 128
 int qf_texel_records_pack(const double *vertices, const int64_t *faces, const float *uv, int64_t n_faces,
                           void *records, void *stream);
@@ -823,15 +815,14 @@ int qf_texel_indices_packed(const void *records, const float *points, const int6
 /* texel [n,2] -> features [n, 3+7L+1] = [diffuse3 | (axis3, lambda, colour3)*L | sigma].      */
 int qf_texture_fetch(const qf_texture_set *tex /* host */, const int64_t *texel, int64_t n,
                      float *features, void *stream);
-/* Fused: texel fetch + dequantise + SG -> rgb [n,3], sigma [n] (no feature round trip).       */
-int qf_texture_shade(const qf_texture_set *tex /* host */, const int64_t *texel,
-                     const float *dirs, int64_t n, float *rgb, float *sigma, void *stream);
 
 /* Device-resident form of the same texture set: one 64-byte record per texel,
  * [alpha | diffuse rgb | (lambda, azimuth, elevation, colour rgb) * n_lobes | zero pad], so a sample reads ONE
  * 64-byte sector instead of 2 + 2L scattered ones from the reference's planes (texture_utils.py:149-175 indexes
  * each plane separately).  qf_texture_pack builds records [T*T, QF_TEXEL_RECORD_BYTES] from the planes;
- * qf_texture_shade_packed == qf_texture_shade on them, bit for bit.                             */
+ * qf_texture_shade_packed fuses fetch + dequantise + SG on them -> rgb [n,3], sigma [n] (no feature round trip):
+ * sigmoid(diffuse + sum over lobes of colour * exp(|lambda| (axis . dir - 1))) with the dequantisers of
+ * qf_texture_fetch, so sigma equals qf_texture_fetch's last column bit for bit.                  */
 #define QF_TEXEL_RECORD_BYTES 64
 int qf_texture_pack(const qf_texture_set *tex /* host */, uint8_t *records, void *stream);
 int qf_texture_shade_packed(const uint8_t *records, int32_t texture_size, int32_t n_lobes,

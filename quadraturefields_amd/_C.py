@@ -144,8 +144,6 @@ _SIGNATURES = {
     "qf_vertex_clustering_count": (c_int, [_P, c_int64, _P, c_int64, c_double, _P, c_int64, _P, _P]),
     "qf_vertex_clustering_emit": (c_int, [_P, c_int64, _P, c_int64, c_double, c_int, _P, c_int64, _P, c_int64, _P, c_int64,
                                           _P, _P]),
-    "qf_sample_offsets_temp_bytes": (c_int64, [c_int64]),
-    "qf_sample_offsets": (c_int, [_P, c_int64, c_int32, _P, _P, c_int64, _P]),
     "qf_frame_offsets_temp_bytes": (c_int64, [c_int64]),
     "qf_frame_offsets": (c_int, [_P, c_int64, c_int32, c_int32, c_int32, _P, _P, _P, c_int64, _P, _P, _P, c_int32, _P]),
     "qf_banded_tile_count": (c_int64, [c_int32, c_int32, c_int32]),
@@ -153,23 +151,20 @@ _SIGNATURES = {
     "qf_pack_tiles": (c_int, [_P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_float, _P, _P, _P, c_int32, _P]),
     "qf_pack_samples": (c_int, [_P, _P, c_int64, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_float, _P, _P]),
     "qf_tile_totals": (c_int, [_P, c_int32, c_int32, _P, _P]),
-    "qf_coherent_order": (c_int, [_P, _P, _P, c_int32, c_int32, _P, _P]),
     "qf_coherent_layout": (c_int, [_P, _P, _P, c_int32, c_int32, _P, _P, c_int32, _P]),
     "qf_resort_by_depth": (c_int, [_P, _P, c_int64, _P, _P]),
     "qf_resort_samples": (c_int, [_P, _P, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "qf_split_layout": (c_int, [_P, c_int64, c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "qf_mesh_update_d": (c_int, [_P, _P, _P, c_int64, c_int64, _P, _P, _P]),
-    "qf_texel_indices": (c_int, [_P, _P, _P, _P, _P, c_int64, c_int32, _P, _P]),
     "qf_texel_records_pack": (c_int, [_P, _P, _P, c_int64, _P, _P]),
     "qf_texel_indices_packed": (c_int, [_P, _P, _P, c_int64, c_int32, _P, _P]),
     "qf_texture_fetch": (c_int, [POINTER(TextureSet), _P, c_int64, _P, _P]),
-    "qf_texture_shade": (c_int, [POINTER(TextureSet), _P, _P, c_int64, _P, _P, _P]),
     "qf_texture_pack": (c_int, [POINTER(TextureSet), _P, _P]),
     "qf_texture_shade_packed": (c_int, [_P, c_int32, c_int32, c_int32, c_float, _P, _P, c_int64, _P, _P, _P]),
     "qf_texture_shade_points": (c_int, [_P, c_int32, c_int32, c_int32, c_float, _P, _P, _P, _P, _P, c_int64, _P, _P, _P, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
-ABI_VERSION = 5              # QF_ABI_VERSION of include/qf_hip.h
+ABI_VERSION = 6              # QF_ABI_VERSION of include/qf_hip.h
 
 _lib = None
 

@@ -684,17 +684,6 @@ extern "C" int qf_tile_totals(const int32_t *hit_count, int32_t width, int32_t h
     return QF_OK;
 }
 
-extern "C" int qf_coherent_order(const int32_t *hit_count, const int64_t *ray_offset, const int64_t *tile_base,
-                                 int32_t width, int32_t height, int32_t *order, void *stream)
-{
-    if (width < 1 || height < 1 || !hit_count || !ray_offset || !tile_base || !order) return QF_ERR_INVALID_ARGUMENT;
-    const int tiles_x = (width + 7) / 8, tiles_y = (height + 7) / 8;
-    hipLaunchKernelGGL(coherent_order_kernel, dim3(tiles_x * tiles_y), dim3(64), 0, qf_stream(stream), hit_count,
-                       ray_offset, tile_base, (int)width, (int)height, tiles_x, order, (int32_t *)nullptr, 0);
-    QF_LAUNCH_CHECK();
-    return QF_OK;
-}
-
 extern "C" int qf_coherent_layout(const int32_t *hit_count, const int64_t *ray_offset, const int64_t *tile_base,
                                   int32_t width, int32_t height, int32_t *order, int32_t *inverse, int32_t band_rows,
                                   void *stream)

@@ -1806,51 +1806,11 @@ __global__ __launch_bounds__(RS_THREADS) void resort_samples_kernel(
     }
 }
 
-// utils.py:1055-1063: float64 Cramer barycentrics -> fp32 clamp / renormalise -> uv -> floor -> clip.
-__global__ void texel_indices_kernel(const double *vertices, const int64_t *faces, const float *uv, const float *points,
-                                     const int64_t *index_tri, int64_t n, int texture_size, int64_t *texel)
-{
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t f = index_tri[i];
-        const int64_t ia = faces[f * 3], ib = faces[f * 3 + 1], ic = faces[f * 3 + 2];
-        const double ax = vertices[ia * 3], ay = vertices[ia * 3 + 1], az = vertices[ia * 3 + 2];
-        const double e0x = vertices[ib * 3] - ax, e0y = vertices[ib * 3 + 1] - ay, e0z = vertices[ib * 3 + 2] - az;
-        const double e1x = vertices[ic * 3] - ax, e1y = vertices[ic * 3 + 1] - ay, e1z = vertices[ic * 3 + 2] - az;
-        const double wx = (double)points[i * 3] - ax, wy = (double)points[i * 3 + 1] - ay, wz = (double)points[i * 3 + 2] - az;
-        const double d00 = (e0x * e0x + e0y * e0y) + e0z * e0z;
-        const double d01 = (e0x * e1x + e0y * e1y) + e0z * e1z;
-        const double d11 = (e1x * e1x + e1y * e1y) + e1z * e1z;
-        const double d02 = (e0x * wx + e0y * wy) + e0z * wz;
-        const double d12 = (e1x * wx + e1y * wy) + e1z * wz;
-        const double inv = 1.0 / (d00 * d11 - d01 * d01);
-        const double b2d = (d00 * d12 - d01 * d02) * inv;
-        const double b1d = (d11 * d02 - d01 * d12) * inv;
-        const double b0d = 1.0 - b1d - b2d;
-        float b0 = fminf(fmaxf((float)b0d, 0.0f), 1.0f);
-        float b1 = fminf(fmaxf((float)b1d, 0.0f), 1.0f);
-        float b2 = fminf(fmaxf((float)b2d, 0.0f), 1.0f);
-        const float s = (b0 + b1) + b2;
-        b0 = b0 / s;
-        b1 = b1 / s;
-        b2 = b2 / s;
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const float u = (uv[ia * 2 + k] * b0 + uv[ib * 2 + k] * b1) + uv[ic * 2 + k] * b2;
-            float fl = floorf(u);
-            // torch: floor -> .long() -> clip(0, T-1); NaN (degenerate triangle) -> int64 min -> 0
-            int64_t q = (fl != fl) ? 0 : (fl <= -9.2e18f ? INT64_MIN : (fl >= 9.2e18f ? INT64_MAX : (int64_t)fl));
-            if (q < 0) q = 0;
-            if (q > texture_size - 1) q = texture_size - 1;
-            texel[i * 2 + k] = q;
-        }
-    }
-}
-
-// The same lookup with everything that depends on the triangle alone computed once per mesh: a 128-byte record per
+// The nearest-texel lookup of utils.py:1055-1063: float64 Cramer barycentrics -> fp32 clamp / renormalise -> uv ->
+// floor -> clip.  Everything that depends on the triangle alone is computed once per mesh into a 128-byte record per
 // triangle -- corner a, edges e0 / e1, their three dot products and the reciprocal determinant (13 doubles), the three
 // corners' uv (6 floats) -- so that a sample reads ONE line instead of following faces -> 3 vertices -> 3 uv, and
-// evaluates two dot products instead of five and no division.  The values are the ones the kernel above computes per
-// sample (same operations on the same inputs), so the texels are identical.
+// evaluates two dot products instead of five and no division (texel_from_record).
 struct TexelRecord {
     double ax, ay, az, e0x, e0y, e0z, e1x, e1y, e1z, d00, d01, d11, inv;
     float uv[6];                     // (u, v) of corners a, b, c
@@ -1897,6 +1857,7 @@ __device__ __forceinline__ void texel_from_record(const TexelRecord &r, float px
     for (int k = 0; k < 2; ++k) {
         const float u = (r.uv[k] * b0 + r.uv[2 + k] * b1) + r.uv[4 + k] * b2;
         float fl = floorf(u);
+        // torch: floor -> .long() -> clip(0, T-1); NaN (degenerate triangle) -> int64 min -> 0
         int64_t q = (fl != fl) ? 0 : (fl <= -9.2e18f ? INT64_MIN : (fl >= 9.2e18f ? INT64_MAX : (int64_t)fl));
         if (q < 0) q = 0;
         if (q > texture_size - 1) q = texture_size - 1;
@@ -1970,8 +1931,8 @@ __global__ void texture_pack_kernel(TexArgs t, uint8_t *records)
 }
 
 // Every quantity a record decodes to is a function of ONE uint8 code, so a workgroup first evaluates the reference's
-// dequantisers (the same expressions as decode_record, hence the same bits) for all 256 codes into LDS and then
-// decodes by lookup: the 4L sin/cos, L exp and 3+3L colour decodes per sample become LDS reads.
+// dequantisers (the same expressions as decode_color / decode_lobe, hence the same bits) for all 256 codes into LDS
+// and then decodes by lookup: the 4L sin/cos, L exp and 3+3L colour decodes per sample become LDS reads.
 // kLookup: the texel is not read but looked up here, from the sample's position and triangle (texel_from_record): the
 // frame path's fusion of qf_texel_indices_packed and this kernel (no int64 [n,2] texel array written and read back).
 // The record stays in REGISTERS: sixteen 32-bit words addressed with compile-time indices only -- the lobe loop is fully
@@ -2055,9 +2016,9 @@ __global__ __launch_bounds__(256) void texture_shade_packed_kernel(const uint8_t
     }
 }
 
-// The planar kernels (the reference's 2 + 2L separate planes): the same register discipline -- one texel's bytes are
-// read plane by plane inside the unrolled lobe loop, each lobe is decoded and consumed at once (no per-lane feature
-// array; round 2 kept float f[60] + a 64-byte record per lane in scratch: 256 B).
+// The feature fetch (get_features_from_texture_map) reads the reference's 2 + 2L separate planes: one texel's bytes
+// are read plane by plane inside the unrolled lobe loop and each lobe is decoded and written at once (no per-lane
+// feature array; round 2 kept float f[60] + a 64-byte record per lane in scratch: 256 B).
 __device__ __forceinline__ void decode_lobe(const TexArgs &t, int l, int64_t px, float *o /* [7] */)
 {
     const uint8_t lc = t.lam[l][px * 3 + 0], az8 = t.lam[l][px * 3 + 1], el8 = t.lam[l][px * 3 + 2];
@@ -2094,34 +2055,6 @@ __global__ void texture_fetch_kernel(TexArgs t, const int64_t *texel, int64_t n,
             }
         }
         f[width - 1] = -logf(fmaxf(1.0f - a, 1e-6f)) / 0.005f;                // texture_utils.py:61-65 (B-9)
-    }
-}
-
-__global__ void texture_shade_kernel(TexArgs t, const int64_t *texel, const float *dirs, int64_t n, float *rgb,
-                                     float *sigma)
-{
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t px = texel[i * 2] * t.size + texel[i * 2 + 1];
-        const float dx = dirs[i * 3], dy = dirs[i * 3 + 1], dz = dirs[i * 3 + 2];
-        float r = 0.0f, g = 0.0f, b = 0.0f;
-#pragma unroll
-        for (int l = 0; l < QF_MAX_LOBES; ++l) {
-            if (l < t.n_lobes) {
-                float x[7];
-                decode_lobe(t, l, px, x);
-                const float nrm = sqrtf((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]);
-                const float dotp = ((x[0] / nrm) * dx + (x[1] / nrm) * dy) + (x[2] / nrm) * dz;
-                const float e = expf(fabsf(x[3]) * (dotp - 1.0f));
-                r += x[4] * e;
-                g += x[5] * e;
-                b += x[6] * e;
-            }
-        }
-        rgb[i * 3 + 0] = 1.0f / (1.0f + expf(-(decode_color(t.diffuse[px * 3 + 0], t.sigmoid_codec) + r)));
-        rgb[i * 3 + 1] = 1.0f / (1.0f + expf(-(decode_color(t.diffuse[px * 3 + 1], t.sigmoid_codec) + g)));
-        rgb[i * 3 + 2] = 1.0f / (1.0f + expf(-(decode_color(t.diffuse[px * 3 + 2], t.sigmoid_codec) + b)));
-        const float a = (float)t.alpha[px] / 255.0f;
-        sigma[i] = -logf(fmaxf(1.0f - a, 1e-6f)) / 0.005f;
     }
 }
 
@@ -2348,16 +2281,6 @@ extern "C" int qf_resort_samples(const int64_t *index_ray, const float *depth, i
     return QF_OK;
 }
 
-extern "C" int qf_texel_indices(const double *vertices, const int64_t *faces, const float *uv, const float *points,
-                                const int64_t *index_tri, int64_t n, int32_t texture_size, int64_t *texel, void *stream)
-{
-    if (n < 0 || texture_size < 1) return QF_ERR_INVALID_ARGUMENT;
-    if (n == 0) return QF_OK;
-    if (!vertices || !faces || !uv || !points || !index_tri || !texel) return QF_ERR_INVALID_ARGUMENT;
-    QF_SIMPLE_LAUNCH(texel_indices_kernel, n, vertices, faces, uv, points, index_tri, n, (int)texture_size, texel);
-    return QF_OK;
-}
-
 extern "C" int qf_texel_records_pack(const double *vertices, const int64_t *faces, const float *uv, int64_t n_faces,
                                      void *records, void *stream)
 {
@@ -2388,19 +2311,6 @@ extern "C" int qf_texture_fetch(const qf_texture_set *tex, const int64_t *texel,
     if (n == 0) return QF_OK;
     if (!texel || !features) return QF_ERR_INVALID_ARGUMENT;
     QF_SIMPLE_LAUNCH(texture_fetch_kernel, n, t, texel, n, features);
-    return QF_OK;
-}
-
-extern "C" int qf_texture_shade(const qf_texture_set *tex, const int64_t *texel, const float *dirs, int64_t n,
-                                float *rgb, float *sigma, void *stream)
-{
-    TexArgs t;
-    int rc = fill_tex_args(tex, &t);
-    if (rc != QF_OK) return rc;
-    if (n < 0) return QF_ERR_INVALID_ARGUMENT;
-    if (n == 0) return QF_OK;
-    if (!texel || !dirs || !rgb || !sigma) return QF_ERR_INVALID_ARGUMENT;
-    QF_SIMPLE_LAUNCH(texture_shade_kernel, n, t, texel, dirs, n, rgb, sigma);
     return QF_OK;
 }
 

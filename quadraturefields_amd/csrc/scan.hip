@@ -1,13 +1,13 @@
 // Sample offsets of the packed quadrature points: ray_offset[r] = sum_{q<r} min(hit_count[q], max_hits), with the
 // grand total in ray_offset[n_rays].  The total lands in device memory, so the caller can read it back while the pack
-// kernel is already running.  Hand-written three-launch scan (below); round 1's rocPRIM/hipCUB lookback scan behind
-// qf_sample_offsets is gone -- the library is no longer linked on any product path.
+// kernel is already running.  Hand-written three-launch scan (below); round 1's rocPRIM/hipCUB lookback scan is gone
+// -- the library is no longer linked on any product path.
 #include "qf_common.h"
 
 // ---------------------------------------------------------------------------------------------------------------------
-// One frame's offsets in three small launches: the per-ray sample offsets (as qf_sample_offsets) AND, for an image-shaped
-// batch, the exclusive scan of the 8x8-tile totals that qf_coherent_layout needs -- round 1 issued a library scan (two
-// kernels), qf_tile_totals, torch.cumsum (two kernels) and a subtraction for the same numbers.
+// One frame's offsets in three small launches: the per-ray sample offsets above AND, for an image-shaped batch, the
+// exclusive scan of the 8x8-tile totals that qf_coherent_layout needs -- round 1 issued a library scan (two kernels),
+// qf_tile_totals, torch.cumsum (two kernels) and a subtraction for the same numbers.
 //   1. frame_partials_kernel: workgroup b < n_blocks sums min(count, K) over its 1024 rays; the workgroups after those
 //      compute the tile totals (one wave per tile, four tiles per workgroup);
 //   2. frame_scan_kernel: ONE workgroup turns both arrays into exclusive prefix sums in place (a few thousand
@@ -212,19 +212,4 @@ extern "C" int qf_tile_offsets(const int32_t *hit_count, int32_t max_hits, int32
                        overflow_in, host_out, zero_word, ray_flag_in);
     QF_LAUNCH_CHECK();
     return QF_OK;
-}
-
-// qf_sample_offsets = the per-ray half of qf_frame_offsets (no tiles, no host block).
-extern "C" int64_t qf_sample_offsets_temp_bytes(int64_t n_rays)
-{
-    const int64_t b = qf_frame_offsets_temp_bytes(n_rays);
-    return b < 0 ? b : (b < 16 ? 16 : b);
-}
-
-extern "C" int qf_sample_offsets(const int32_t *hit_count, int64_t n_rays, int32_t max_hits, int64_t *ray_offset,
-                                 void *temp, int64_t temp_bytes, void *stream)
-{
-    if (temp_bytes < qf_sample_offsets_temp_bytes(n_rays)) return QF_ERR_INVALID_ARGUMENT;
-    return qf_frame_offsets(hit_count, n_rays, max_hits, 0, 0, ray_offset, nullptr, temp, temp_bytes, nullptr, nullptr,
-                            nullptr, 0, stream);
 }

@@ -136,7 +136,7 @@ class Field(nn.Module):
 
     def density(self, x, order=None, n_device=None):
         """[N,3] in [-scale, scale] -> [N,1].  field.py:186-203, one fused launch.  ``order`` (extension): int32
-        processing permutation (``RayIntersector.coherent_order``), cache locality only."""
+        processing permutation (``RayIntersector.coherent_layout`` / ``last_order``), cache locality only."""
         self._check_compute_dtype()
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
             if self.fused_backward and not x.requires_grad:

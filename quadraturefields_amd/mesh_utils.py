@@ -964,7 +964,10 @@ class RayIntersector:
 
     def coherent_layout(self, hit_count, ray_offset, total: int, width: int, tile_base=None, want_order=True,
                         band_rows: int = 0):
-        """``coherent_order`` and its inverse map (``inverse[sample] = position``).  Given the inverse,
+        """(order, inverse): the int32 permutation of the ``total`` packed samples of a row-major ``width``-wide image,
+        ordered (8x8 tile, hit rank, pixel), and its inverse map (``inverse[sample] = position``).  Handing ``order`` to
+        ``radiance_field(points, dirs, order=...)`` makes the points of one wave pass neighbours on the same surface
+        patch (cache locality only; results are unchanged); ``want_order=False`` returns None for it.  Given the inverse,
         ``qf_pack_samples`` also writes ``xyz[order]`` / ``dirs[order]``, so ``field(xyz_c, dirs_c)`` reads and writes
         sequentially (the indirection through ``order`` costs it 10 %), and
         ``derive_properties(..., sample_index=inverse)`` picks colour and density back up per ray.  ``tile_base``: the
@@ -1014,21 +1017,6 @@ class RayIntersector:
                                           _C.ptr(ray_offset), _C.ptr(tile_base), _C.ptr(invalid), _C.ptr(order),
                                           _C.ptr(inverse), _C.stream()), "qf_split_layout")
         return order, inverse, invalid
-
-    @_on_device
-    def coherent_order(self, hit_count: torch.Tensor, ray_offset: torch.Tensor, total: int, width: int) -> torch.Tensor:
-        """int32 permutation of the ``total`` packed samples of a row-major ``width``-wide image, ordered
-        (8x8 tile, hit rank, pixel).  Handing it to ``radiance_field(points, dirs, order=...)`` makes the points of
-        one wave pass neighbours on the same surface patch (cache locality only; results are unchanged)."""
-        height = hit_count.shape[0] // width
-        tiles = ((width + 7) // 8) * ((height + 7) // 8)
-        totals = torch.empty((tiles,), dtype=torch.int64, device=hit_count.device)
-        _C.check(_C.lib().qf_tile_totals(_C.ptr(hit_count), width, height, _C.ptr(totals), _C.stream()), "qf_tile_totals")
-        base = (torch.cumsum(totals, dim=0) - totals).contiguous()
-        order = torch.empty((total,), dtype=torch.int32, device=hit_count.device)
-        _C.check(_C.lib().qf_coherent_order(_C.ptr(hit_count), _C.ptr(ray_offset), _C.ptr(base), width, height,
-                                            _C.ptr(order), _C.stream()), "qf_coherent_order")
-        return order
 
     @torch.no_grad()
     def _warn_if_not_unit(self, vectors) -> None:

@@ -186,21 +186,16 @@ class FeatureCompression:
             cache = self._records = (tuple((p.data_ptr(), p._version) for p in planes), rec)
         return cache[1]
 
-    def shade(self, indices, dirs, packed: bool = True):
-        """Fused fetch + dequantise + spherical-Gaussian shading: (rgb [S,3], sigma [S]).  ``packed`` reads the
-        interleaved texel records (one sector per sample); ``packed=False`` reads the reference's planes.  Same bits."""
+    def shade(self, indices, dirs):
+        """Fused fetch + dequantise + spherical-Gaussian shading: (rgb [S,3], sigma [S]) from the interleaved texel
+        records (one sector per sample)."""
         indices = _C.i64c(indices)
         dirs = _C.f32c(dirs)
         n = indices.shape[0]
         rgb = torch.empty((n, 3), dtype=torch.float32, device=indices.device)
         sigma = torch.empty((n,), dtype=torch.float32, device=indices.device)
-        if packed:
-            _C.check(_C.lib().qf_texture_shade_packed(
-                _C.ptr(self.records()), int(self.alpha.shape[0]), self.num_lobes,
-                1 if self.compression_type == "sigma" else 0, float(self.lambda_thres), _C.ptr(indices), _C.ptr(dirs), n,
-                _C.ptr(rgb), _C.ptr(sigma), _C.stream()), "qf_texture_shade_packed")
-            return rgb, sigma
-        t = self.texture_set()
-        _C.check(_C.lib().qf_texture_shade(ctypes.byref(t), _C.ptr(indices), _C.ptr(dirs), n, _C.ptr(rgb),
-                                           _C.ptr(sigma), _C.stream()), "qf_texture_shade")
+        _C.check(_C.lib().qf_texture_shade_packed(
+            _C.ptr(self.records()), int(self.alpha.shape[0]), self.num_lobes,
+            1 if self.compression_type == "sigma" else 0, float(self.lambda_thres), _C.ptr(indices), _C.ptr(dirs), n,
+            _C.ptr(rgb), _C.ptr(sigma), _C.stream()), "qf_texture_shade_packed")
         return rgb, sigma

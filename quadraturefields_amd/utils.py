@@ -266,7 +266,8 @@ def render_image_finetune_with_occgrid(
     mesh_finetune=None, scaling=1 / 128, bg_color="white", order=None, order_inverse=None,
 ):
     """Render the samples of one split through the (deformed) quadrature points -- utils.py:465-607.
-    ``order`` (extension, optional): coherent processing order from ``RayIntersector.coherent_order``;
+    ``order`` (extension, optional): coherent processing order (``RayIntersector.last_order``, or the first member
+    of ``RayIntersector.coherent_layout``);
     ``order_inverse``: its inverse map if the caller has it (``RayIntersector.last_layout[0]``).
 
     Returns the reference's 9-tuple (colors, opacities, depths, n_samples, weights, positions, index_ray,
@@ -449,8 +450,8 @@ def render_image_fit_sg_with_occgrid(
 
 
 def _triangle_records(mesh_intersect, uv):
-    """(records, vertices float64, faces, uv fp32) on the device: the per-(mesh, uv) table of 128-byte triangle records
-    of ``qf_texel_records_pack``, built on first use and rebuilt when the mesh's vertices or the uv tensor change."""
+    """The per-(mesh, uv) table of 128-byte triangle records of ``qf_texel_records_pack`` on the device, built on first
+    use and rebuilt when the mesh's vertices or the uv tensor change."""
     cache = getattr(mesh_intersect, "_texel_cache", None)
     if cache is None or cache[0] is not mesh_intersect.mesh.vertices:
         v64 = torch.from_numpy(np.ascontiguousarray(mesh_intersect.mesh.vertices, dtype=np.float64)).to(mesh_intersect.device)
@@ -464,22 +465,17 @@ def _triangle_records(mesh_intersect, uv):
         _C.check(_C.lib().qf_texel_records_pack(_C.ptr(v64), _C.ptr(faces), _C.ptr(uv), faces.shape[0], _C.ptr(records),
                                                 _C.stream()), "qf_texel_records_pack")
         cache[3], cache[4] = key, (records, uv)             # the uv tensor stays referenced: its address is the key
-    return cache[4][0], v64, faces, uv
+    return cache[4][0]
 
 
-def texel_indices(mesh_intersect, uv, points, index_tri, texture_size: int, packed: bool = True) -> torch.Tensor:
-    """Nearest-texel lookup of utils.py:1055-1063 on the device (float64 barycentrics, fp32 UV blend).  ``packed``: from
-    the per-(mesh, uv) table of 128-byte triangle records; ``packed=False``: following faces -> vertices -> uv per
-    sample.  Same texels."""
-    records, v64, faces, uv = _triangle_records(mesh_intersect, uv)
+def texel_indices(mesh_intersect, uv, points, index_tri, texture_size: int) -> torch.Tensor:
+    """Nearest-texel lookup of utils.py:1055-1063 on the device (float64 barycentrics, fp32 UV blend) from the
+    per-(mesh, uv) table of 128-byte triangle records."""
+    records = _triangle_records(mesh_intersect, uv)
     points = _C.f32c(points)
     index_tri = _C.i64c(index_tri)
     n = points.shape[0]
     texel = torch.empty((n, 2), dtype=torch.int64, device=points.device)
-    if not packed:
-        _C.check(_C.lib().qf_texel_indices(_C.ptr(v64), _C.ptr(faces), _C.ptr(uv), _C.ptr(points), _C.ptr(index_tri), n,
-                                           int(texture_size), _C.ptr(texel), _C.stream()), "qf_texel_indices")
-        return texel
     _C.check(_C.lib().qf_texel_indices_packed(_C.ptr(records), _C.ptr(points), _C.ptr(index_tri), n, int(texture_size),
                                               _C.ptr(texel), _C.stream()), "qf_texel_indices_packed")
     return texel
@@ -490,7 +486,7 @@ def shade_baked_points(mesh_intersect, uv, compressor, points, index_tri, dirs, 
     """(rgb [n,3], sigma [n]) of samples given by position and triangle: ``texel_indices`` + ``compressor.shade`` in one
     launch (``qf_texture_shade_points``: the texel is looked up inside the shading kernel, no index array in between).
     Same values as the two calls."""
-    records, _, _, _ = _triangle_records(mesh_intersect, uv)
+    records = _triangle_records(mesh_intersect, uv)
     points, dirs = _C.f32c(points), _C.f32c(dirs)
     # int32 ids (what the tile pack writes) go to the kernel as they are; anything else as the reference's int64
     tri32 = index_tri.contiguous() if index_tri.dtype == torch.int32 else None

@@ -319,8 +319,9 @@ def test_wide_raster_selects_the_k_nearest_like_the_bvh(device, k, wide, slabs, 
         assert ri._raster_streak > 0 or ri.repaired_frames > 0
 
 
-def test_coherent_order_is_the_tile_rank_pixel_permutation(device):
-    """qf_coherent_order == argsort of (8x8 tile, hit rank, pixel in tile); the field result does not depend on it."""
+def test_last_order_is_the_tile_rank_pixel_permutation(device):
+    """RayIntersector.last_order (qf_coherent_layout's order) == argsort of (8x8 tile, hit rank, pixel in tile); the field
+    result does not depend on it."""
     from quadraturefields_amd import synthetic
     from quadraturefields_amd.mesh_utils import MeshIntersection, make_camera
     from quadraturefields_amd.radiance_fields.ngp import NGPRadianceField

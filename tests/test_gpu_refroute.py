@@ -1,6 +1,6 @@
 """GPU: the pieces behind the reference-shaped eval loop (bench.py ``reference_route``): the split layout derived from
 a window's ray ids, the re-sort launch that also writes the streamed copies, ``generate_splits`` on device arrays,
-``MeshFinetune.update_d`` as one launch, the hand-written ``qf_sample_offsets`` -- and that the eval loop of
+``MeshFinetune.update_d`` as one launch, the hand-written per-ray scan of ``qf_frame_offsets`` -- and that the eval loop of
 train_finetune.py:575-629, restated over the reference-named entry points, gives the FrameRenderer's pixels."""
 import numpy as np
 import pytest
@@ -195,16 +195,18 @@ def test_mesh_update_d_matches_index_add(device):
 
 
 def test_sample_offsets_hand_written_scan(device):
-    """qf_sample_offsets (no library scan behind it any more): exclusive sums of min(count, K) + the grand total."""
+    """qf_frame_offsets without tiles (no library scan behind it any more): exclusive sums of min(count, K) + the grand
+    total."""
     from quadraturefields_amd import _C
     g = torch.Generator().manual_seed(1)
     for n in (1, 7, 1024, 1025, 70001):
         cnt = torch.randint(-2, 40, (n,), generator=g, dtype=torch.int32).to(device)
         k = 25
         out = torch.empty((n + 1,), dtype=torch.int64, device=device)
-        nb = int(_C.lib().qf_sample_offsets_temp_bytes(n))
+        nb = int(_C.lib().qf_frame_offsets_temp_bytes(n))
         temp = torch.empty((nb,), dtype=torch.uint8, device=device)
-        _C.check(_C.lib().qf_sample_offsets(_C.ptr(cnt), n, k, _C.ptr(out), _C.ptr(temp), nb, _C.stream()), "qf_sample_offsets")
+        _C.check(_C.lib().qf_frame_offsets(_C.ptr(cnt), n, k, 0, 0, _C.ptr(out), None, _C.ptr(temp), nb, None, None, None,
+                                           0, _C.stream()), "qf_frame_offsets")
         c = cnt.clamp(0, k).long()
         ref = torch.cat([torch.zeros(1, dtype=torch.int64, device=device), torch.cumsum(c, 0)])
         assert torch.equal(out, ref)

@@ -314,8 +314,8 @@ def test_config3_bf16_dense_shell_frame_matches_the_bf16_oracle(device, seeded):
 
 
 def test_config5_baked_render_at_full_texture_size(device):
-    """BASELINE configs[4] at its full texture size (4096^2, L = 6; 1.07 GB of texel records): the packed-record shade
-    equals the planar one bit for bit on a frame's samples, untextured rays come out white with alpha 0, the render is
+    """BASELINE configs[4] at its full texture size (4096^2, L = 6; 1.07 GB of texel records): at a frame's texels the
+    records hold the planes' bytes and shade to the fetched features (sigma bit for bit, rgb to rounding), untextured rays come out white with alpha 0, the render is
     invariant to how the frame is split into bands, and a 64x64 crop agrees with the oracle's baked render."""
     from quadraturefields_amd import synthetic, utils
     from quadraturefields_amd.mesh_utils import MeshIntersection, make_camera
@@ -340,12 +340,23 @@ def test_config5_baked_render_at_full_texture_size(device):
     assert torch.isfinite(rgb).all() and float(rgb.min()) >= 0.0 and float(rgb.max()) <= 1.0
     miss = alpha.reshape(-1) == 0
     assert bool(miss.any()) and bool((rgb[miss] == 1).all())
-    # packed records vs the reference's planes on the frame's samples
+    # the texel records vs the reference's planes on the frame's samples: the same bytes, and the fused shade = the
+    # fetched features' sigma and their two-call rgb
     data = mi.sampling_raytrace_device(d, o, camera=make_camera(c2w, focal, w, h), layout=False)
     texel = utils.texel_indices(mi, uv, data[0], data[4], size)
-    a = comp.shade(texel, data[1], packed=True)
-    b = comp.shade(texel, data[1], packed=False)
-    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
+    ty, tx = texel[:, 0], texel[:, 1]
+    rec = comp.records()[ty * size + tx]
+    assert torch.equal(rec[:, 0], comp.alpha[ty, tx]) and torch.equal(rec[:, 1:4], comp.diffuse[ty, tx])
+    for l in range(lobes):
+        assert torch.equal(rec[:, 4 + 6 * l:7 + 6 * l], comp.lambdas[l][ty, tx])
+        assert torch.equal(rec[:, 7 + 6 * l:10 + 6 * l], comp.sg_colors[l][ty, tx])
+    rgb_s, sig_s = comp.shade(texel, data[1])
+    feats = comp.get_features_from_texture_map(texel)
+    assert torch.equal(sig_s, feats[:, -1])
+    # as in test_gpu_texture.py::test_all_code_points: lambda up to e^5 and large colours turn a 1-ulp difference in
+    # (axis . d) into up to ~1e-3 relative in the pre-sigmoid sum, hence the bound (sigmoid slope <= 1/4)
+    want = comp.features_to_rgb(feats, data[1])
+    assert bool(((rgb_s - want).abs() <= 5e-5 + 1e-4 * want.abs()).all())
     # two bands = the frame
     from quadraturefields_amd import parallel
     parts = []

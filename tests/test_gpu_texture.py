@@ -73,12 +73,11 @@ def test_texel_indices_bit_exact(device):
     far = xyz + 0.5
     want = oq.texel_indices(mesh.vertices[f], far.cpu().numpy(), torch.from_numpy(uv)[torch.from_numpy(f)], size)
     assert torch.equal(utils.texel_indices(mi, uv, far, index_tri, size).cpu(), want)
-    # the per-triangle record table (default) and the per-sample faces -> vertices -> uv walk give the same texels; the
-    # table follows the uv it was built from (cached per uv tensor, rebuilt when that tensor is modified in place)
+    # the per-triangle record table follows the uv it was built from (cached per uv tensor, rebuilt when that tensor is
+    # modified in place)
     uv_d = torch.from_numpy(uv).to(device)
-    a = utils.texel_indices(mi, uv_d, xyz, index_tri, size, packed=True)
-    b = utils.texel_indices(mi, uv_d, xyz, index_tri, size, packed=False)
-    assert torch.equal(a, b) and torch.equal(a, got)
+    a = utils.texel_indices(mi, uv_d, xyz, index_tri, size)
+    assert torch.equal(a, got)
     # the fused lookup + shading launch of the frame path = the two calls
     from quadraturefields_amd.texture_utils import FeatureCompression
     tex = synthetic.random_textures(size, 3, seed=2)
@@ -89,8 +88,9 @@ def test_texel_indices_bit_exact(device):
     rgb1, sig1 = utils.shade_baked_points(mi, uv_d, comp, xyz, index_tri, dirs)
     assert torch.equal(rgb1, rgb2) and torch.equal(sig1, sig2)
     uv_d.mul_(0.5)
-    c = utils.texel_indices(mi, uv_d, xyz, index_tri, size, packed=True)
-    assert torch.equal(c, utils.texel_indices(mi, uv_d, xyz, index_tri, size, packed=False)) and not torch.equal(c, a)
+    c = utils.texel_indices(mi, uv_d, xyz, index_tri, size)
+    want = oq.texel_indices(mesh.vertices[f], xyz.cpu().numpy(), uv_d.cpu()[torch.from_numpy(f)], size)
+    assert torch.equal(c.cpu(), want) and not torch.equal(c, a)
 
 
 def test_compress_roundtrip_through_textures(device):
@@ -127,8 +127,8 @@ def test_compress_roundtrip_through_textures(device):
 @pytest.mark.gpu
 @pytest.mark.parametrize("lobes", [1, 3, 6, 8])
 def test_packed_texel_records_equal_planes(device, lobes):
-    """The interleaved 64-byte texel records (one sector per sample) shade to the same bits as the reference's planes,
-    and are rebuilt when a plane changes."""
+    """The interleaved 64-byte texel records (one sector per sample) hold the planes' bytes, shade to the fetched
+    features' sigma bit for bit and to their two-call rgb to rounding, and are rebuilt when a plane changes."""
     from quadraturefields_amd import synthetic
     from quadraturefields_amd.texture_utils import FeatureCompression
     size = 96
@@ -141,9 +141,7 @@ def test_packed_texel_records_equal_planes(device, lobes):
     idx[0] = torch.tensor([0, 0])
     idx[1] = torch.tensor([size - 1, size - 1])
     d = torch.nn.functional.normalize(torch.randn(n, 3, generator=g), dim=-1).to(device)
-    rgb_p, sig_p = comp.shade(idx, d, packed=True)
-    rgb_r, sig_r = comp.shade(idx, d, packed=False)
-    assert torch.equal(rgb_p, rgb_r) and torch.equal(sig_p, sig_r)
+    rgb_p, sig_p = comp.shade(idx, d)
     rec = comp.records()
     assert rec.shape == (size * size, 64) and rec.dtype == torch.uint8
     assert torch.equal(rec[:, 0].reshape(size, size), comp.alpha)
@@ -153,10 +151,11 @@ def test_packed_texel_records_equal_planes(device, lobes):
     assert int(rec[:, 4 + 6 * lobes:].max()) == 0
     # two-call form (texture_utils.py:144-147 on the fetched rows) = the fused shade, to rounding
     feats = comp.get_features_from_texture_map(idx)
+    assert torch.equal(sig_p, feats[:, -1])
     assert (comp.features_to_rgb(feats[:, :-1], d) - rgb_p).abs().max() <= 2e-6
     assert (comp.features_to_rgb(feats, d) - rgb_p).abs().max() <= 2e-6
     mix = comp.spherical_gaussian_mixture(feats[:, 3:-1], d)
     assert (torch.sigmoid(feats[:, :3] + mix) - rgb_p).abs().max() <= 2e-6
     comp.alpha[idx[:, 0], idx[:, 1]] = 77                 # in-place edit: the records follow
     rgb2, sig2 = comp.shade(idx, d)
-    assert torch.equal(sig2, comp.shade(idx, d, packed=False)[1]) and not torch.equal(sig2, sig_p)
+    assert torch.equal(sig2, comp.get_features_from_texture_map(idx)[:, -1]) and not torch.equal(sig2, sig_p)

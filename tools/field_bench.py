@@ -42,7 +42,7 @@ def main():
     if args.order == "coherent":
         hc = hits[2]
         cs = torch.cumsum(hc.to(torch.int64), 0)
-        order = ri.coherent_order(hc, (cs - hc).contiguous(), int(cs[-1]), bench.W)
+        order = ri.coherent_layout(hc, (cs - hc).contiguous(), int(cs[-1]), bench.W)[0]
     elif args.order != "ray":
         ray = index_ray
         first = torch.zeros(o.shape[0] + 1, dtype=torch.int64, device=dev)
