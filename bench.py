@@ -1,6 +1,12 @@
 """Headline benchmark: rays/s of the mesh-quadrature render at 800x800 (BASELINE.json configs[1]).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run does only what the headline needs: it builds the scene, spins the device up, runs the W warm-up and K timed
+steps, writes ``--dump-outputs`` if asked, and prints the JSON line (``value``, ``ms_per_step``, ``config``,
+``distributed``).  Everything else this file measures runs only with ``--full``: the point count of the timed frames,
+per-stage times, the BVH traversal, ``roofline``, ``repeat``, ``sharded_frame``, ``reference_route``, ``configs`` and
+``cpu_baseline`` (the ``--no-*`` / ``--scenes`` / ``--repeats`` options trim a ``--full`` run).
 
 One step = one full 800x800 frame per rank through the hot path on synthetic inputs already resident in HBM:
 ray/mesh intersection (camera-coherent pass, exact BVH traversal as its fallback) -> sample packing -> fused field
@@ -20,7 +26,7 @@ GPU, RCCL):
   looped over eight seeded scenes.  Reported as latency (host waits for every frame) and as pipelined throughput,
   next to the same loop's 1-rank figure when N = 1.
 
-At N = 1 rank 0 also appends ``configs``: BASELINE configs[2] (1080p, bf16, T = 2^21, dense shells) and configs[4]
+With ``--full`` at N = 1 rank 0 also appends ``configs``: BASELINE configs[2] (1080p, bf16, T = 2^21, dense shells) and configs[4]
 (baked SG textures 4096^2, L = 6), each with the roofline of its own dominant kernel measured with HIP events, and
 the ``cpu_baseline`` (the oracle on the host cores).  Rank 0 prints ONE JSON line.
 """
@@ -592,6 +598,60 @@ def sharded_frames(device, rank, world, scene0, n_scenes, frames_per_scene, back
     }
 
 
+def stage_lines(stages, mi, rays, cameras, pts, pts_total, elapsed, steps, intersector):
+    """--full, rank 0: the timed frames' point count, per-stage HIP-event times (the field stage from the timed region,
+    the others from an extra untimed pass), the BVH traversal of the same frames and the field kernel's roofline."""
+    n_frames = len(rays)
+    ms = stages.stage_ms()                      # field: HIP events inside the timed region
+    for i in range(min(5, n_frames)):           # the other stages: an extra, untimed pass with events everywhere
+        stages.frame(rays[i][0], rays[i][1], cameras[i], True)
+    field_ms = ms["field"]
+    stages.ev["field"] = []
+    ms = stages.stage_ms(np.median)
+    ms["field"] = field_ms
+    # the general intersector (exact BVH traversal of the same frames; the camera-coherent pass is the default above)
+    ri = mi.rayintersector
+    ev = []
+    for i in range(min(6, n_frames)):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        ri._hits_bvh(rays[i][0], rays[i][1], MAX_HITS, W)
+        b.record()
+        ev.append((a, b))
+    torch.cuda.synchronize()
+    bvh_ms = float(np.median([a.elapsed_time(b) for a, b in ev[1:]]))
+    # HBM-side bytes of the dominant kernel come from PMC counters (separate rocprofv3 --pmc passes over this same
+    # command, see profiles/<round>/README.md); bench.py cannot sample them itself, so the committed measurement is
+    # scaled to this run's points per launch.
+    traffic = traffic_src = None
+    for rnd in PROFILE_ROUNDS:
+        tpath = os.path.join(ROOT, "profiles", rnd, "field_traffic.json")
+        if os.path.exists(tpath):
+            tj = json.load(open(tpath))
+            traffic_src = f"profiles/{rnd}/field_traffic.json (FETCH_SIZE + WRITE_SIZE, bytes per point x points per launch)"
+            traffic = (tj["fetch_bytes_per_launch"] + tj["write_bytes_per_launch"]) / tj["points_per_launch"]
+            break
+    pts_per_launch = pts / steps
+    field_s = (ms["field"] or 0.0) * 1e-3
+    achieved = pts_per_launch * ALG_BYTES_PER_POINT / field_s / 1e9 if field_s > 0 else 0.0
+    return {
+        "quadrature_points_per_frame": pts_per_launch,
+        "field_evals_per_s": pts_total / elapsed,
+        "field_evals_per_s_in_kernel": pts_per_launch / field_s if field_s > 0 else None,
+        "stage_ms": ms,
+        "intersect_ms": {"camera_coherent": ms["traverse"] if intersector == "raster" else None,
+                         "bvh_traversal": bvh_ms},
+        "roofline": {
+            "kernel": "field_kernel<NGP> (hash-grid gather + MLPs)", "bound": "hbm", "achieved": achieved,
+            "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+            "traffic": None if traffic is None else traffic * pts_per_launch, "traffic_unit": "bytes per launch",
+            "traffic_source": traffic_src,
+            "algorithmic_bytes_per_point": ALG_BYTES_PER_POINT, "points_per_launch": pts_per_launch,
+            "avg_launch_ms": ms["field"],
+        },
+    }
+
+
 def dump_outputs(out_dir, arrays, limit_bytes=64 << 20):
     """``--dump-outputs``: each device tensor as ``out_dir/<name>.npy`` in float32.  A frame is 20 B per pixel (12.8 MB
     at 800x800, 51.2 MB at --up-sample 2), so the whole frame fits under the limit and is written, not a sample of it."""
@@ -646,12 +706,21 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="skip the configs[2] / configs[4] lines (N = 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure everything else too: the timed frames' point count, per-stage and BVH "
+                         "traversal times, roofline, repeat, sharded_frame, reference_route, configs, cpu_baseline.  "
+                         "Without it only the headline runs and the options below up to --sharded-frames do nothing")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the cpu_baseline leg (N = 1)")
+    ap.add_argument("--no-configs", action="store_true", help="--full: skip the configs[2] / configs[4] lines (N = 1)")
     ap.add_argument("--no-reference-route", action="store_true",
-                    help="skip the reference_route leg (the reference-named entry points timed beside the headline, N = 1)")
-    ap.add_argument("--scenes", type=int, default=8, help="seeded scenes of the sharded_frame loop (0 = skip it)")
-    ap.add_argument("--sharded-frames", type=int, default=4, help="frames per scene in the sharded_frame loop")
+                    help="--full: skip the reference_route leg (the reference-named entry points timed beside the headline, "
+                         "N = 1)")
+    ap.add_argument("--repeats", type=int, default=9,
+                    help="--full: after the timed region, this many more untimed-for-value repetitions of the same K-step "
+                         "loop; their median / min / max ms_per_step ride along in the JSON line (`repeat`), so that a 2 %% "
+                         "change is distinguishable from run-to-run noise (0 = skip)")
+    ap.add_argument("--scenes", type=int, default=8, help="--full: seeded scenes of the sharded_frame loop (0 = skip it)")
+    ap.add_argument("--sharded-frames", type=int, default=4, help="--full: frames per scene in the sharded_frame loop")
     ap.add_argument("--spin-up", type=float, default=1.0,
                     help="seconds of untimed frames before the warm-up steps, to bring the GPU clocks up")
     ap.add_argument("--up-sample", type=int, default=1, choices=[1, 2],
@@ -671,10 +740,6 @@ def main():
                          "the rank that scores / stores an evaluation run; all: all_gather_into_tensor to every rank (the "
                          "default of rounds 1-3); none: no data-path collective")
     ap.add_argument("--no-gather", action="store_true", help="same as --frame-gather none")
-    ap.add_argument("--repeats", type=int, default=9,
-                    help="after the timed region: this many more untimed-for-value repetitions of the same K-step loop; their "
-                         "median / min / max ms_per_step ride along in the JSON line (`repeat`), so that a 2 %% change is "
-                         "distinguishable from run-to-run noise (0 = skip)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="process-group backend for N > 1 (nccl = RCCL).  gloo + --single-device rehearses the multi-rank "
                          "control flow on a one-GPU box (all ranks on cuda:0)")
@@ -820,7 +885,7 @@ def main():
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     log(f"timed region done: {elapsed:.3f} s for {args.steps} steps")
-    if nowait:              # the no-wait frames do not report their point counts: count the same frames now, untimed
+    if args.full and nowait:    # the no-wait frames do not report their point counts: count the same frames now, untimed
         pts = sum(stages.frame(rays[i][0], rays[i][1], cameras[i])[3] for i in range(args.warmup, n_frames))
         torch.cuda.synchronize()
     t = torch.tensor([elapsed, float(pts)], dtype=torch.float64, device=device if args.backend == "nccl" else "cpu")
@@ -839,7 +904,7 @@ def main():
     # sample cannot tell a 2 % change from noise -- so the same K-step loop runs `--repeats` more times, each bracketed
     # exactly like the timed region, and the spread rides along.
     repeat = None
-    if args.repeats > 0:
+    if args.full and args.repeats > 0:
         samples = []
         for _ in range(args.repeats):
             if world > 1:
@@ -862,45 +927,13 @@ def main():
                   "value_at_median": W * H * world / (float(np.median(per_step)) * 1e-3)}
 
     sharded = None
-    if args.scenes > 0:             # every rank takes part
+    if args.full and args.scenes > 0:       # every rank takes part
         sharded = sharded_frames(device, rank, world, (mesh, mi, field), args.scenes, args.sharded_frames, args.backend)
 
     if rank != 0:
         parallel.shutdown()
         return
-    ms = stages.stage_ms()                      # field: HIP events inside the timed region
-    for i in range(min(5, n_frames)):           # the other stages: an extra, untimed pass with events everywhere
-        stages.frame(rays[i][0], rays[i][1], cameras[i], True)
-    field_ms = ms["field"]
-    stages.ev["field"] = []
-    ms = stages.stage_ms(np.median)
-    ms["field"] = field_ms
-    # the general intersector (exact BVH traversal of the same frames; the camera-coherent pass is the default above)
-    ri = mi.rayintersector
-    ev = []
-    for i in range(min(6, n_frames)):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        ri._hits_bvh(rays[i][0], rays[i][1], MAX_HITS, W)
-        b.record()
-        ev.append((a, b))
-    torch.cuda.synchronize()
-    bvh_ms = float(np.median([a.elapsed_time(b) for a, b in ev[1:]]))
-    # HBM-side bytes of the dominant kernel come from PMC counters (separate rocprofv3 --pmc passes over this same
-    # command, see profiles/<round>/README.md); bench.py cannot sample them itself, so the committed measurement is
-    # scaled to this run's points per launch.
-    traffic = traffic_src = None
-    for rnd in PROFILE_ROUNDS:
-        tpath = os.path.join(ROOT, "profiles", rnd, "field_traffic.json")
-        if os.path.exists(tpath):
-            tj = json.load(open(tpath))
-            traffic_src = f"profiles/{rnd}/field_traffic.json (FETCH_SIZE + WRITE_SIZE, bytes per point x points per launch)"
-            traffic = (tj["fetch_bytes_per_launch"] + tj["write_bytes_per_launch"]) / tj["points_per_launch"]
-            break
     rays_total = W * H * args.steps * world
-    pts_per_launch = pts / args.steps
-    field_s = (ms["field"] or 0.0) * 1e-3
-    achieved = pts_per_launch * ALG_BYTES_PER_POINT / field_s / 1e9 if field_s > 0 else 0.0
     result = {
         "metric": f"rays/sec at {W}x{H} Lego (mesh-quadrature render: ray/mesh intersection + hash-grid/MLP field + "
                   "compositing)",
@@ -936,21 +969,9 @@ def main():
                               "none": ", no data-path collective"}[frame_mode],
         },
         "ms_per_step_ranks": {"min": rank_ms[0], "max": rank_ms[1]},
-        "quadrature_points_per_frame": pts_per_launch,
-        "field_evals_per_s": pts_total / elapsed,
-        "field_evals_per_s_in_kernel": pts_per_launch / field_s if field_s > 0 else None,
-        "stage_ms": ms,
-        "intersect_ms": {"camera_coherent": ms["traverse"] if args.intersector == "raster" else None,
-                         "bvh_traversal": bvh_ms},
-        "roofline": {
-            "kernel": "field_kernel<NGP> (hash-grid gather + MLPs)", "bound": "hbm", "achieved": achieved,
-            "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-            "traffic": None if traffic is None else traffic * pts_per_launch, "traffic_unit": "bytes per launch",
-            "traffic_source": traffic_src,
-            "algorithmic_bytes_per_point": ALG_BYTES_PER_POINT, "points_per_launch": pts_per_launch,
-            "avg_launch_ms": ms["field"],
-        },
     }
+    if args.full:
+        result.update(stage_lines(stages, mi, rays, cameras, pts, pts_total, elapsed, args.steps, args.intersector))
     if repeat is not None:
         result["repeat"] = repeat
     result["distributed"] = dist_info if dist_info is not None else {
@@ -958,11 +979,11 @@ def main():
         "devices": parallel.device_report(0, 1, device)}
     if sharded is not None:
         result["sharded_frame"] = sharded
-    if world == 1 and not args.no_reference_route and args.up_sample == 1:
+    if args.full and world == 1 and not args.no_reference_route and args.up_sample == 1:
         log("reference_route (loader item -> generate_splits -> render_image_finetune_with_occgrid; baked-texture loop)")
         result["reference_route"] = reference_route_line(device, (mesh, mi, field))
         torch.cuda.empty_cache()
-    if world == 1 and not args.no_configs and args.up_sample == 1:
+    if args.full and world == 1 and not args.no_configs and args.up_sample == 1:
         log("configs[4] (baked textures)")
         cfg5 = config5_line(device, (mesh, mi, field))
         torch.cuda.empty_cache()
@@ -970,7 +991,7 @@ def main():
         cfg3 = config3_line(device)
         torch.cuda.empty_cache()
         result["configs"] = [cfg3, cfg5]
-    if not args.no_cpu_baseline and world == 1:      # rank 0 at N = 1 only
+    if args.full and not args.no_cpu_baseline and world == 1:      # rank 0 at N = 1 only
         log("cpu baseline (oracle on host cores)")
         base, rgb_o, idx, (ray_o, tri_o) = cpu_baseline(mesh, field, rays[0][0].cpu(), rays[0][1].cpu())
         rgb0 = stages.frame(rays[0][0], rays[0][1], cameras[0])[0].cpu()[idx]

@@ -24,7 +24,7 @@ build() {   # $1 = 1|2
   done
   /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o $W/libqf_sim$1.so $W/obj$1/*.o
 }
-run() { timeout -k 10 200 python $R/bench.py --no-configs --scenes 0 --no-cpu-baseline --no-reference-route 2>/dev/null | python -c "import json,sys; r=json.loads(sys.stdin.read()); print('$1: ms_per_frame', round(r['ms_per_step'],4), 'field_ms', round(r['stage_ms']['field'],4), 'points', r['quadrature_points_per_frame'])"; }
+run() { timeout -k 10 200 python $R/bench.py --full --no-configs --scenes 0 --no-cpu-baseline --no-reference-route 2>/dev/null | python -c "import json,sys; r=json.loads(sys.stdin.read()); print('$1: ms_per_frame', round(r['ms_per_step'],4), 'field_ms', round(r['stage_ms']['field'],4), 'points', r['quadrature_points_per_frame'])"; }
 pmc() { cd /tmp && export TMPDIR=/tmp; rm -rf /tmp/pmc_$1; timeout -k 10 240 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum TCC_EA0_RDREQ_sum --output-format csv -d /tmp/pmc_$1 -- python3 $R/tools/field_bench.py --stage field --iters 3 --physical > /tmp/pmc_$1.log 2>&1; python3 $R/tools/pmc_summary.py /tmp/pmc_$1 | grep -A5 field_kernel | sed "s/^/$1: /"; cd $R; }
 run "hashed gather (product build)"
 pmc product

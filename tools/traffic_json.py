@@ -24,7 +24,7 @@ bench = json.load(open(os.path.join(root, "pmc_FETCH_SIZE.json")))
 print(json.dumps({
     "kernel": "field_kernel<1, false>", "fetch_bytes_per_launch": fetch, "write_bytes_per_launch": write,
     "points_per_launch": bench["quadrature_points_per_frame"],
-    "source": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE (separate passes) over `python bench.py --steps 5 "
+    "source": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE (separate passes) over `python bench.py --full --steps 5 "
               f"--warmup 1 --no-cpu-baseline`, mean of {n_f} / {n_w} dispatches (tools/profile_bench.sh)",
     "correction": "factor 1.0: tools/calib_fetch.hip (16.78 M 8-byte loads from distinct 64-B sectors of a 2 GiB table) "
                   "reads FETCH_SIZE = 64 B per load = TCC_EA0_RDREQ x 64 B exactly; the L2 fills 64-B sectors on this "
