@@ -16,9 +16,10 @@ OBJ_DIR = os.path.join(CSRC, "_obj")
 LIB_PATH = os.path.join(PKG_DIR, "libqf_hip.so")
 ARCH = "gfx950"
 
-# (source, extra flags).  exact.hip carries every integer-deciding comparison and texel_fill.hip the fp64 rules of the
-# texel-position map, marching_cubes.hip the fp32 vertex rule and the fp64 face decider, vertex_clustering.hip the fp64
-# cell, mean and quadric rules: no FMA contraction.
+# (source, extra flags).  No FMA contraction in the index-exact stages (exact_common.h: bvh_traverse, raster, sample_pack,
+# texture and grid_march carry every integer-deciding comparison), texel_fill.hip (the fp64 rules of the texel-position
+# map), marching_cubes.hip (the fp32 vertex rule and the fp64 face decider) and vertex_clustering.hip (the fp64 cell, mean
+# and quadric rules).
 SOURCES = [
     ("field_eval.hip", []),
     ("field_eval_bf16.hip", []),
@@ -27,7 +28,11 @@ SOURCES = [
     ("scan.hip", []),
     ("composite.hip", []),
     ("optim.hip", []),
-    ("exact.hip", ["-ffp-contract=off"]),
+    ("bvh_traverse.hip", ["-ffp-contract=off"]),
+    ("raster.hip", ["-ffp-contract=off"]),
+    ("sample_pack.hip", ["-ffp-contract=off"]),
+    ("texture.hip", ["-ffp-contract=off"]),
+    ("grid_march.hip", ["-ffp-contract=off"]),
     ("texel_fill.hip", ["-ffp-contract=off"]),
     ("marching_cubes.hip", ["-ffp-contract=off"]),
     ("vertex_clustering.hip", ["-ffp-contract=off"]),
@@ -59,9 +64,13 @@ def _stale(target: str, deps) -> bool:
     return any(os.path.getmtime(d) > t for d in deps)
 
 
+def _obj(src: str) -> str:
+    return os.path.join(OBJ_DIR, os.path.splitext(src)[0] + ".o")
+
+
 def _compile(item):
     src, extra = item
-    obj = os.path.join(OBJ_DIR, os.path.splitext(src)[0] + ".o")
+    obj = _obj(src)
     if not _stale(obj, _deps(src)):
         return obj, False
     cmd = [_hipcc()] + COMMON + extra + ["-c", os.path.join(CSRC, src), "-o", obj]
@@ -76,8 +85,11 @@ def _compile(item):
 def build(force: bool = False, verbose: bool = False) -> str:
     """Compile every HIP source for gfx950 and link libqf_hip.so; returns its path."""
     os.makedirs(OBJ_DIR, exist_ok=True)
-    if force:
-        for f in os.listdir(OBJ_DIR):
+    # --force clears every object; otherwise only those of sources that are gone (tools that link _obj/*.o would pick
+    # up their symbols a second time)
+    keep = set() if force else {_obj(src) for src, _ in SOURCES}
+    for f in os.listdir(OBJ_DIR):
+        if os.path.join(OBJ_DIR, f) not in keep:
             os.remove(os.path.join(OBJ_DIR, f))
     with ThreadPoolExecutor(max_workers=4) as pool:
         results = list(pool.map(_compile, SOURCES))

@@ -1,4 +1,4 @@
-// Internal layout of the opaque qf_bvh handle (shared by bvh_build.cpp and exact.hip).
+// Internal layout of the opaque qf_bvh handle (shared by bvh_build.cpp, bvh_traverse.hip and raster.hip).
 #pragma once
 #include <stdint.h>
 
@@ -34,7 +34,7 @@
 struct qf_bvh {
     float *d_nodes8 = nullptr;
     float *d_tris = nullptr;
-    // triangle-chunk culling of the camera-coherent pass (exact.hip: chunk_boxes_kernel / cull_chunks_kernel), allocated
+    // triangle-chunk culling of the camera-coherent pass (raster.hip: chunk_boxes_kernel / cull_chunks_kernel), allocated
     // on first use: boxes of 64 consecutive leaf-order triangles; [2 counters | visible chunk ids]
     float *d_chunk_box = nullptr;
     int32_t *d_visible = nullptr;
@@ -55,7 +55,7 @@ struct qf_bvh {
     float min_sep = 0.f;             // > 0: the trimesh/Embree re-origin rule (qf_bvh_set_min_separation)
     // mean crossings of a random line through the mesh's bounding box, 2 area(mesh) / area(box) (Cauchy-Crofton), from
     // the build-time vertices: with fewer than max_hits / 2 the K-lists (almost) never fill and the general traversal
-    // visits the hit children in ANY order (exact.hip, bvh_launch)
+    // visits the hit children in ANY order (bvh_traverse.hip, bvh_launch)
     float depth_complexity = 0.f;
     std::vector<float> h_nodes;      // binary tree (build, host refit, inspection)
     std::vector<float> h_nodes8;     // wide tree mirror

@@ -316,10 +316,6 @@ __global__ void apply_deformation_kernel(const float *f, float scaling, const fl
 
 }  // namespace
 
-#define QF_SIMPLE_LAUNCH(kernel, count, ...)                                                            \
-    hipLaunchKernelGGL(kernel, dim3(qf_grid_1d((count), 256)), dim3(256), 0, qf_stream(stream), __VA_ARGS__); \
-    QF_LAUNCH_CHECK();
-
 extern "C" int qf_mark_pack_boundaries(const int64_t *ridx, int64_t n, uint8_t *boundary, void *stream)
 {
     if (n < 0) return QF_ERR_INVALID_ARGUMENT;

@@ -43,6 +43,12 @@ static inline int qf_grid_1d(int64_t n, int block, int blocks_per_cu = 8)
     return (int)(want < cap ? want : cap);
 }
 
+// Launch of a grid-stride elementwise kernel over `count` items (qf_grid_1d, 256 threads) on the entry point's `stream`,
+// followed by the launch check
+#define QF_SIMPLE_LAUNCH(kernel, count, ...)                                                                  \
+    hipLaunchKernelGGL(kernel, dim3(qf_grid_1d((count), 256)), dim3(256), 0, qf_stream(stream), __VA_ARGS__); \
+    QF_LAUNCH_CHECK();
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) for a kernel that wants more than 48 KB of dynamic LDS: the attribute
 // is PER DEVICE, so one flag per device ordinal (atomic: the entry points may be called from several host threads); a
 // process that launches on a second GPU sets it there too instead of failing the launch.

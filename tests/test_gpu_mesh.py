@@ -2,7 +2,7 @@
 
 Bar: bit-exact triangle ids, hit counts, ray ids and sample order.  The hit distance t, the fp64 locations and
 the depths are computed with the same individually rounded IEEE operations on both sides (no FMA contraction in
-exact.hip / intersect_ref.c), so they are compared for exact equality too.
+exact_common.h and the stages that include it / intersect_ref.c), so they are compared for exact equality too.
 """
 import numpy as np
 import pytest

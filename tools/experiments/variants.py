@@ -21,7 +21,6 @@ CSRC = os.path.join(ROOT, "quadraturefields_amd", "csrc")
 OUT = os.path.join(ROOT, "tools", "experiments", "_build")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC,
          "-Wall", "-Wno-unused-function", "-Wno-unused-variable", "-Wno-unused-but-set-variable"]
-EXTRA = {"exact.hip": ["-ffp-contract=off"]}
 
 # ----------------------------------------------------------------------------------------------------------------------
 # field_kernel: where does its 1.32 ms go?  
@@ -153,19 +152,19 @@ _TRAV_ORDERED = ("    const bool ordered = bvh->depth_complexity >= 0.5f * (floa
                  "    const bool ordered = true;       // EXPERIMENT trav_ordered\n")
 
 VARIANTS = {
-    "trav_ordered": ("exact.hip", [_TRAV_ORDERED], []),
+    "trav_ordered": ("bvh_traverse.hip", [_TRAV_ORDERED], []),
     "bf16_no_mlp": ("field_eval_bf16.hip", [_B_NO_MLP], []),
     "bf16_no_gather": ("field_eval_bf16.hip", [_B_NO_GATHER], []),
     "bf16_xpair": ("field_eval_bf16.hip", [_B_XPAIR], []),
-    "tex_stride48": ("exact.hip", _TEX, ["-DQF_EXP_TEX_STRIDE=48"]),
-    "tex_tiled64": ("exact.hip", _TEX, ["-DQF_EXP_TEX_STRIDE=64", "-DQF_EXP_TEX_TILED"]),
-    "tex_tiled48": ("exact.hip", _TEX, ["-DQF_EXP_TEX_STRIDE=48", "-DQF_EXP_TEX_TILED"]),
-    "tex_morton48": ("exact.hip", _TEX, ["-DQF_EXP_TEX_STRIDE=48", "-DQF_EXP_TEX_MORTON"]),
-    "tex_ldspair": ("exact.hip", _TEX_LDS, []),
-    "tex_ldspair_tiled48": ("exact.hip", _TEX + _TEX_LDS, ["-DQF_EXP_TEX_STRIDE=48", "-DQF_EXP_TEX_TILED"]),
+    "tex_stride48": ("texture.hip", _TEX, ["-DQF_EXP_TEX_STRIDE=48"]),
+    "tex_tiled64": ("texture.hip", _TEX, ["-DQF_EXP_TEX_STRIDE=64", "-DQF_EXP_TEX_TILED"]),
+    "tex_tiled48": ("texture.hip", _TEX, ["-DQF_EXP_TEX_STRIDE=48", "-DQF_EXP_TEX_TILED"]),
+    "tex_morton48": ("texture.hip", _TEX, ["-DQF_EXP_TEX_STRIDE=48", "-DQF_EXP_TEX_MORTON"]),
+    "tex_ldspair": ("texture.hip", _TEX_LDS, []),
+    "tex_ldspair_tiled48": ("texture.hip", _TEX + _TEX_LDS, ["-DQF_EXP_TEX_STRIDE=48", "-DQF_EXP_TEX_TILED"]),
     "no_mlp": ("field_eval.hip", [_NO_MLP], []),
     "no_gather": ("field_eval.hip", [_NO_GATHER], []),
-    "trav_stats": ("exact.hip", [_TRAV_STATS_DECL, _TRAV_STATS_RAY, _TRAV_STATS_NODE, _TRAV_STATS_LEAF, _TRAV_STATS_HIT], []),
+    "trav_stats": ("bvh_traverse.hip", [_TRAV_STATS_DECL, _TRAV_STATS_RAY, _TRAV_STATS_NODE, _TRAV_STATS_LEAF, _TRAV_STATS_HIT], []),
 }
 
 
@@ -198,7 +197,7 @@ def build(name):
     stem = os.path.splitext(src)[0]
     obj = os.path.join(OUT, f"{name}_{stem}.o")
     hipcc = "/opt/rocm/bin/hipcc"
-    _run([hipcc] + FLAGS + EXTRA.get(src, []) + flags + ["-x", "hip", "-c", patched, "-o", obj])
+    _run([hipcc] + FLAGS + dict(product.SOURCES)[src] + flags + ["-x", "hip", "-c", patched, "-o", obj])
     misc = os.path.join(OUT, "misc_exp.o")
     _run([hipcc] + FLAGS + ["-DQF_ABI_VERSION_OFFSET=1000", "-x", "hip", "-c", os.path.join(CSRC, "misc.cpp"), "-o", misc])
     others = [os.path.join(product.OBJ_DIR, f) for f in sorted(os.listdir(product.OBJ_DIR))
