@@ -226,6 +226,39 @@ int qf_deform_field_forward_f16(const qf_grid_desc *grid /* host */, const uint1
                                 const float *xyz, int64_t n, const int64_t *n_device, const int32_t *order,
                                 float *out /* [n] */, float *enc_out /* [n,32] or NULL */, void *stream);
 
+/* The quadrature field's value and spatial-gradient norm (field_utils.extract_grid, examples/field_utils.py:276-318, over
+ * Field of examples/field.py:130-238 with back_prop=False): x01 = (x+scale)/(scale+scale); cat[x01, grid(x01)] (35) ->
+ * hidden -> hidden -> 1 with biases, activation QF_ACT_RELU or QF_ACT_ELU (torch.nn.ELU(), alpha 1), hidden 16 or 32;
+ * w1 [hidden,35], b1, w2 [hidden,hidden], b2, wout [1,hidden], bout [1].  The gradient is the decoder's backward to
+ * the three x01 columns (the encoder sees x01.detach()), divided by (scale+scale); its Euclidean norm is clipped to
+ * [0, 65504] (a NaN stays NaN).
+ * Source, exactly one of:
+ *   - a lattice: axis [n*pool] (torch.linspace(-1, 1, n*pool) * scale in fp32), lattice point (i,j,k) =
+ *     (axis[i], axis[j], axis[k]); pool 1 or 2, n*pool <= 16384.  Output [a,b,c] (pool 2: the mean of lattice indices
+ *     {2a,2a+1} x {2b,2b+1} x {2c,2c+1}, summed from 0 with the first index outermost and divided by 8 -- torch's CPU
+ *     AvgPool3d, bit for bit) for a in [x_begin, x_begin + x_count) (<= n); value / grad_norm hold that slab,
+ *     [x_count, n, n] C order.  xyz NULL, n_points 0, n_device NULL.
+ *   - a point list: xyz [n_points,3], n_device as in qf_field_forward; value / grad_norm [n_points].  axis NULL, n,
+ *     x_begin, x_count 0, pool 1.
+ * value fp32; grad_norm IEEE binary16 (the fp32 value, or pooled fp32 mean, rounded once to nearest even), or NULL to
+ * skip the gradient.  Errors (before any launch): QF_ERR_UNSUPPORTED for another hidden, activation, pool or grid;
+ * QF_ERR_INVALID_ARGUMENT for NULL arrays, scale not in (0, 3e38], a slab outside [0, n) or a mixed source.    */
+#define QF_ACT_RELU 0
+#define QF_ACT_ELU 1
+int qf_field_grid_extract(const qf_grid_desc *grid /* host */, const float *table, float scale, int32_t hidden,
+                          int32_t activation, const float *w1, const float *b1, const float *w2, const float *b2,
+                          const float *wout, const float *bout, const float *axis, int32_t n, int32_t x_begin,
+                          int32_t x_count, int32_t pool, const float *xyz, int64_t n_points, const int64_t *n_device,
+                          float *value, uint16_t *grad_norm, void *stream);
+
+/* fp16 table variant ([rows,2] binary16, low half = feature 0): the contract of qf_deform_field_forward_f16 -- rows
+ * converted exactly, blended in fp32, each of the 32 features rounded once to fp16, the decoder fp32.          */
+int qf_field_grid_extract_f16(const qf_grid_desc *grid /* host */, const uint16_t *table, float scale, int32_t hidden,
+                              int32_t activation, const float *w1, const float *b1, const float *w2, const float *b2,
+                              const float *wout, const float *bout, const float *axis, int32_t n, int32_t x_begin,
+                              int32_t x_count, int32_t pool, const float *xyz, int64_t n_points,
+                              const int64_t *n_device, float *value, uint16_t *grad_norm, void *stream);
+
 /* Backward of the decoder of qf_deform_field_forward, fused (training: the deformation field of
  * train_finetune.py:387-399 is optimised together with the radiance field).  enc [n,32] = grid encoding of x01 [n,3],
  * d_out [n] = dL/dfield.  d_enc [n,32] -> qf_grid_encode_backward; d_x01 (optional) = the part of dL/dx01 that enters

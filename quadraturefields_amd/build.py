@@ -23,6 +23,7 @@ ARCH = "gfx950"
 SOURCES = [
     ("field_eval.hip", []),
     ("field_eval_bf16.hip", []),
+    ("grid_extract.hip", []),
     ("grid_backward.hip", []),
     ("mlp_train.hip", []),
     ("scan.hip", []),

@@ -4,7 +4,9 @@ Mirrors ``Field`` of ``examples/field.py:130-270`` as the render path uses it
 (``examples/utils.py:555-566``: ``field_net(x, return_grad=False)[0]``): hash grid (tcnn ``Encoding``)
 followed by ``cat[x01, h] -> BasicDecoder``.  Inference is one fused launch; when autograd is recording the
 differentiable route (HIP grid forward/backward + library GEMMs) is taken, which also serves ``field_grad`` --
-including ``create_graph=True`` (the reference's default), through the second-order grid kernel.
+including ``create_graph=True`` (the reference's default), through the second-order grid kernel.  The finetune
+configuration (relu, hidden 32) infers through the deformation kernel; stage 2's (elu, hidden 16, train_field.py:238-252)
+and the other two combinations through qf_field_grid_extract's point list (``field_utils`` uses its lattice source).
 """
 import numpy as np
 import torch
@@ -73,10 +75,13 @@ class Field(nn.Module):
     def __init__(self, scale, back_prop=0, precision=16, log2_T=19, L=16, max_res=512, output_dim=1, min_res=16,
                  hidden_size=32, num_features=2, nl="elu", bias=True, bias_last=True):
         super().__init__()
-        if nl != "relu" or output_dim != 1 or hidden_size != 32 or not bias or not bias_last:
-            raise NotImplementedError("the fused kernel implements the finetune configuration of "
-                                      "train_finetune.py:387-399 (relu, hidden 32, output 1, biases)")
+        if nl not in self.ACTIVATIONS or output_dim != 1 or hidden_size not in (16, 32) or not bias or not bias_last:
+            raise NotImplementedError("the fused kernels implement nl in {'relu', 'elu'}, hidden_size 16 or 32, "
+                                      "output_dim 1 and both biases: the finetune configuration of "
+                                      "train_finetune.py:387-399 (relu, hidden 32) and stage 2's of "
+                                      "train_field.py:238-252 (elu, hidden 16)")
         self.output_dim = output_dim
+        self.nl, self.hidden_size = nl, hidden_size
         # kept for API parity: ``precision`` selects nothing, ``compute_dtype`` (below) does
         self.dtype = torch.float16 if precision == 16 else torch.float32
         self.scale = scale
@@ -93,8 +98,19 @@ class Field(nn.Module):
                              "interpolation": "Linear"},
             dtype=self.dtype)
         self.decoder_field = BasicDecoder(input_dim=L * num_features + 3, output_dim=output_dim,
-                                          activation=torch.nn.ReLU(), bias=bias, num_layers=2,
+                                          activation=torch.nn.ELU() if nl == "elu" else torch.nn.ReLU(),
+                                          bias=bias, num_layers=2,
                                           hidden_dim=hidden_size, skip=[], bias_last=bias_last)
+
+    #: Activations of the decoder (field.py:172-175): torch.nn.ReLU() or torch.nn.ELU() (alpha 1).
+    ACTIVATIONS = ("relu", "elu")
+
+    @property
+    def deform_kernel(self) -> bool:
+        """True for the finetune configuration (relu, hidden 32), which the deformation kernel (qf_deform_field_forward)
+        and its fused backward serve; every other accepted configuration infers through qf_field_grid_extract's point
+        list and trains through the differentiable route."""
+        return self.nl == "relu" and self.hidden_size == 32
 
     #: Precision of the fused inference kernel: "fp32" (default; parity with the fp32 oracle to ~1e-6) or "fp16", the
     #: precision the reference builds this field in (``Field(precision=16)``, field.py:135-138,157-171: an fp16 tcnn
@@ -139,7 +155,7 @@ class Field(nn.Module):
         processing permutation (``RayIntersector.coherent_layout`` / ``last_order``), cache locality only."""
         self._check_compute_dtype()
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-            if self.fused_backward and not x.requires_grad:
+            if self.fused_backward and self.deform_kernel and not x.requires_grad:
                 d = self.decoder_field       # parameters train, the input is data: fused first-order backward
                 return _DeformTrainFn.apply(x, self.xyz_encoder.params, d.layers[0].weight, d.layers[0].bias,
                                             d.layers[1].weight, d.layers[1].bias, d.lout.weight, d.lout.bias, self)
@@ -160,6 +176,8 @@ class Field(nn.Module):
         d = self.decoder_field
         w = [_C.f32c(t.detach()) for t in (d.layers[0].weight, d.layers[0].bias, d.layers[1].weight,
                                            d.layers[1].bias, d.lout.weight, d.lout.bias)]
+        if not self.deform_kernel:
+            return self._extract_points(x, w, n_device, compute_dtype)
         if (compute_dtype or self.compute_dtype) == "fp16":
             name, table = "qf_deform_field_forward_f16", self._half_table()
         else:
@@ -170,6 +188,35 @@ class Field(nn.Module):
             _C.ptr(order, torch.int32) if order is not None and order.shape[0] == n else None,
             _C.ptr(out), _C.ptr(enc_out), _C.stream()), name)
         return out[:, None]
+
+    def _extract_points(self, x, w, n_device=None, compute_dtype=None):
+        """Inference of a configuration other than the finetune one: qf_field_grid_extract on a point list, value only."""
+        n = x.shape[0]
+        out = torch.empty((n,), dtype=torch.float32, device=x.device)
+        name, table = self.extract_entry(compute_dtype)
+        _C.check(getattr(_C.lib(), name)(
+            self.xyz_encoder.grid.desc, _C.ptr(table), float(self.scale), self.hidden_size, self.activation_code,
+            *[_C.ptr(t) for t in w], None, 0, 0, 0, 1, _C.ptr(x), n, _C.ptr(n_device, torch.int64),
+            _C.ptr(out), None, _C.stream()), name)
+        return out[:, None]
+
+    @property
+    def activation_code(self) -> int:
+        """QF_ACT_RELU / QF_ACT_ELU of include/qf_hip.h."""
+        return 1 if self.nl == "elu" else 0
+
+    def extract_entry(self, compute_dtype=None):
+        """(qf_field_grid_extract entry point, table) for ``compute_dtype`` (None = the field's own)."""
+        self._check_compute_dtype()
+        if (compute_dtype or self.compute_dtype) == "fp16":
+            return "qf_field_grid_extract_f16", self._half_table()
+        return "qf_field_grid_extract", self.xyz_encoder.params.detach()
+
+    def decoder_arrays(self):
+        """w1, b1, w2, b2, wout, bout as contiguous fp32 tensors (the kernels' argument order)."""
+        d = self.decoder_field
+        return [_C.f32c(t.detach()) for t in (d.layers[0].weight, d.layers[0].bias, d.layers[1].weight,
+                                              d.layers[1].bias, d.lout.weight, d.lout.bias)]
 
     def field(self, x, order=None, n_device=None):
         return self.density(x, order, n_device)[:, 0:self.output_dim]
