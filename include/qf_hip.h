@@ -507,6 +507,30 @@ int qf_bvh_repair_overflow(const qf_bvh *bvh, const float *rays_o, const float *
                            int32_t *hit_count, uint64_t *keep_mask, int32_t *raw_count,
                            const int32_t *traverse_all_flag, void *stream);
 
+/* The plain camera-coherent pass of a render-only frame with the hits BINNED PER 8x8 TILE instead of appended to per-ray
+ * lists (same triangle set-up, guard band, ray check, origin rule and mt_hit on the same values as qf_raster_intersect
+ * without cull_chunks; only what happens to an accepted hit differs): a wave stages its hits in LDS and reserves room in
+ * the bin of each tile they fall into with one atomic per (wave, tile) on tile_cursor[tile] -- the per-hit returning
+ * atomic on the pixel's counter bounded qf_raster_intersect -- and a second launch (one wave per tile) counts the tile's
+ * records per pixel.  Afterwards:
+ *   bins        [n_tiles][64 * max_hits] 8-byte records (t bits | tri << 6 | pixel in tile); n_tiles = ceil(w/8) *
+ *               ceil(h/8), tiles row-major; bins_bytes >= qf_hit_bins_bytes(w, h, max_hits); 8-byte aligned
+ *   tile_cursor [n_tiles] records reserved (past the capacity the cursor keeps counting, nothing is written)
+ *   hit_count   [n_rays]  every pixel's candidate count, as qf_raster_intersect leaves it (> max_hits: overflowed);
+ *               all 64 pixels of a tile whose bin ran over are marked overflowed.  WRITTEN for every pixel: no fill
+ *   overflow    [1]       candidates beyond max_hits (zeroed here, with ray_flag)
+ *   tile_mask   [n_tiles] uint64, bit p = pixel p (row-major in the tile) is overflowed: its list is NOT in the bin
+ * Next: qf_bvh_repair_overflow (unchanged: it rewrites the per-ray rows hit_t / hit_tri and the counts of the overflowed
+ * pixels, of every pixel when ray_flag was raised), qf_tile_offsets, then qf_pack_tiles_bins.  The re-origin rule can
+ * not be decided up front on this route (no keep masks: the other pixels have no per-ray rows).  All buffers are the
+ * caller's; nothing is kept on the handle, so frames in flight on several streams only need buffers of their own.
+ * QF_ERR_UNSUPPORTED: more than 2^26 triangles (the record's id field).  max_hits <= 32 for qf_pack_tiles_bins.     */
+int64_t qf_hit_bins_bytes(int32_t width, int32_t height, int32_t max_hits);      /* -1: invalid arguments */
+int qf_raster_intersect_tiles(qf_bvh *bvh, const qf_camera *cam /* host */, const float *rays_o, const float *rays_d,
+                              int64_t n_rays, int32_t max_hits, int32_t *tile_cursor, uint64_t *tile_mask, void *bins,
+                              int64_t bins_bytes, int32_t *hit_count, int32_t *overflow, int32_t *ray_flag /* or NULL */,
+                              void *stream);
+
 /* Occupancy-grid ray marching: nerfacc 0.5.3 OccGridEstimator.sampling -> traverse_grids for one grid level and
  * cone_angle = 0 (examples/utils.py:137-147,266-285).  Samples are [t0 + k*step, t0 + (k+1)*step],
  * t0 = the ray's entry into `aabb` clipped to [near_plane (or t_min[r]), far_plane (or t_max[r])], kept iff the
@@ -683,6 +707,17 @@ int qf_pack_tiles(const float *rays_o, const float *rays_d, int32_t width, int32
                                              zero_word) -- no memset launch; the count stays in *dropped */,
                   void *stream);
 
+/* qf_pack_tiles after qf_raster_intersect_tiles + qf_bvh_repair_overflow + qf_tile_offsets: a pixel's list comes from
+ * its tile's bin, except for the pixels of tile_mask and -- when *ray_flag (or NULL) is raised -- for every pixel, which
+ * read their per-ray row of hit_t / hit_tri (both required: the repair writes both).  Same outputs, bit for bit.
+ * max_hits <= 32.                                                                                                 */
+int qf_pack_tiles_bins(const float *rays_o, const float *rays_d, int32_t width, int32_t height, int32_t max_hits,
+                       const int32_t *hit_tri, const float *hit_t, const int32_t *hit_count, const int64_t *tile_base,
+                       const int64_t *total, float *xyz_c, float *dirs_c, float *depth_c, int32_t *tri_c /* or NULL */,
+                       float min_separation, int32_t *final_count, int32_t *dropped, int64_t *host_out,
+                       int32_t dropped_is_zero, const int32_t *tile_cursor, const uint64_t *tile_mask, const void *bins,
+                       const int32_t *ray_flag, void *stream);
+
 /* Spatially coherent PROCESSING order for qf_field_forward when the rays are a row-major width x height image:
  * (8x8 pixel tile, hit rank, pixel in tile).  Two steps around one exclusive scan the caller does:
  *   qf_tile_totals     : tile_total[tile] = sum of hit_count over the tile's pixels (row-major tiles, ceil(w/8) a row)
@@ -727,7 +762,14 @@ int qf_row_sample_counts(const int32_t *hit_count, int32_t max_hits, int32_t wid
  * overflow count travel to host_block[0..1] (pinned, device-writable; may be NULL) on their own.  Every pointer is
  * caller-owned device memory of the stated size; the results are those of the separate calls, bit for bit (the
  * function only composes them -- a row band of a frame sharded over 8 GPUs is ~0.3 ms of kernels, and a dozen
- * separately bound calls per band kept the host behind the GPU).  No reference counterpart.                       */
+ * separately bound calls per band kept the host behind the GPU).  No reference counterpart.
+ * The plain pass (cull_chunks bit 0 clear) with a field, max_hits <= 32 and fewer than 2^26 triangles takes the hit-bin
+ * route instead -- qf_raster_intersect_tiles ... qf_pack_tiles_bins, same results bit for bit -- unless cull_chunks bit 1
+ * (QF_FRAME_PER_RAY_LISTS) asks for the per-ray lists.  Its bins, cursors and masks are carved out of the job's own
+ * rgb_c / sigma_c, which nothing writes before the field runs -- after the pack has read them -- so nothing is kept on
+ * the handle and a caller with frames in flight on two streams needs what it needed before: a job's buffers are not
+ * shared with another job in flight.                                                                            */
+#define QF_FRAME_PER_RAY_LISTS 2   /* qf_frame_job.cull_chunks, bit 1 */
 #define QF_FIELD_FP32 0   /* qf_field_forward: fp32 table and weights (every zero-initialised job) */
 #define QF_FIELD_BF16 1   /* qf_field_forward_bf16 */
 #define QF_FIELD_FP16 2   /* qf_field_forward_f16 */
@@ -736,7 +778,8 @@ typedef struct qf_frame_job {
     const float *rays_o, *rays_d;       /* [n_rays,3] */
     int64_t n_rays;                     /* == camera->width * camera->height */
     int32_t max_hits;                   /* K */
-    int32_t cull_chunks;                /* qf_raster_intersect's: the camera sees a part of the scene */
+    int32_t cull_chunks;                /* bit 0: qf_raster_intersect's (the camera sees a part of the scene);
+                                           bit 1: QF_FRAME_PER_RAY_LISTS */
     float min_separation;               /* the tile pack's re-origin rule (0 = off) */
     int32_t bg_mode;                    /* QF_BG_* */
     float delta_const;                  /* render_step_size */

@@ -150,6 +150,10 @@ _SIGNATURES = {
     "qf_frame_offsets": (c_int, [_P, c_int64, c_int32, c_int32, c_int32, _P, _P, _P, c_int64, _P, _P, _P, c_int32, _P]),
     "qf_banded_tile_count": (c_int64, [c_int32, c_int32, c_int32]),
     "qf_tile_offsets": (c_int, [_P, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    "qf_hit_bins_bytes": (c_int64, [c_int32, c_int32, c_int32]),
+    "qf_raster_intersect_tiles": (c_int, [_P, POINTER(Camera), _P, _P, c_int64, c_int32, _P, _P, _P, c_int64, _P, _P, _P, _P]),
+    "qf_pack_tiles_bins": (c_int, [_P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_float, _P, _P, _P,
+                                   c_int32, _P, _P, _P, _P, _P]),
     "qf_pack_tiles": (c_int, [_P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_float, _P, _P, _P, c_int32, _P]),
     "qf_pack_samples": (c_int, [_P, _P, c_int64, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_float, _P, _P]),
     "qf_tile_totals": (c_int, [_P, c_int32, c_int32, _P, _P]),

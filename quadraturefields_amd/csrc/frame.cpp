@@ -1,6 +1,8 @@
 // One camera frame of the mesh-quadrature render as ONE host call: the fixed launch sequence of a render-only frame
 // (FrameRenderer.render_async: examples/utils.py:510-620 behind nerf_synthetic.py:310-373's camera rays), composed
-// from the library's own entry points -- nothing here launches a kernel of its own.
+// from the library's own entry points -- nothing here launches a kernel of its own.  Two sequences: the per-ray lists
+// (qf_raster_intersect ... qf_pack_tiles) and, for the plain pass with a field, the hit bins (qf_raster_intersect_tiles
+// ... qf_pack_tiles_bins); same frame bit for bit.
 #include "qf_common.h"
 
 extern "C" int qf_frame_render(qf_bvh *bvh, const qf_frame_job *job, void *stream)
@@ -45,24 +47,52 @@ extern "C" int qf_frame_render(qf_bvh *bvh, const qf_frame_job *job, void *strea
     }
     const int64_t cap = j.n_rays * (int64_t)j.max_hits;
     int32_t *overflow = j.hit_count + j.n_rays;
-    // 1. camera-coherent intersection (lists in arrival order), 2. exact K nearest for the pixels that overflowed
-    int rc = qf_raster_intersect(bvh, j.camera, j.rays_o, j.rays_d, j.n_rays, j.max_hits, j.hit_tri, j.hit_t, j.hit_count,
-                                 overflow, j.tri_c ? 0 : 2 /* no ids wanted: the pass skips their stores */, j.cull_chunks,
-                                 overflow + 1, stream);
-    if (rc != QF_OK) return rc;
-    // (... and for EVERY pixel when the pass's ray check found that the rays are not this camera's pixel grid: the pass
-    // wrote nothing then, and this launch is the intersection)
-    rc = qf_bvh_repair_overflow(bvh, j.rays_o, j.rays_d, j.n_rays, j.max_hits, w, j.hit_tri, j.hit_t, j.hit_count, nullptr,
-                                nullptr, overflow + 1, stream);
-    if (rc != QF_OK) return rc;
-    // 3. tile bases + slot total (device; a copy on its way to the pinned block), 4. the tile pack with the re-origin rule
-    rc = qf_tile_offsets(j.hit_count, j.max_hits, w, h, j.tile_base, j.total, overflow, overflow + 1, j.host_block, j.dropped,
-                         stream);
-    if (rc != QF_OK) return rc;
-    rc = qf_pack_tiles(j.rays_o, j.rays_d, w, h, j.max_hits, j.hit_tri, j.hit_t, j.hit_count, j.tile_base, j.total, j.xyz_c,
-                       j.dirs_c, j.depth_c, j.tri_c, nullptr, nullptr, j.min_separation, j.final_count, j.dropped, nullptr, 1,
-                       stream);
-    if (rc != QF_OK) return rc;
+    const int32_t cull = j.cull_chunks & 1;
+    // The hit-bin route (qf_raster_intersect_tiles): the bins live in rgb_c and the tile masks and cursors in sigma_c until
+    // the pack has read them; the field writes both only afterwards.
+    const int64_t n_tiles = (int64_t)((w + 7) / 8) * ((h + 7) / 8);
+    const int64_t bins_bytes = qf_hit_bins_bytes(w, h, j.max_hits);
+    const bool use_bins = j.field && !cull && !(j.cull_chunks & QF_FRAME_PER_RAY_LISTS) && j.max_hits <= 32 &&
+                          qf_bvh_num_triangles(bvh) < (1 << 26) && bins_bytes >= 0 &&
+                          bins_bytes <= cap * 3 * (int64_t)sizeof(float) && n_tiles * 12 <= cap * (int64_t)sizeof(float) &&
+                          reinterpret_cast<uintptr_t>(j.rgb_c) % 8 == 0 && reinterpret_cast<uintptr_t>(j.sigma_c) % 8 == 0;
+    if (use_bins) {
+        uint64_t *tile_mask = reinterpret_cast<uint64_t *>(j.sigma_c);
+        int32_t *tile_cursor = reinterpret_cast<int32_t *>(tile_mask + n_tiles);
+        int rc = qf_raster_intersect_tiles(bvh, j.camera, j.rays_o, j.rays_d, j.n_rays, j.max_hits, tile_cursor, tile_mask,
+                                           j.rgb_c, bins_bytes, j.hit_count, overflow, overflow + 1, stream);
+        if (rc != QF_OK) return rc;
+        rc = qf_bvh_repair_overflow(bvh, j.rays_o, j.rays_d, j.n_rays, j.max_hits, w, j.hit_tri, j.hit_t, j.hit_count, nullptr,
+                                    nullptr, overflow + 1, stream);
+        if (rc != QF_OK) return rc;
+        rc = qf_tile_offsets(j.hit_count, j.max_hits, w, h, j.tile_base, j.total, overflow, overflow + 1, j.host_block,
+                             j.dropped, stream);
+        if (rc != QF_OK) return rc;
+        rc = qf_pack_tiles_bins(j.rays_o, j.rays_d, w, h, j.max_hits, j.hit_tri, j.hit_t, j.hit_count, j.tile_base, j.total,
+                                j.xyz_c, j.dirs_c, j.depth_c, j.tri_c, j.min_separation, j.final_count, j.dropped, nullptr, 1,
+                                tile_cursor, tile_mask, j.rgb_c, overflow + 1, stream);
+        if (rc != QF_OK) return rc;
+    } else {
+        // 1. camera-coherent intersection (lists in arrival order), 2. exact K nearest for the pixels that overflowed
+        int rc = qf_raster_intersect(bvh, j.camera, j.rays_o, j.rays_d, j.n_rays, j.max_hits, j.hit_tri, j.hit_t, j.hit_count,
+                                     overflow, j.tri_c ? 0 : 2 /* no ids wanted: the pass skips their stores */, cull,
+                                     overflow + 1, stream);
+        if (rc != QF_OK) return rc;
+        // (... and for EVERY pixel when the pass's ray check found that the rays are not this camera's pixel grid: the pass
+        // wrote nothing then, and this launch is the intersection)
+        rc = qf_bvh_repair_overflow(bvh, j.rays_o, j.rays_d, j.n_rays, j.max_hits, w, j.hit_tri, j.hit_t, j.hit_count, nullptr,
+                                    nullptr, overflow + 1, stream);
+        if (rc != QF_OK) return rc;
+        // 3. tile bases + slot total (device; a copy on its way to the pinned block), 4. the tile pack with the re-origin rule
+        rc = qf_tile_offsets(j.hit_count, j.max_hits, w, h, j.tile_base, j.total, overflow, overflow + 1, j.host_block, j.dropped,
+                             stream);
+        if (rc != QF_OK) return rc;
+        rc = qf_pack_tiles(j.rays_o, j.rays_d, w, h, j.max_hits, j.hit_tri, j.hit_t, j.hit_count, j.tile_base, j.total, j.xyz_c,
+                           j.dirs_c, j.depth_c, j.tri_c, nullptr, nullptr, j.min_separation, j.final_count, j.dropped, nullptr, 1,
+                           stream);
+        if (rc != QF_OK) return rc;
+    }
+    int rc = QF_OK;
     if (!j.field) return QF_OK;                 // sampling only
     // 5. the field over min(*total, cap) points, in the job's precision, 6. the tile compositor
     if (j.field_precision == QF_FIELD_FP32) {

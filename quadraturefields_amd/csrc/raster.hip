@@ -1,5 +1,5 @@
 // The camera-coherent intersector: triangles rasterised against the pixel grid of one pinhole camera (plain, culled
-// and depth-slab passes), the device-side camera check, the K-nearest selection of the wide passes and the per-ray
+// and depth-slab passes; the plain pass also with its hits binned per 8x8 tile), the device-side camera check, the K-nearest selection of the wide passes and the per-ray
 // sort / re-origin filter of the hit lists.
 #include <type_traits>
 
@@ -105,12 +105,49 @@ __device__ __forceinline__ bool tri_setup(const float4 a, const float4 b, const 
     return true;
 }
 
-template <int kRasterLanes, bool kWide, bool kSlab = false>
+// ---- hit bins (the plain render-only frame, qf_raster_intersect_tiles): an accepted hit goes to the bin of its pixel's
+// 8x8 tile -- one dense run of at most 64 * K eight-byte records (t bits, tri << 6 | pixel in tile) per tile -- instead
+// of taking a slot in its pixel's list with a returning device-wide atomic of its own.  A wave stages its hits in LDS
+// (an LDS atomic per hit) and, after its last pixel, reserves space with ONE returning atomicAdd on tile_cursor[tile] per
+// distinct tile among each 64 staged hits; the reservation that runs past the capacity writes nothing beyond it and the
+// cursor keeps counting (tile_count_kernel then sends the whole tile to the repair).  Aggregating where the hit is found
+// instead -- among the lanes that find one in the same loop iteration -- was measured and did not pay: the atomic's round
+// trip stays in the per-candidate chain (profiles/r5/hit_bins.md).
+constexpr int kBinStage = 256;           // staged hits per wave (16 triangles find 64 on average); the rest go one by one
+constexpr int kBinIdBits = 26;           // triangle ids that fit beside the 6-bit pixel
+struct BinStage { int n; int tile[kBinStage]; uint2 rec[kBinStage]; };
+struct TileBins {
+    int32_t *cursor;                     // [n_tiles]
+    uint2 *bins;                         // [n_tiles][cap]
+    int cap;                             // 64 * max_hits
+    BinStage *stage;                     // the wave's own LDS area
+};
+
+// the lanes that call this together share one reservation per distinct tile
+__device__ __forceinline__ void bin_records(const TileBins &tb, int tile, uint2 rec)
+{
+    const int lane = (int)__lane_id();
+    for (;;) {
+        const int t0 = __builtin_amdgcn_readfirstlane(tile);
+        const unsigned long long m = __ballot(tile == t0);
+        if (tile == t0) {
+            const int rank = __popcll(m & ((1ull << lane) - 1ull));
+            int base = 0;
+            if (rank == 0) base = atomicAdd(&tb.cursor[t0], __popcll(m));
+            base = __shfl(base, __ffsll((long long)m) - 1, 64);
+            if (base + rank < tb.cap) tb.bins[(int64_t)t0 * tb.cap + base + rank] = rec;
+            break;
+        }
+    }
+}
+
+template <int kRasterLanes, bool kWide, bool kSlab = false, bool kBins = false>
 __device__ __forceinline__ void raster_triangle(const float4 *__restrict__ tris, int64_t tri_i, int sub, const RasterCam &cam,
                                                 const float *__restrict__ rays_o, const float *__restrict__ rays_d,
                                                 int max_hits, int32_t *__restrict__ hit_tri, float *__restrict__ hit_t,
                                                 int32_t *__restrict__ hit_count, int32_t *__restrict__ overflow,
-                                                const bool cam_origin, const SlabArgs slab = SlabArgs())
+                                                const bool cam_origin, const SlabArgs slab = SlabArgs(),
+                                                const TileBins bins = TileBins())
 {
     const float4 a = tris[tri_i * 3 + 0], b = tris[tri_i * 3 + 1], c = tris[tri_i * 3 + 2];
     const int id = __float_as_int(a.w);
@@ -161,6 +198,14 @@ __device__ __forceinline__ void raster_triangle(const float4 *__restrict__ tris,
             else atomicAdd(overflow, 1);
             continue;
         }
+        if (kBins) {
+            const int tile = (cy_ >> 3) * ((cam.w + 7) >> 3) + (cx_ >> 3);
+            const uint2 rec = make_uint2(__float_as_uint(t), ((uint32_t)id << 6) | (uint32_t)((cy_ & 7) * 8 + (cx_ & 7)));
+            const int at = atomicAdd(&bins.stage->n, 1);
+            if (at < kBinStage) { bins.stage->tile[at] = tile; bins.stage->rec[at] = rec; }
+            else bin_records(bins, tile, rec);
+            continue;
+        }
         const int slot = atomicAdd(&hit_count[ray], 1);
         if (slot < max_hits) {
             const int64_t at = kWide ? (int64_t)slot * ((int64_t)cam.w * cam.h) + ray : ray * max_hits + slot;
@@ -187,6 +232,82 @@ __global__ __launch_bounds__(256) void raster_kernel(const float4 *__restrict__ 
     const bool cam_origin = ray_flag != nullptr; // verified: every origin IS the camera centre
     raster_triangle<kRasterLanes, kWide>(tris, tri_i, sub, cam, rays_o, rays_d, max_hits, hit_tri, hit_t, hit_count, overflow,
                                          cam_origin);
+}
+
+// raster_kernel<kRasterLanes, false> with the hits going to the tile bins.  No lane leaves before the flush: the staged
+// hits are handed out by lane index.
+template <int kRasterLanes>
+__global__ __launch_bounds__(256) void raster_bins_kernel(const float4 *__restrict__ tris, int64_t n_tri, RasterCam cam,
+                                                          const float *__restrict__ rays_o, const float *__restrict__ rays_d,
+                                                          int max_hits, int32_t *__restrict__ tile_cursor,
+                                                          uint2 *__restrict__ bin_records_out,
+                                                          const int32_t *__restrict__ ray_flag)
+{
+    __shared__ BinStage s_stage[4];
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t tri_i = gid / kRasterLanes;
+    const int sub = (int)(gid % kRasterLanes);
+    if (ray_flag && *ray_flag) return;           // see raster_kernel (grid-uniform)
+    const bool cam_origin = ray_flag != nullptr;
+    const int lane = (int)(threadIdx.x & 63);
+    TileBins tb;
+    tb.cursor = tile_cursor;
+    tb.bins = bin_records_out;
+    tb.cap = 64 * max_hits;
+    tb.stage = &s_stage[threadIdx.x >> 6];
+    if (lane == 0) tb.stage->n = 0;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");       // (the area is the wave's own: no barrier between waves)
+    __builtin_amdgcn_wave_barrier();
+    if (tri_i < n_tri)
+        raster_triangle<kRasterLanes, false, false, true>(tris, tri_i, sub, cam, rays_o, rays_d, max_hits, nullptr, nullptr,
+                                                          nullptr, nullptr, cam_origin, SlabArgs(), tb);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    const int n = tb.stage->n < kBinStage ? tb.stage->n : kBinStage;
+    for (int i = lane; i < n; i += 64) bin_records(tb, tb.stage->tile[i], tb.stage->rec[i]);
+}
+
+// One wave per 8x8 tile after raster_bins_kernel: the tile's records -> the 64 hit_count words of its pixels (what the
+// flat pass's per-pixel atomics leave: the number of candidates, past K included), the frame's overflow word (+ count - K
+// per pixel, as the flat pass adds one per candidate past K; it only steers the caller's policy) and the tile's word of tile_mask: bit p set = pixel p's
+// list is not in the bin -- it collected more than K candidates and is qf_bvh_repair_overflow's -- so the pack reads its
+// per-ray row.  A bin that ran over its 64 * K records (some pixel of it holds more than K then) marks all its pixels.
+// Every count of the frame is written here: the route has no hit_count fill.
+__global__ __launch_bounds__(64) void tile_count_kernel(const int32_t *__restrict__ tile_cursor, const uint2 *__restrict__ bins,
+                                                        int max_hits, int w, int h, int tiles_x,
+                                                        int32_t *__restrict__ hit_count, int32_t *__restrict__ overflow,
+                                                        uint64_t *__restrict__ tile_mask)
+{
+    __shared__ int s_cnt[64];
+    const int tile = blockIdx.x, lane = threadIdx.x;
+    const int cap = 64 * max_hits;
+    const int cursor = tile_cursor[tile];
+    const int n = cursor < cap ? cursor : cap;
+    const int px = (tile % tiles_x) * 8 + (lane & 7), py = (tile / tiles_x) * 8 + (lane >> 3);
+    const bool inside = px < w && py < h;
+    int c = 0;
+    if (n > 0) {                                              // wave-uniform
+        s_cnt[lane] = 0;
+        __syncthreads();
+        const uint2 *run = bins + (int64_t)tile * cap;
+        for (int i = lane; i < n; i += 64) atomicAdd(&s_cnt[run[i].y & 63u], 1);
+        __syncthreads();
+        c = s_cnt[lane];
+    }
+    int over = c > max_hits ? c - max_hits : 0;
+    if (cursor > cap) {                                       // records were lost: the whole tile goes to the repair
+        c = c > max_hits ? c : max_hits + 1;
+        // (its candidates past K: at least cursor - cap, and exactly that when every pixel of the tile holds K or more)
+        over = lane == 0 ? cursor - cap : 0;
+    }
+    if (inside) hit_count[(int64_t)py * w + px] = c;
+    const unsigned long long mask = __ballot(inside && c > max_hits);
+    if (mask) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) over += __shfl_xor(over, off, 64);
+        if (lane == 0) atomicAdd(overflow, over);
+    }
+    if (lane == 0) tile_mask[tile] = mask;
 }
 
 // The precondition of the whole camera-coherent route, VERIFIED (round 4): ray i of the batch must be pixel
@@ -883,6 +1004,53 @@ extern "C" int qf_raster_intersect(qf_bvh *bvh, const qf_camera *cam, const floa
                                  origin_flag, cull_chunks != 0, st, sort_lists == 2);
     if (rc != QF_OK) return rc;
     if (sort_lists == 1 && n_rays > 0) return filter_launch(n_rays, max_hits, bvh->min_sep, hit_tri, hit_t, hit_count, st);
+    return QF_OK;
+}
+
+extern "C" int64_t qf_hit_bins_bytes(int32_t width, int32_t height, int32_t max_hits)
+{
+    if (width < 1 || height < 1 || max_hits < 1 || max_hits > kMaxHits) return -1;
+    return (int64_t)((width + 7) / 8) * ((height + 7) / 8) * 64 * max_hits * (int64_t)sizeof(uint2);
+}
+
+extern "C" int qf_raster_intersect_tiles(qf_bvh *bvh, const qf_camera *cam, const float *rays_o, const float *rays_d,
+                                         int64_t n_rays, int32_t max_hits, int32_t *tile_cursor, uint64_t *tile_mask,
+                                         void *bins, int64_t bins_bytes, int32_t *hit_count, int32_t *overflow,
+                                         int32_t *origin_flag, void *stream)
+{
+    if (!raster_args_ok(bvh, cam, n_rays, max_hits)) return QF_ERR_INVALID_ARGUMENT;
+    if (!rays_o || !rays_d || !tile_cursor || !tile_mask || !bins || !hit_count || !overflow) return QF_ERR_INVALID_ARGUMENT;
+    if (bins_bytes < qf_hit_bins_bytes(cam->width, cam->height, max_hits)) return QF_ERR_INVALID_ARGUMENT;
+    if (reinterpret_cast<uintptr_t>(bins) % sizeof(uint2) || reinterpret_cast<uintptr_t>(tile_mask) % sizeof(uint64_t))
+        return QF_ERR_INVALID_ARGUMENT;
+    if (bvh->n_tri >= (1 << kBinIdBits)) return QF_ERR_UNSUPPORTED;         // the record's id field
+    hipStream_t st = qf_stream(stream);
+    const int tiles_x = (cam->width + 7) / 8, n_tiles = tiles_x * ((cam->height + 7) / 8);
+    // only the cursors, the overflow word and the ray flag are zeroed: tile_count_kernel writes every count
+    QF_HIP_TRY(hipMemsetAsync(tile_cursor, 0, (size_t)n_tiles * sizeof(int32_t), st));
+    if (origin_flag == overflow + 1) {
+        QF_HIP_TRY(hipMemsetAsync(overflow, 0, 2 * sizeof(int32_t), st));
+    } else {
+        QF_HIP_TRY(hipMemsetAsync(overflow, 0, sizeof(int32_t), st));
+        if (origin_flag) QF_HIP_TRY(hipMemsetAsync(origin_flag, 0, sizeof(int32_t), st));
+    }
+    const RasterCam rc = make_raster_cam(cam);
+    uint2 *records = reinterpret_cast<uint2 *>(bins);
+    if (bvh->n_tri > 0) {
+        const int lanes = raster_lanes(n_rays, bvh->n_tri);
+        const int64_t blocks = qf_div_up(bvh->n_tri * lanes, 256);
+        if (blocks > 0x7fffffff) return QF_ERR_UNSUPPORTED;
+        camera_check_launch(rc, rays_o, rays_d, n_rays, origin_flag, st);
+        QF_LAUNCH_CHECK();
+        with_lanes(lanes, [&](auto L) {
+            hipLaunchKernelGGL(raster_bins_kernel<decltype(L)::value>, dim3((unsigned)blocks), dim3(256), 0, st,
+                               reinterpret_cast<const float4 *>(bvh->d_tris), bvh->n_tri, rc, rays_o, rays_d, (int)max_hits,
+                               tile_cursor, records, origin_flag);
+        });
+    }
+    hipLaunchKernelGGL(tile_count_kernel, dim3((unsigned)n_tiles), dim3(64), 0, st, tile_cursor, records, (int)max_hits,
+                       rc.w, rc.h, tiles_x, hit_count, overflow, tile_mask);
+    QF_LAUNCH_CHECK();
     return QF_OK;
 }
 

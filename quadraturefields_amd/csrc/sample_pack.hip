@@ -6,38 +6,11 @@
 
 namespace {
 
-// The bitonic sort of sort_row_32 (exact_common.h) fed straight from global memory (the pack kernels): lane = ray reads
-// ITS OWN list -- rows of K entries, four entries per request (f32x4u) -- into the network's registers, sorts, and leaves
-// the sorted list in its LDS row for the loops that index it by rank.  Every load of the list is independent of the others, so the wave
-// waits for memory once; the staged variant (coalesced loop -> LDS -> registers) waited once per loop iteration, which
-// is what a tile wave's time was made of (one wave per tile, nothing to overlap with).  kN = 16 or 32: network size,
-// picked per tile from its longest list.  `deepest` (wave-uniform) bounds what is read.
+// The network itself: kN entries in registers ((t, tri) keys with ids, distances alone without), the first `cnt` of them
+// live, sorted and left in the lane's LDS row.
 template <int kN, bool kTri>
-__device__ __forceinline__ void load_sort_row(const float *__restrict__ g_t, const int32_t *__restrict__ g_i, int K,
-                                              int cnt, int deepest, float *row_t, int32_t *row_i)
+__device__ __forceinline__ void sort_to_row(float (&t)[kN], int32_t (&id)[kN], int cnt, float *row_t, int32_t *row_i)
 {
-    float t[kN];
-    int32_t id[kN];
-#pragma unroll
-    for (int j = 0; j < kN / 4; ++j) {
-        f32x4u v = {INFINITY, INFINITY, INFINITY, INFINITY};
-        i32x4u w = {-1, -1, -1, -1};
-        if (4 * j < deepest) {                                  // wave-uniform; deepest <= K
-            if (4 * j + 3 < K) {                                // the whole quartet lies inside the row: one request
-                v = *reinterpret_cast<const f32x4u *>(g_t + 4 * j);
-                if (kTri) w = *reinterpret_cast<const i32x4u *>(g_i + 4 * j);
-            } else {                                            // the row's last 1..3 entries
-#pragma unroll
-                for (int e = 0; e < 3; ++e)
-                    if (4 * j + e < K) {
-                        v[e] = g_t[4 * j + e];
-                        if (kTri) w[e] = g_i[4 * j + e];
-                    }
-            }
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { t[4 * j + e] = v[e]; id[4 * j + e] = w[e]; }
-    }
     if (kTri) {
         uint64_t key[kN];
 #pragma unroll
@@ -84,6 +57,60 @@ __device__ __forceinline__ void load_sort_row(const float *__restrict__ g_t, con
         for (int k = 0; k < kN; ++k)
             if (k < cnt) row_t[k] = t[k];
     }
+}
+
+// The bitonic sort of sort_row_32 (exact_common.h) fed straight from global memory (the pack kernels): lane = ray reads
+// ITS OWN list -- rows of K entries, four entries per request (f32x4u) -- into the network's registers, sorts, and leaves
+// the sorted list in its LDS row for the loops that index it by rank.  Every load of the list is independent of the others, so the wave
+// waits for memory once; the staged variant (coalesced loop -> LDS -> registers) waited once per loop iteration, which
+// is what a tile wave's time was made of (one wave per tile, nothing to overlap with).  kN = 16 or 32: network size,
+// picked per tile from its longest list.  `deepest` (wave-uniform) bounds what is read.
+template <int kN, bool kTri>
+__device__ __forceinline__ void load_sort_row(const float *__restrict__ g_t, const int32_t *__restrict__ g_i, int K,
+                                              int cnt, int deepest, float *row_t, int32_t *row_i)
+{
+    float t[kN];
+    int32_t id[kN];
+#pragma unroll
+    for (int j = 0; j < kN / 4; ++j) {
+        f32x4u v = {INFINITY, INFINITY, INFINITY, INFINITY};
+        i32x4u w = {-1, -1, -1, -1};
+        if (4 * j < deepest) {                                  // wave-uniform; deepest <= K
+            if (4 * j + 3 < K) {                                // the whole quartet lies inside the row: one request
+                v = *reinterpret_cast<const f32x4u *>(g_t + 4 * j);
+                if (kTri) w = *reinterpret_cast<const i32x4u *>(g_i + 4 * j);
+            } else {                                            // the row's last 1..3 entries
+#pragma unroll
+                for (int e = 0; e < 3; ++e)
+                    if (4 * j + e < K) {
+                        v[e] = g_t[4 * j + e];
+                        if (kTri) w[e] = g_i[4 * j + e];
+                    }
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { t[4 * j + e] = v[e]; id[4 * j + e] = w[e]; }
+    }
+    sort_to_row<kN, kTri>(t, id, cnt, row_t, row_i);
+}
+
+// A binned pixel's list (pack_tiles_kernel<kTri, true>): its `cnt` unordered entries are in its LDS row already, put
+// there record by record; the same network sorts them in place.
+template <int kN, bool kTri>
+__device__ __forceinline__ void sort_row_in_place(int cnt, int deepest, float *row_t, int32_t *row_i)
+{
+    float t[kN];
+    int32_t id[kN];
+#pragma unroll
+    for (int k = 0; k < kN; ++k) {
+        t[k] = INFINITY;
+        id[k] = -1;
+        if (k < deepest && k < cnt) {                           // (k < deepest: wave-uniform, deepest <= K = the row's length)
+            t[k] = row_t[k];
+            if (kTri) id[k] = row_i[k];
+        }
+    }
+    sort_to_row<kN, kTri>(t, id, cnt, row_t, row_i);
 }
 
 // sampling_raytrace_numpy (mesh_utils.py:359-387): per-ray hit lists (in ANY order) -> packed samples sorted by
@@ -257,13 +284,20 @@ __global__ __launch_bounds__(kPackRays) void pack_samples_kernel(
 // before) + (pixels before this one that also have a rank-k hit): the coherent order of qf_coherent_layout, produced
 // by the ballots directly, so neither the order, nor its inverse, nor index_ray / index_tri / ray-major depths exist
 // for such a frame.  Values are pack_samples_kernel's bit for bit (tests).
-template <bool kTri>
+// kBins (qf_pack_tiles_bins, K <= 32): the lists come from the tile's hit bin (qf_raster_intersect_tiles) -- one dense run
+// of min(tile_cursor, 64 K) records, dealt to the pixels' LDS rows by the pixel-in-tile they carry (LDS counters) --
+// except for the pixels of tile_mask (repaired by qf_bvh_repair_overflow: their per-ray rows hold the exact K nearest)
+// and for every pixel when the pass's ray flag is up (the pass wrote nothing, the repair traversed every ray): those
+// read their per-ray row as without bins.  From the sorted rows onwards nothing differs.
+template <bool kTri, bool kBins>
 __global__ __launch_bounds__(64) void pack_tiles_kernel(
     const float *__restrict__ rays_o, const float *__restrict__ rays_d, int w, int h, int tiles_x, int n_tiles, int max_hits,
     const int32_t *__restrict__ hit_tri, const float *__restrict__ hit_t, const int32_t *__restrict__ hit_count,
     const int64_t *__restrict__ tile_base, const int64_t *__restrict__ total, float *__restrict__ xyz_c,
     float *__restrict__ dirs_c, float *__restrict__ depth_c, int32_t *__restrict__ tri_c, const uint64_t *__restrict__ keep_mask,
-    const int32_t *__restrict__ raw_count, float min_sep, int32_t *__restrict__ final_count, int32_t *__restrict__ dropped)
+    const int32_t *__restrict__ raw_count, float min_sep, int32_t *__restrict__ final_count, int32_t *__restrict__ dropped,
+    const int32_t *__restrict__ tile_cursor, const uint64_t *__restrict__ tile_mask, const uint2 *__restrict__ bins,
+    const int32_t *__restrict__ ray_flag)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int K = max_hits, Kp = max_hits | 1;            // odd row stride: conflict-free column access
@@ -302,7 +336,34 @@ __global__ __launch_bounds__(64) void pack_tiles_kernel(
     const float ox = rays_o[ray * 3], oy = rays_o[ray * 3 + 1], oz = rays_o[ray * 3 + 2];
     const float dx = rays_d[ray * 3], dy = rays_d[ray * 3 + 1], dz = rays_d[ray * 3 + 2];
     int64_t base = tile_base[tile];
-    if (K <= 32) {
+    if (kBins) {
+        __shared__ int s_fill[64];
+        const unsigned long long by_row = (ray_flag && *ray_flag) ? ~0ull : tile_mask[tile];
+        const int cap = 64 * K;
+        const int cursor = tile_cursor[tile];
+        const int n = by_row == ~0ull ? 0 : (cursor < cap ? cursor : cap);
+        const uint2 *run = bins + (int64_t)tile * cap;
+        s_fill[lane] = 0;
+        __syncthreads();
+        for (int i = lane; i < n; i += 64) {
+            const uint2 rec = run[i];
+            const int p = (int)(rec.y & 63u);
+            const int at = atomicAdd(&s_fill[p], 1);
+            if (!((by_row >> p) & 1ull) && at < K) {          // (a binned pixel holds at most K records)
+                s_t[p * Kp + at] = __uint_as_float(rec.x);
+                if (kTri) s_tri[p * Kp + at] = (int32_t)(rec.y >> 6);
+            }
+        }
+        __syncthreads();
+        const bool own_row = (by_row >> lane) & 1ull;
+        if (deepest <= 16) {
+            if (own_row) load_sort_row<16, kTri>(hit_t + ray * K, hit_tri + ray * K, K, cnt, deepest, row_t, row_i);
+            else sort_row_in_place<16, kTri>(cnt, deepest, row_t, row_i);
+        } else {
+            if (own_row) load_sort_row<32, kTri>(hit_t + ray * K, hit_tri + ray * K, K, cnt, deepest, row_t, row_i);
+            else sort_row_in_place<32, kTri>(cnt, deepest, row_t, row_i);
+        }
+    } else if (K <= 32) {
         // lists of up to 32 hits: global memory -> registers -> sorted -> the lane's own LDS row (load_sort_row); no lane
         // reads another lane's row below, so no barrier
         if (deepest <= 16) load_sort_row<16, kTri>(hit_t + ray * K, hit_tri + ray * K, K, cnt, deepest, row_t, row_i);
@@ -602,11 +663,13 @@ extern "C" int qf_pack_samples(const float *rays_o, const float *rays_d, int64_t
     return QF_OK;
 }
 
-extern "C" int qf_pack_tiles(const float *rays_o, const float *rays_d, int32_t width, int32_t height, int32_t max_hits,
+// qf_pack_tiles and qf_pack_tiles_bins (tile_cursor / tile_mask / bins set)
+static int pack_tiles_launch(const float *rays_o, const float *rays_d, int32_t width, int32_t height, int32_t max_hits,
                              const int32_t *hit_tri, const float *hit_t, const int32_t *hit_count, const int64_t *tile_base,
                              const int64_t *total, float *xyz_c, float *dirs_c, float *depth_c, int32_t *tri_c,
                              const uint64_t *keep_mask, const int32_t *raw_count, float min_separation,
                              int32_t *final_count, int32_t *dropped, int64_t *host_out, int32_t dropped_is_zero,
+                             const int32_t *tile_cursor, const uint64_t *tile_mask, const void *bins, const int32_t *ray_flag,
                              void *stream)
 {
     if ((keep_mask == nullptr) != (raw_count == nullptr)) return QF_ERR_INVALID_ARGUMENT;
@@ -622,14 +685,42 @@ extern "C" int qf_pack_tiles(const float *rays_o, const float *rays_d, int32_t w
     const int tiles_x = (width + 7) / 8, tiles_y = (height + 7) / 8;
     const float sep = rule_here ? min_separation : 0.0f;
     // with triangle ids the LDS rows stage them beside the distances
-    auto *kernel = tri_c ? pack_tiles_kernel<true> : pack_tiles_kernel<false>;
+    auto *kernel = bins ? (tri_c ? pack_tiles_kernel<true, true> : pack_tiles_kernel<false, true>)
+                        : (tri_c ? pack_tiles_kernel<true, false> : pack_tiles_kernel<false, false>);
     const size_t lds = (size_t)64 * (max_hits | 1) * (tri_c ? 8 : 4);
     hipLaunchKernelGGL(kernel, dim3((unsigned)(tiles_x * tiles_y)), dim3(64), lds, st, rays_o, rays_d, (int)width, (int)height,
                        tiles_x, tiles_x * tiles_y, (int)max_hits, hit_tri, hit_t, hit_count, tile_base, total, xyz_c, dirs_c,
-                       depth_c, tri_c, keep_mask, raw_count, sep, final_count, dropped);
+                       depth_c, tri_c, keep_mask, raw_count, sep, final_count, dropped, tile_cursor, tile_mask,
+                       reinterpret_cast<const uint2 *>(bins), ray_flag);
     if (host_out) hipLaunchKernelGGL(publish_dropped_kernel, dim3(1), dim3(1), 0, st, dropped, host_out);
     QF_LAUNCH_CHECK();
     return QF_OK;
+}
+
+extern "C" int qf_pack_tiles(const float *rays_o, const float *rays_d, int32_t width, int32_t height, int32_t max_hits,
+                             const int32_t *hit_tri, const float *hit_t, const int32_t *hit_count, const int64_t *tile_base,
+                             const int64_t *total, float *xyz_c, float *dirs_c, float *depth_c, int32_t *tri_c,
+                             const uint64_t *keep_mask, const int32_t *raw_count, float min_separation,
+                             int32_t *final_count, int32_t *dropped, int64_t *host_out, int32_t dropped_is_zero,
+                             void *stream)
+{
+    return pack_tiles_launch(rays_o, rays_d, width, height, max_hits, hit_tri, hit_t, hit_count, tile_base, total, xyz_c, dirs_c,
+                             depth_c, tri_c, keep_mask, raw_count, min_separation, final_count, dropped, host_out,
+                             dropped_is_zero, nullptr, nullptr, nullptr, nullptr, stream);
+}
+
+extern "C" int qf_pack_tiles_bins(const float *rays_o, const float *rays_d, int32_t width, int32_t height, int32_t max_hits,
+                                  const int32_t *hit_tri, const float *hit_t, const int32_t *hit_count,
+                                  const int64_t *tile_base, const int64_t *total, float *xyz_c, float *dirs_c, float *depth_c,
+                                  int32_t *tri_c, float min_separation, int32_t *final_count, int32_t *dropped,
+                                  int64_t *host_out, int32_t dropped_is_zero, const int32_t *tile_cursor,
+                                  const uint64_t *tile_mask, const void *bins, const int32_t *ray_flag, void *stream)
+{
+    if (!tile_cursor || !tile_mask || !bins || max_hits > 32) return QF_ERR_INVALID_ARGUMENT;
+    if (!hit_tri) return QF_ERR_INVALID_ARGUMENT;           // (a repaired pixel's row: the repair writes ids on every route)
+    return pack_tiles_launch(rays_o, rays_d, width, height, max_hits, hit_tri, hit_t, hit_count, tile_base, total, xyz_c, dirs_c,
+                             depth_c, tri_c, nullptr, nullptr, min_separation, final_count, dropped, host_out, dropped_is_zero,
+                             tile_cursor, tile_mask, bins, ray_flag, stream);
 }
 
 extern "C" int qf_resort_by_depth(const int64_t *index_ray, const float *depth, int64_t n, int64_t *perm, void *stream)

@@ -448,9 +448,37 @@ class RayIntersector:
         frame._scratch, frame._seq = self._scratch_stamp
         return frame
 
+    #: render-only frames on the plain pass bin their hits per 8x8 tile (``qf_raster_intersect_tiles``); False keeps
+    #: them on the per-ray lists (the two routes give the same frame bit for bit)
+    hit_bins = True
+
+    def _hit_bins_ready(self, k, camera) -> bool:
+        """Is this frame's pass the plain one (no wide lists, no culling, rule not decided up front) at a K and a triangle
+        count the hit bins' records hold?"""
+        self._seed_policy(k)
+        return (self.hit_bins and int(self.raster_wide) <= k and k <= 32 and not getattr(camera, "cull", False)
+                and int(self.mesh.faces.shape[0]) < (1 << 26) and not (self.min_separation > 0 and self._rule_upfront > 0))
+
+    def _bin_scratch(self, camera, k):
+        """(tile cursors, tile masks, bins) of a frame on the hit-bin route: one set per (stream, scratch slot), like the
+        frame scratch -- two frames in flight never share bins -- grown to the largest frame seen there."""
+        key = (_C.raw_stream(), self.scratch_slot)
+        n_tiles = ((int(camera.width) + 7) // 8) * ((int(camera.height) + 7) // 8)
+        nbytes = int(_C.lib().qf_hit_bins_bytes(int(camera.width), int(camera.height), k))
+        if nbytes < 0:
+            raise _C.QFError("qf_hit_bins_bytes failed")
+        s = self.__dict__.setdefault("_bin_scratch_sets", {}).get(key)
+        if s is None or s[0].numel() < n_tiles or s[2].numel() < nbytes // 8:
+            s = self._bin_scratch_sets[key] = (torch.empty((n_tiles,), dtype=torch.int32, device=self.device),
+                                               torch.empty((n_tiles,), dtype=torch.int64, device=self.device),
+                                               torch.empty((nbytes // 8,), dtype=torch.int64, device=self.device))
+        return s
+
     @_on_device
-    def _hits_raster_frame(self, o, d, k, camera):
-        """Camera-coherent pass whose overflow counter lives next to the frame's sample total (one readback)."""
+    def _hits_raster_frame(self, o, d, k, camera, bins=False):
+        """Camera-coherent pass whose overflow counter lives next to the frame's sample total (one readback).
+        ``bins`` (``_hit_bins_ready``): the hits go to per-tile bins; only the overflowed pixels' per-ray rows are
+        written (by the repair), and ``hit_count._qf_bins`` carries the bins to the tile pack."""
         n = o.shape[0]
         hit_tri, hit_t, _ = self._alloc_hits(n, k)
         # the overflow counter rides right behind the counts (qf_raster_intersect then zeroes both with one fill); the
@@ -464,6 +492,15 @@ class RayIntersector:
         wide = max(int(self.raster_wide), 0)
         # a camera that sees part of the scene (parallel.band_camera sets .cull): cull the triangles in chunks first
         cull = 1 if getattr(camera, "cull", False) else 0
+        if bins:
+            cursor, mask, records = self._bin_scratch(camera, k)
+            _C.check(_C.lib().qf_raster_intersect_tiles(self._handle, ctypes.byref(camera), _C.ptr(o), _C.ptr(d), n, k,
+                                                        _C.ptr(cursor), _C.ptr(mask), _C.ptr(records), records.numel() * 8,
+                                                        _C.ptr(hit_count), _C.ptr(overflow), _C.ptr(origin_flag),
+                                                        _C.stream()), "qf_raster_intersect_tiles")
+            self._repair(o, d, k, int(camera.width), hit_tri, hit_t, hit_count, with_mask=False, all_flag=origin_flag)
+            hit_count._qf_bins = (cursor, mask, records, origin_flag)
+            return hit_tri, hit_t, hit_count, overflow
         if wide > k and self.raster_slabs >= 2:
             sel_cap = k + 8 if self.min_separation > 0 else k            # select_capacity() of the kernels
             wide_s = min(sel_cap + 1 + self.SLAB_ROOM, 4096)
@@ -613,14 +650,24 @@ class RayIntersector:
             optimistic = False
             final_count = torch.empty((n,), dtype=torch.int32, device=dev)
             frame.tri_c = torch.empty((cap,), dtype=torch.int32, device=dev) if want_tri else None
-            _C.check(_C.lib().qf_pack_tiles(_C.ptr(o), _C.ptr(d), int(width), n // int(width), k, _C.ptr(hit_tri),
-                                            _C.ptr(hit_t), _C.ptr(hit_count), _C.ptr(tile_base), _C.ptr(buf[n:]),
-                                            _C.ptr(xyz_c), _C.ptr(dirs_c), _C.ptr(depth_c), _C.ptr(frame.tri_c),
-                                            _C.ptr(keep[0]), _C.ptr(keep[1]),
-                                            float(self.min_separation) if keep[0] is None else 0.0,
-                                            _C.ptr(final_count), _C.ptr(dropped),
-                                            ctypes.c_void_p(host.data_ptr()) if publish else None, 1, _C.stream()),
-                     "qf_pack_tiles")
+            bins = getattr(hit_count, "_qf_bins", None)
+            if bins is not None:              # the hit-bin route (``_hits_raster_frame``): lists from the tiles' bins
+                _C.check(_C.lib().qf_pack_tiles_bins(_C.ptr(o), _C.ptr(d), int(width), n // int(width), k, _C.ptr(hit_tri),
+                                                     _C.ptr(hit_t), _C.ptr(hit_count), _C.ptr(tile_base), _C.ptr(buf[n:]),
+                                                     _C.ptr(xyz_c), _C.ptr(dirs_c), _C.ptr(depth_c), _C.ptr(frame.tri_c),
+                                                     float(self.min_separation), _C.ptr(final_count), _C.ptr(dropped),
+                                                     ctypes.c_void_p(host.data_ptr()) if publish else None, 1,
+                                                     _C.ptr(bins[0]), _C.ptr(bins[1]), _C.ptr(bins[2]), _C.ptr(bins[3]),
+                                                     _C.stream()), "qf_pack_tiles_bins")
+            else:
+                _C.check(_C.lib().qf_pack_tiles(_C.ptr(o), _C.ptr(d), int(width), n // int(width), k, _C.ptr(hit_tri),
+                                                _C.ptr(hit_t), _C.ptr(hit_count), _C.ptr(tile_base), _C.ptr(buf[n:]),
+                                                _C.ptr(xyz_c), _C.ptr(dirs_c), _C.ptr(depth_c), _C.ptr(frame.tri_c),
+                                                _C.ptr(keep[0]), _C.ptr(keep[1]),
+                                                float(self.min_separation) if keep[0] is None else 0.0,
+                                                _C.ptr(final_count), _C.ptr(dropped),
+                                                ctypes.c_void_p(host.data_ptr()) if publish else None, 1, _C.stream()),
+                         "qf_pack_tiles")
             frame.hit_count = final_count
             frame.dropped_dev = None if publish else dropped
             ev_flag.record()
@@ -863,7 +910,8 @@ class RayIntersector:
             raise ValueError("sample_frame_device: origins / vectors must be the camera's full pixel grid")
         self._settle_deferred_policy()
         if self.want_raster(camera):
-            hit_tri, hit_t, hit_count, overflow = self._hits_raster_frame(o, d, k, camera)
+            hit_tri, hit_t, hit_count, overflow = self._hits_raster_frame(o, d, k, camera,
+                                                                          bins=self._hit_bins_ready(k, camera))
         else:
             hit_tri, hit_t, hit_count = self._hits_bvh(o, d, k, camera.width)
             overflow = None
@@ -915,7 +963,7 @@ class RayIntersector:
         job = _C.FrameJob()
         job.camera = ctypes.addressof(camera)
         job.rays_o, job.rays_d, job.n_rays, job.max_hits = o.data_ptr(), d.data_ptr(), n, k
-        job.cull_chunks = 1 if getattr(camera, "cull", False) else 0
+        job.cull_chunks = (1 if getattr(camera, "cull", False) else 0) | (0 if self.hit_bins else 2)   # QF_FRAME_PER_RAY_LISTS
         job.min_separation = float(self.min_separation)
         job.hit_tri, job.hit_t, job.hit_count = hit_tri.data_ptr(), hit_t.data_ptr(), counts.data_ptr()
         job.final_count, job.tile_base = final_count.data_ptr(), tile_base.data_ptr()

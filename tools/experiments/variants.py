@@ -144,6 +144,17 @@ _B_XPAIR = (_B_GATHER, """            // EXPERIMENT bf16_xpair: corners c, c+1 a
             }
 """)
 
+# ----------------------------------------------------------------------------------------------------------------------
+# raster_bins_kernel: where is a hit aggregated with the other hits of its wave?  (profiles/r5/hit_bins.md)  The product
+# stages a wave's hits in LDS and takes one returning atomic per distinct tile among each 64 of them AFTER the wave's last
+# pixel.  hit_bins_ballot aggregates where the hit is found instead, among the lanes that found one in the same loop
+# iteration: no LDS, but the atomic's round trip is back in the per-candidate chain.  (Step 1 of that note measured both
+# forms as a kernel launched beside raster_kernel<4, false>, before the route existed.)
+_BINS_BALLOT = ("""            const int at = atomicAdd(&bins.stage->n, 1);
+            if (at < kBinStage) { bins.stage->tile[at] = tile; bins.stage->rec[at] = rec; }
+            else bin_records(bins, tile, rec);
+""", "            bin_records(bins, tile, rec);          // EXPERIMENT hit_bins_ballot\n")
+
 # (trav_unordered -- any hit child next instead of the nearest -- was measured here in round 4: frame 0.961 -> 0.917 ms,
 # 2^17 random rays 0.549 -> 0.528; it is in the product now: bvh8_traverse_kernel<kOrdered>, chosen per mesh)
 
@@ -152,6 +163,7 @@ _TRAV_ORDERED = ("    const bool ordered = bvh->depth_complexity >= 0.5f * (floa
                  "    const bool ordered = true;       // EXPERIMENT trav_ordered\n")
 
 VARIANTS = {
+    "hit_bins_ballot": ("raster.hip", [_BINS_BALLOT], []),
     "trav_ordered": ("bvh_traverse.hip", [_TRAV_ORDERED], []),
     "bf16_no_mlp": ("field_eval_bf16.hip", [_B_NO_MLP], []),
     "bf16_no_gather": ("field_eval_bf16.hip", [_B_NO_GATHER], []),
