@@ -914,6 +914,39 @@ int qf_texture_shade_points(const uint8_t *records, int32_t texture_size, int32_
                             const int64_t *index_tri, const int32_t *index_tri32, const float *dirs, int64_t n,
                             const int64_t *n_device, float *rgb, float *sigma, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Frame metrics: the tail of the reference's evaluation loops (train_finetune.py:620-667) without a host wait.
+ *
+ * qf_frame_score scores ONE frame into ONE slot of a device-resident table [capacity, 4] of fp64 records
+ * (mse, psnr, ssim, depth_max), enqueued on `stream`; the caller reads the table once, after the last frame.
+ *   rgb    fp32 [factor*height, factor*width, 3]: the render, ray-major as the renderers return it (rgb_height and
+ *          rgb_width state its size and must equal factor*height and factor*width); depth fp32 [factor*height,
+ *          factor*width] or NULL; pixels fp32 [height, width, 3]: the ground truth; factor 1..4; height, width >= 11.
+ *   Down-sample: the factor x factor block summed in fp32 in row-major order, times 1/factor^2 once (cv2.INTER_AREA for
+ *          an integer factor).  mse over the 3*height*width values of rgb_small - pixels; psnr = -10 log10(mse), inf
+ *          at 0.  ssim: torchmetrics' StructuralSimilarityIndexMeasure(data_range=1) with its defaults -- 11x11
+ *          Gaussian windows (sigma 1.5) that lie inside the image, per channel, c1 = 1e-4, c2 = 9e-4, the weights
+ *          and the window moments in fp64, the mean over the 3*(height-10)*(width-10) values as rounded to the fp32 map;
+ *          the UNCLAMPED down-sampled render goes in, as in the scripts.  depth_max: the maximum of depth_small
+ *          (0 without depth).
+ *   Optional outputs (NULL = skip): rgb_small fp32 [height, width, 3], depth_small fp32 [height, width],
+ *          ssim_map fp32 [height-10, width-10, 3].
+ *   scratch: qf_frame_score_scratch_bytes(height, width) bytes (-1: invalid size) of per-workgroup partial sums; a
+ *          second one-workgroup launch adds them in a fixed order (no floating-point atomics: the same inputs give the
+ *          same bits).  Frames on one stream may share it.
+ * qf_frame_images_u8 writes the three images of the scripts from rgb_small, pixels, depth_small and the slot's record
+ * (`record` = table + 4*slot) in one launch, each optional: rgb8 = uint8(clamp(rgb,0,1)*255),
+ * err8 = uint8(clamp(|clamp(rgb,0,1) - pixels|,0,1)*255), depth8 = uint8(depth / depth_max * 255), by truncation;
+ * depth_max is read on the device.  depth_max == 0 (a frame without a hit) gives a zero depth image, where the
+ * reference divides by zero.                                                                   */
+int64_t qf_frame_score_scratch_bytes(int32_t height, int32_t width);
+int qf_frame_score(const float *rgb, int32_t rgb_height, int32_t rgb_width, const float *depth, const float *pixels,
+                   int32_t height, int32_t width, int32_t factor, float *rgb_small, float *depth_small,
+                   float *ssim_map, double *table, int64_t slot, int64_t capacity, void *scratch,
+                   int64_t scratch_bytes, void *stream);
+int qf_frame_images_u8(const float *rgb_small, const float *pixels, const float *depth_small, const double *record,
+                       int32_t height, int32_t width, uint8_t *rgb8, uint8_t *err8, uint8_t *depth8, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,7 @@ SOURCES = [
     ("scan.hip", []),
     ("composite.hip", []),
     ("optim.hip", []),
+    ("frame_metrics.hip", []),
     ("bvh_traverse.hip", ["-ffp-contract=off"]),
     ("raster.hip", ["-ffp-contract=off"]),
     ("sample_pack.hip", ["-ffp-contract=off"]),

@@ -128,6 +128,16 @@ def seeded_ngp_state(log2_hashmap_size: int, n_rows: int, seed: int = 42, sg_lob
     return state
 
 
+def perturbed_ngp_state(state: dict, n_rows: int, amount: float = 0.05, seed: int = 1):
+    """``seeded_ngp_state``'s dict with uniform noise of ``amount`` added to the hash table only (the last 2 n_rows values
+    of ``mlp_base.params``): a field that renders almost the same frame, so that scoring one against the other gives a
+    PSNR and an SSIM that are neither perfect nor noise."""
+    g = torch.Generator().manual_seed(seed)
+    out = {k: v.clone() for k, v in state.items()}
+    out["mlp_base.params"][-2 * n_rows:] += (torch.rand(2 * n_rows, generator=g) * 2 - 1) * amount
+    return out
+
+
 def seeded_deform_state(n_params_grid: int, seed: int = 7, table_amp: float = 0.5):
     g = torch.Generator().manual_seed(seed)
 
