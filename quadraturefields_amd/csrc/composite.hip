@@ -1008,6 +1008,12 @@ extern "C" int qf_mesh_update_d(const float *d, const float *w, const int64_t *i
 //   gC = A g_rgb ; gA = g_alpha + sum_ch g_rgb (C - {1, 0, bg}) ; gw_i = gC.c_i + gA + gD t_i
 //   w_i = T_i (1 - exp(-tau_i)), dw_i/dtau_i = T_i exp(-tau_i), dw_k/dtau_i = -w_k for k > i
 //   => gtau_i = gw_i T_i exp(-tau_i) - sum_{k>i} gw_k w_k ; gsigma_i = gtau_i delta_i ; gc_i = w_i gC ; gt_i = w_i gD
+// T_i = exp(-cum_i) needs sample i's EXCLUSIVE optical depth in the backward sweep.  Peeling it off the total
+// (cum -= tau) gives (small + huge) - huge behind an opaque sample -- the absolute rounding error of huge in every
+// exponent in front of it, and inf - inf = NaN for sigma = +inf.  One lane owns a ray of any length, so the forward
+// sweep parks cum_i in grad_sigma[i] (this lane's own output, overwritten by the backward sweep) and the backward
+// sweep reads it back: 4 B written and 4 B read per sample on top of the 20 B read twice and 20 B written, and the
+// exponents are the forward kernels' bit for bit.  With that the gradient is finite for sigma = +inf (delta > 0).
 namespace {
 
 __global__ void derive_properties_backward_kernel(const float *rgb_s, const float *sigma, const float *depth_s,
@@ -1025,6 +1031,7 @@ __global__ void derive_properties_backward_kernel(const float *rgb_s, const floa
         for (; end < n && index_ray[end] == ray; ++end) {
             const float tau = sigma[end] * (deltas ? deltas[end] : delta_const);
             const float w = expf(-cum) * (1.0f - expf(-tau));
+            grad_sigma[end] = cum;                        // parked for the backward sweep
             cum += tau;
             cr += w * rgb_s[end * 3 + 0];
             cg += w * rgb_s[end * 3 + 1];
@@ -1042,13 +1049,12 @@ __global__ void derive_properties_backward_kernel(const float *rgb_s, const floa
         const float gA = ((g_alpha && in_image) ? g_alpha[ray] : 0.0f) +
                          (plain ? 0.0f : gr * (cr - b0) + gg * (cg - b1) + gb * (cb - b2));
         const float gCr = plain ? gr : ca * gr, gCg = plain ? gg : ca * gg, gCb = plain ? gb : ca * gb;
-        // backward sweep: cum holds the total optical depth; peel samples off the far end
+        // backward sweep from the far end
         float suffix = 0.0f;
         for (int64_t j = end - 1; j >= i; --j) {
             const float dl = deltas ? deltas[j] : delta_const;
             const float tau = sigma[j] * dl;
-            cum -= tau;                                   // exclusive optical depth of sample j (up to rounding)
-            const float T = expf(-cum), e = expf(-tau);
+            const float T = expf(-grad_sigma[j]), e = expf(-tau);      // the exclusive optical depth parked above
             const float w = T * (1.0f - e);
             const float gw = gCr * rgb_s[j * 3 + 0] + gCg * rgb_s[j * 3 + 1] + gCb * rgb_s[j * 3 + 2] + gA + gD * depth_s[j];
             grad_sigma[j] = (gw * T * e - suffix) * dl;

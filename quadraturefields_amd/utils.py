@@ -96,7 +96,11 @@ REPRODUCE_EVAL_RNG_ADVANCE = False
 class _DerivePropertiesFn(torch.autograd.Function):
     """Differentiable compositing: forward = qf_derive_properties, backward = qf_derive_properties_backward
     (gradients w.r.t. per-sample colour, density and depth; the returned weights are not differentiated, the
-    reference only uses them detached -- examples/field.py:246-252)."""
+    reference only uses them detached -- examples/field.py:246-252).
+
+    Domain: densities in [0, +inf] with ``delta > 0`` wherever the density is infinite (``inf * 0`` is NaN in the
+    forward already); ``delta = 0`` with a finite density is a sample of no weight.  The gradients are finite on all
+    of it: an opaque sample has gradient 0 w.r.t. its own density, everything behind it has weight and gradients 0."""
 
     @staticmethod
     def forward(ctx, color, density, depths, deltas_t, delta_c, index_ray, N, mode, bk, sample_index=None):
