@@ -618,6 +618,39 @@ int qf_vertex_clustering_emit(const double *vertices, int64_t n_vertices, const 
                               double *out_vertices, int64_t n_out_vertices, int64_t *out_faces, int64_t n_out_faces,
                               int64_t *n_fallback, void *stream);
 
+/* Per-triangle UV atlas of a mesh: every face gets its own staircase of texels on shelves of a texture_size^2 atlas.
+ * It stands where the reference runs the ScanNet segmentator and xatlas (examples/generate_uv_xatlas_old.py); the
+ * rules are this project's own.  vertices fp64 [V,3], faces int64 [F,3].  With
+ * l_f = sqrt(|(b - a) x (c - a)|), face f is class k = min(max_leg, floor(texels_per_unit * l_f)) and owns
+ * (k+1)(k+2)/2 texels.  All arithmetic is fp64 without FMA contraction; bit-identical run to run.
+ * Three calls on one workspace:
+ *   qf_uv_atlas_measure  validates and measures the mesh; counts[3] (device int64) = non-finite vertices, faces with
+ *                        an index outside [0, V), faces with l > 0.  If one of the first two is nonzero nothing else
+ *                        was computed: the other calls then write zeros to result (fits = 0) and class_counts and
+ *                        no mesh.
+ *   qf_uv_atlas_probe    lays the atlas out for one density; result[4] (device int64) = rows used, texels used, faces
+ *                        of class max_leg, fits (rows used <= texture_size - 1: the last row and column stay empty).
+ *   qf_uv_atlas_emit     probes again at texels_per_unit and, if that fits, writes the unshared mesh: out_vertices
+ *                        fp64 [3F,3] (vertex 3f+i is input vertex faces[f,i]), out_uv fp64 [3F,2] in [0,1) with
+ *                        uv[:,0] the row, face_class int32 [F], face_origin int32 [F,2] (top-left row and column of
+ *                        the face's block), face_half uint8 [F] (0: the block's lower staircase, 1: the upper one),
+ *                        class_counts int64 [max_leg+1] and result[4] as above.  If it does not fit, only
+ *                        class_counts and result are written.
+ * workspace: device scratch of at least qf_uv_atlas_workspace_bytes(F) bytes, about 41 F bytes plus the sort scratch
+ * (that function returns -1 for sizes the entries refuse); measure fills it, probe and emit need it as measure left it.
+ * QF_ERR_INVALID_ARGUMENT before any launch for: F < 1 or 3F >= 2^31, V outside [1, 2^31), max_leg outside [0, 63],
+ * texture_size outside [max_leg + 3, 16384], a texels_per_unit that is negative or not finite, a NULL pointer, a
+ * short workspace.                                                                                                  */
+int64_t qf_uv_atlas_workspace_bytes(int64_t n_faces);
+int qf_uv_atlas_measure(const double *vertices, int64_t n_vertices, const int64_t *faces, int64_t n_faces,
+                        void *workspace, int64_t workspace_bytes, int64_t *counts, void *stream);
+int qf_uv_atlas_probe(int64_t n_faces, double texels_per_unit, int32_t max_leg, int32_t texture_size, void *workspace,
+                      int64_t workspace_bytes, int64_t *result, void *stream);
+int qf_uv_atlas_emit(const double *vertices, int64_t n_vertices, const int64_t *faces, int64_t n_faces,
+                     double texels_per_unit, int32_t max_leg, int32_t texture_size, void *workspace,
+                     int64_t workspace_bytes, double *out_vertices, double *out_uv, int32_t *face_class,
+                     int32_t *face_origin, uint8_t *face_half, int64_t *class_counts, int64_t *result, void *stream);
+
 /* One frame's offsets in three small launches.  ray_offset [n_rays+1]: the offsets of the packed samples,
  * ray_offset[r] = sum_{q<r} min(hit_count[q], max_hits) for r = 0..n_rays, i.e. ray_offset[n_rays] is the total sample
  * count (left in device memory, so the caller can start qf_pack_samples before reading it back); replaces the index

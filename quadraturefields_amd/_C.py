@@ -146,6 +146,11 @@ _SIGNATURES = {
     "qf_vertex_clustering_count": (c_int, [_P, c_int64, _P, c_int64, c_double, _P, c_int64, _P, _P]),
     "qf_vertex_clustering_emit": (c_int, [_P, c_int64, _P, c_int64, c_double, c_int, _P, c_int64, _P, c_int64, _P, c_int64,
                                           _P, _P]),
+    "qf_uv_atlas_workspace_bytes": (c_int64, [c_int64]),
+    "qf_uv_atlas_measure": (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, _P, _P]),
+    "qf_uv_atlas_probe": (c_int, [c_int64, c_double, c_int32, c_int32, _P, c_int64, _P, _P]),
+    "qf_uv_atlas_emit": (c_int, [_P, c_int64, _P, c_int64, c_double, c_int32, c_int32, _P, c_int64, _P, _P, _P, _P, _P,
+                                 _P, _P, _P]),
     "qf_frame_offsets_temp_bytes": (c_int64, [c_int64]),
     "qf_frame_offsets": (c_int, [_P, c_int64, c_int32, c_int32, c_int32, _P, _P, _P, c_int64, _P, _P, _P, c_int32, _P]),
     "qf_banded_tile_count": (c_int64, [c_int32, c_int32, c_int32]),

@@ -18,8 +18,8 @@ ARCH = "gfx950"
 
 # (source, extra flags).  No FMA contraction in the index-exact stages (exact_common.h: bvh_traverse, raster, sample_pack,
 # texture and grid_march carry every integer-deciding comparison), texel_fill.hip (the fp64 rules of the texel-position
-# map), marching_cubes.hip (the fp32 vertex rule and the fp64 face decider) and vertex_clustering.hip (the fp64 cell, mean
-# and quadric rules).
+# map), marching_cubes.hip (the fp32 vertex rule and the fp64 face decider), vertex_clustering.hip (the fp64 cell, mean
+# and quadric rules) and uv_atlas.hip (the fp64 measure, class and corner rules).
 SOURCES = [
     ("field_eval.hip", []),
     ("field_eval_bf16.hip", []),
@@ -38,6 +38,7 @@ SOURCES = [
     ("texel_fill.hip", ["-ffp-contract=off"]),
     ("marching_cubes.hip", ["-ffp-contract=off"]),
     ("vertex_clustering.hip", ["-ffp-contract=off"]),
+    ("uv_atlas.hip", ["-ffp-contract=off"]),
     ("bvh_build.cpp", ["-x", "hip"]),
     ("misc.cpp", ["-x", "hip"]),
     ("frame.cpp", ["-x", "hip"]),

@@ -54,6 +54,22 @@ class TriMesh:
             rec["i"] = self.faces
             f.write(rec.tobytes())
 
+    def export_obj(self, path: str) -> None:
+        """Wavefront OBJ: ``v x y z``, with UVs ``vt u v`` per vertex and ``f a/a b/b c/c`` (else ``f a b c``).  Values
+        are written with 17 significant digits, so that ``load_mesh`` reads the same float64s back.  ``load_mesh``
+        numbers OBJ vertices by first use in the faces: the arrays come back identical for a mesh whose vertices already
+        are in that order, each used by some face (an unshared mesh with ``faces = arange``, as
+        ``uv_atlas.per_triangle_atlas`` returns); any other mesh with UVs comes back with the same triangles but its
+        vertices permuted, and without those no face uses."""
+        has_uv = self.visual.uv is not None
+        with open(path, "w") as f:
+            f.write("".join("v %.17g %.17g %.17g\n" % tuple(v) for v in self.vertices.tolist()))
+            if has_uv:
+                f.write("".join("vt %.17g %.17g\n" % tuple(t) for t in self.visual.uv.tolist()))
+                f.write("".join("f %d/%d %d/%d %d/%d\n" % (a, a, b, b, c, c) for a, b, c in (self.faces + 1).tolist()))
+            else:
+                f.write("".join("f %d %d %d\n" % tuple(t) for t in (self.faces + 1).tolist()))
+
 
 def _load_ply(path: str) -> TriMesh:
     with open(path, "rb") as f:
