@@ -779,6 +779,26 @@ int qf_composite_tiles(const float *rgb_c /* [n,3] */, const float *sigma_c /* [
                        const float *bkgd /* [3] or NULL */, float *out_rgb, float *out_alpha, float *out_depth,
                        float *weights_c, float *out_packed, void *stream);
 
+/* qf_composite_tiles that FOLDS its weights into the samples' triangles instead of storing them: stage 6a of the baking
+ * pipeline (prune_mesh_after_finetuning.py:323-373 -- scatter_max of a view's weights over index_tri, running maximum
+ * over the training views) inside the compositor's own walk.  tri_c [n] int32: the samples' triangle ids in the
+ * coherent order (qf_pack_tiles / qf_pack_tiles_bins write them); tri_weight [n_tri] float32, IN/OUT:
+ * tri_weight[t] = max(tri_weight[t], weight of every sample on t).  Its entries must be non-negative on entry (zeros
+ * before the first view); the maximum persists across calls and views and does not depend on the order of the calls.
+ * Equal, bit for bit, to qf_composite_tiles(weights_c) followed by qf_scatter_max over the valid ids.  Samples whose id is
+ * outside [0, n_tri) are skipped and counted in *bad_ids (device int32, or NULL; added to, as qf_mesh_update_d's
+ * counter); NaN weights are skipped.  counts (device int64[2], or NULL; added to): counts[0] += the frame's samples,
+ * counts[1] += those with weight > valid_threshold -- the two numbers the stage records per view.
+ * The image is optional: out_rgb, out_alpha, out_depth and out_packed all NULL = no image (bg_mode and bkgd are then not
+ * read); otherwise qf_composite_tiles' rules and its pixels, bit for bit.  No weight array is written.  n_tri < 2^31. */
+int qf_composite_tiles_trimax(const float *rgb_c /* [n,3] */, const float *sigma_c /* [n] */, const float *depth_c /* [n] */,
+                              float delta_const, const int32_t *hit_count /* [w*h] */, int32_t max_hits,
+                              const int64_t *tile_base, int32_t width, int32_t height, int32_t bg_mode,
+                              const float *bkgd /* [3] or NULL */, float *out_rgb, float *out_alpha, float *out_depth,
+                              float *out_packed, const int32_t *tri_c /* [n] */, float *tri_weight /* [n_tri], in/out */,
+                              int64_t n_tri, float valid_threshold, int64_t *counts /* device [2] or NULL */,
+                              int32_t *bad_ids /* device or NULL */, void *stream);
+
 /* out_rows[y] = sum over the pixels of row y of min(hit_count, max_hits): quadrature points per pixel row of a frame
  * (band).  No reference counterpart: the cost profile the band-sharded renderer balances its cuts with.   */
 int qf_row_sample_counts(const int32_t *hit_count, int32_t max_hits, int32_t width, int32_t height, float *out_rows,
@@ -839,6 +859,15 @@ typedef struct qf_frame_job {
     float *out_rgb, *out_alpha, *out_depth, *out_packed;
 } qf_frame_job;
 int qf_frame_render(qf_bvh *bvh, const qf_frame_job *job /* host */, void *stream);
+
+/* One training view of the pruning stage as ONE host call: qf_frame_render's launch sequence (hit-bin route and repair
+ * included) with the last launch replaced by qf_composite_tiles_trimax.  job->field and job->tri_c are required (the pack
+ * writes the ids); job->out_rgb / out_alpha / out_depth / out_packed may all be NULL (no image).  tri_weight, n_tri,
+ * valid_threshold, counts and bad_ids as qf_composite_tiles_trimax takes them.  The whole job is validated before the
+ * first launch.                                                                                                     */
+int qf_frame_prune(qf_bvh *bvh, const qf_frame_job *job /* host */, float *tri_weight /* [n_tri], in/out */, int64_t n_tri,
+                   float valid_threshold, int64_t *counts /* device [2] or NULL */, int32_t *bad_ids /* device or NULL */,
+                   void *stream);
 
 /* The "before" evaluation of a frame in the coherent order (train_finetune.py:696; utils.py:555-572 + the re-sort of
  * mesh_utils.py:389-403): every sample is displaced along its ray by tanh(f) * scaling -- f_c [n] = the deformation

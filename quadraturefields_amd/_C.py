@@ -73,6 +73,7 @@ _P = c_void_p
 _SIGNATURES = {
     "qf_status_string": (c_char_p, [c_int]),
     "qf_frame_render": (c_int, [_P, POINTER(FrameJob), _P]),
+    "qf_frame_prune": (c_int, [_P, POINTER(FrameJob), _P, c_int64, c_float, _P, _P, _P]),
     "qf_abi_version": (c_int, []),
     "qf_device_cu_count": (c_int, []),
     "qf_grid_desc_init": (c_int, [POINTER(GridDesc), c_uint32, c_uint32, c_uint32, c_double]),
@@ -102,6 +103,8 @@ _SIGNATURES = {
     "qf_derive_properties": (c_int, [_P, _P, _P, _P, c_float, _P, c_int64, c_int64, c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "qf_deform_resort_tiles": (c_int, [_P, c_float, _P, _P, _P, _P, c_int32, _P, c_int64, _P, c_int32, c_int32, _P, _P, _P]),
     "qf_composite_tiles": (c_int, [_P, _P, _P, c_float, _P, c_int32, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    "qf_composite_tiles_trimax": (c_int, [_P, _P, _P, c_float, _P, c_int32, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P,
+                                          c_int64, c_float, _P, _P, _P]),
     "qf_row_sample_counts": (c_int, [_P, c_int32, c_int32, c_int32, _P, _P]),
     "qf_derive_properties_backward": (c_int, [_P, _P, _P, _P, c_float, _P, c_int64, c_int64, c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "qf_pack_info": (c_int, [_P, c_int64, c_int64, _P, _P]),

@@ -112,7 +112,16 @@ def triangle_max_weights(weights: torch.Tensor, index_tri: torch.Tensor, out: to
 
 
 def prune_faces(mesh: TriMesh, triangle_weights, threshold: float = 1e-3) -> TriMesh:
-    """Mesh with the faces whose maximum weight is <= threshold removed (vertices kept, as ``update_faces``)."""
+    """Mesh with the faces whose maximum weight is <= threshold removed (vertices kept, as ``update_faces``).
+    ``triangle_weights`` may also be a boolean keep mask, and either may be a device tensor: the faces are then selected
+    on the device (the weights / mask make no round trip; only the kept faces come back for the ``TriMesh``)."""
+    if isinstance(triangle_weights, torch.Tensor) and triangle_weights.is_cuda:
+        t = triangle_weights.detach().reshape(-1)
+        keep = t if t.dtype == torch.bool else t > threshold
+        if keep.shape[0] != mesh.faces.shape[0]:
+            raise ValueError(f"{keep.shape[0]} weights for {mesh.faces.shape[0]} faces")
+        faces = torch.from_numpy(np.ascontiguousarray(mesh.faces)).to(t.device)[keep]
+        return TriMesh(mesh.vertices.copy(), faces.cpu().numpy(), mesh.visual.uv)
     tw = triangle_weights.detach().cpu().numpy() if isinstance(triangle_weights, torch.Tensor) else np.asarray(triangle_weights)
-    keep = tw.reshape(-1) > threshold
+    keep = tw.reshape(-1) if tw.dtype == np.bool_ else tw.reshape(-1) > threshold
     return TriMesh(mesh.vertices.copy(), mesh.faces[keep], mesh.visual.uv)

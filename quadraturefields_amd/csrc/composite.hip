@@ -529,6 +529,90 @@ __global__ __launch_bounds__(64) void composite_tiles_kernel(
     out_depth[ray] = acc.cd;
 }
 
+// composite_tiles_kernel's walk (one wave per 8x8 tile, rank-k step over ballots, loads of step k+1 before the arithmetic
+// of step k, composite_step / composite_blend unchanged) that FOLDS each sample's weight into its triangle instead of
+// storing it: tri_weight[tri_c[pos]] = max(.., wt) -- stage 6a of the baking pipeline (prune_mesh_after_finetuning.py:
+// scatter_max of a view's weights over index_tri, running maximum over the views), without a weight array, an int64 copy
+// of the ids or a third pass over both.
+// The maximum: weights are T * alpha >= 0 and tri_weight is non-negative on entry, so the IEEE bit pattern orders like
+// the value and ONE integer atomicMax on the bits is the float maximum (no compare-and-swap loop).
+// Read before the atomic: tri_weight[t] only ever grows, so a plain load of it -- however stale: an L1 / L2 line of this
+// XCD that another XCD's atomic has since passed -- is a LOWER bound of the current value.  A lane whose wt does not
+// exceed what it read cannot change the maximum and issues nothing; a lane whose wt does exceed it issues the atomic,
+// which compares against the current value at the memory side.  A stale read can therefore only cause a redundant
+// atomic, never a missed update, and the result is exactly the unfiltered one.  After the first views nearly every sample
+// loses the comparison: the steady state is one 4-byte gather and no atomic per sample.  The same comparison drops NaN
+// weights (NaN > x is false) and, tri_weight being >= 0, negative ones -- what qf_scatter_max leaves of them too.
+// The gather of step k is issued with the loads of step k+1 (its address, the id, arrived with step k's sample).
+// Ids outside [0, n_tri) are skipped and counted (as qf_mesh_update_d counts them).  counts[0] += samples,
+// counts[1] += samples with wt > valid_threshold: ballot popcounts per step, one 64-bit atomic each per wave.
+__global__ __launch_bounds__(64) void composite_tiles_trimax_kernel(
+    const float *__restrict__ rgb_c, const float *__restrict__ sigma_c, const float *__restrict__ depth_c,
+    float delta_const, const int32_t *__restrict__ hit_count, int max_hits, const int64_t *__restrict__ tile_base, int w,
+    int h, int tiles_x, int bg_mode, const float *__restrict__ bkgd, float *__restrict__ out_rgb, float *__restrict__ out_alpha,
+    float *__restrict__ out_depth, float *__restrict__ out_packed, const int32_t *__restrict__ tri_c, float *tri_weight,
+    int64_t n_tri, float valid_threshold, unsigned long long *counts, int32_t *bad_ids)
+{
+    const int tile = blockIdx.x, lane = threadIdx.x;
+    int64_t ray = 0;
+    int cnt = 0;
+    const int inside = tile_lane_ray(tile, lane, w, h, tiles_x, &ray);
+    if (inside) cnt = hit_count[ray] < max_hits ? hit_count[ray] : max_hits;
+    int64_t base = tile_base[tile];
+    const unsigned long long below = (1ull << lane) - 1ull;
+    RayAccum acc;
+    unsigned long long mask = __ballot(cnt > 0);
+    int64_t pos = base + __popcll(mask & below);
+    float sg = 0.0f, r = 0.0f, g = 0.0f, b = 0.0f, dep = 0.0f;
+    int tri = -1;
+    if (cnt > 0) { sg = sigma_c[pos]; r = rgb_c[pos * 3]; g = rgb_c[pos * 3 + 1]; b = rgb_c[pos * 3 + 2]; dep = depth_c[pos]; tri = tri_c[pos]; }
+    int n_samples = 0, n_valid = 0, n_bad = 0;        // wave-uniform
+    for (int k = 0; mask != 0ull; ++k) {              // wave-uniform
+        base += __popcll(mask);
+        const bool live = cnt > k;
+        const bool known = live && tri >= 0 && (int64_t)tri < n_tri;
+        float seen = 0.0f;
+        if (known) seen = tri_weight[tri];            // possibly stale: a lower bound (see above)
+        const unsigned long long next = __ballot(cnt > k + 1);
+        const int64_t npos = base + __popcll(next & below);
+        float nsg = 0.0f, nr = 0.0f, ng = 0.0f, nb = 0.0f, ndep = 0.0f;
+        int ntri = -1;
+        if (cnt > k + 1) { nsg = sigma_c[npos]; nr = rgb_c[npos * 3]; ng = rgb_c[npos * 3 + 1]; nb = rgb_c[npos * 3 + 2]; ndep = depth_c[npos]; ntri = tri_c[npos]; }
+        float wt = 0.0f;
+        if (live) {
+            const float tau = sample_tau(sg, delta_const);
+            wt = composite_step(acc, tau, sample_alpha(tau), r, g, b, dep);
+            if (known && wt > seen) atomicMax(reinterpret_cast<int *>(tri_weight + tri), __float_as_int(wt));
+        }
+        n_samples += __popcll(mask);
+        n_valid += __popcll(__ballot(live && wt > valid_threshold));
+        n_bad += __popcll(__ballot(live && !known));
+        mask = next; pos = npos; sg = nsg; r = nr; g = ng; b = nb; dep = ndep; tri = ntri;
+    }
+    if (lane == 0) {
+        if (counts && n_samples) atomicAdd(counts, (unsigned long long)n_samples);
+        if (counts && n_valid) atomicAdd(counts + 1, (unsigned long long)n_valid);
+        if (bad_ids && n_bad) atomicAdd(bad_ids, n_bad);
+    }
+    if (!inside || (!out_packed && !out_rgb)) return;
+    float px[3];
+    if (cnt > 0) {
+        composite_blend(acc, bg_mode, bkgd, px);
+    } else {                                           // fill_background_kernel's values
+        px[0] = px[1] = px[2] = (bg_mode == QF_BG_BLACK || bg_mode == QF_BG_NONE) ? 0.0f : 1.0f;
+    }
+    if (out_packed) {
+        float *o = out_packed + ray * 5;
+        o[0] = px[0]; o[1] = px[1]; o[2] = px[2]; o[3] = acc.ca; o[4] = acc.cd;
+        return;
+    }
+    out_rgb[ray * 3 + 0] = px[0];
+    out_rgb[ray * 3 + 1] = px[1];
+    out_rgb[ray * 3 + 2] = px[2];
+    out_alpha[ray] = acc.ca;
+    out_depth[ray] = acc.cd;
+}
+
 // quadrature points per pixel row, sum_x min(hit_count, K): what parallel.ShardedFrameRenderer balances its bands with
 // (one wave per row; replaces a clamp, a reshape and a row sum in torch)
 __global__ __launch_bounds__(64) void row_sample_counts_kernel(const int32_t *__restrict__ hit_count, int max_hits, int w, int h,
@@ -656,6 +740,29 @@ extern "C" int qf_composite_tiles(const float *rgb_c, const float *sigma_c, cons
     hipLaunchKernelGGL(composite_tiles_kernel, dim3(tiles_x * tiles_y), dim3(64), 0, qf_stream(stream), rgb_c, sigma_c,
                        depth_c, delta_const, hit_count, (int)max_hits, tile_base, (int)width, (int)height, tiles_x, (int)bg_mode, bkgd,
                        out_rgb, out_alpha, out_depth, weights_c, out_packed);
+    QF_LAUNCH_CHECK();
+    return QF_OK;
+}
+
+extern "C" int qf_composite_tiles_trimax(const float *rgb_c, const float *sigma_c, const float *depth_c, float delta_const,
+                                         const int32_t *hit_count, int32_t max_hits, const int64_t *tile_base,
+                                         int32_t width, int32_t height, int32_t bg_mode, const float *bkgd, float *out_rgb,
+                                         float *out_alpha, float *out_depth, float *out_packed, const int32_t *tri_c,
+                                         float *tri_weight, int64_t n_tri, float valid_threshold, int64_t *counts,
+                                         int32_t *bad_ids, void *stream)
+{
+    if (width < 1 || height < 1 || max_hits < 1 || n_tri < 0 || n_tri > 0x7fffffff) return QF_ERR_INVALID_ARGUMENT;
+    if (!rgb_c || !sigma_c || !depth_c || !hit_count || !tile_base || !tri_c || !tri_weight) return QF_ERR_INVALID_ARGUMENT;
+    if (out_packed || out_rgb || out_alpha || out_depth) {          // an image is wanted: qf_composite_tiles' rules
+        if (bg_mode < 0 || bg_mode > 3) return QF_ERR_INVALID_ARGUMENT;
+        if (!out_packed && (!out_rgb || !out_alpha || !out_depth)) return QF_ERR_INVALID_ARGUMENT;
+        if (bg_mode == QF_BG_CUSTOM && !bkgd) return QF_ERR_INVALID_ARGUMENT;
+    }
+    const int tiles_x = (width + 7) / 8, tiles_y = (height + 7) / 8;
+    hipLaunchKernelGGL(composite_tiles_trimax_kernel, dim3(tiles_x * tiles_y), dim3(64), 0, qf_stream(stream), rgb_c, sigma_c,
+                       depth_c, delta_const, hit_count, (int)max_hits, tile_base, (int)width, (int)height, tiles_x, (int)bg_mode,
+                       bkgd, out_rgb, out_alpha, out_depth, out_packed, tri_c, tri_weight, n_tri, valid_threshold,
+                       reinterpret_cast<unsigned long long *>(counts), bad_ids);
     QF_LAUNCH_CHECK();
     return QF_OK;
 }

@@ -2,10 +2,23 @@
 // (FrameRenderer.render_async: examples/utils.py:510-620 behind nerf_synthetic.py:310-373's camera rays), composed
 // from the library's own entry points -- nothing here launches a kernel of its own.  Two sequences: the per-ray lists
 // (qf_raster_intersect ... qf_pack_tiles) and, for the plain pass with a field, the hit bins (qf_raster_intersect_tiles
-// ... qf_pack_tiles_bins); same frame bit for bit.
+// ... qf_pack_tiles_bins); same frame bit for bit.  qf_frame_prune is the same sequence with the last launch replaced by
+// qf_composite_tiles_trimax (the tile compositor that folds its weights into the triangles).
 #include "qf_common.h"
 
-extern "C" int qf_frame_render(qf_bvh *bvh, const qf_frame_job *job, void *stream)
+namespace {
+
+// what qf_frame_prune adds to a job (its parameters; the job struct has no room for them)
+struct PruneTarget {
+    float *tri_weight;
+    int64_t n_tri;
+    float valid_threshold;
+    int64_t *counts;
+    int32_t *bad_ids;
+};
+
+// The frame's launch sequence; prune == nullptr: qf_frame_render.
+int frame_sequence(qf_bvh *bvh, const qf_frame_job *job, const PruneTarget *prune, void *stream)
 {
     if (!bvh || !job || !job->camera) return QF_ERR_INVALID_ARGUMENT;
     const qf_frame_job &j = *job;
@@ -15,6 +28,10 @@ extern "C" int qf_frame_render(qf_bvh *bvh, const qf_frame_job *job, void *strea
         !j.dropped || !j.xyz_c || !j.dirs_c || !j.depth_c)
         return QF_ERR_INVALID_ARGUMENT;
     if (j.field_precision < QF_FIELD_FP32 || j.field_precision > QF_FIELD_FP16) return QF_ERR_INVALID_ARGUMENT;
+    // pruning composites: a field, the samples' triangle ids and the per-triangle maxima are required; the image is not
+    const bool image = !prune || j.out_packed || j.out_rgb || j.out_alpha || j.out_depth;
+    if (prune && (!j.field || !j.tri_c || !prune->tri_weight || prune->n_tri < 0 || prune->n_tri > 0x7fffffff))
+        return QF_ERR_INVALID_ARGUMENT;
     // The whole job is checked BEFORE the first launch: the entry points below repeat these tests, but by the
     // time qf_field_forward or qf_composite_tiles would refuse, four kernels have run, the handle's cull parity has
     // flipped and the pinned block has been written -- a C caller would get INVALID_ARGUMENT for a half-executed frame.
@@ -41,9 +58,11 @@ extern "C" int qf_frame_render(qf_bvh *bvh, const qf_frame_job *job, void *strea
         for (int k = 0; k < 3; ++k)
             if (!(f.aabb[3 + k] > f.aabb[k])) return QF_ERR_INVALID_ARGUMENT;
         // ... and the compositor's (qf_composite_tiles): an image to write, a known background, its colour when custom
-        if (j.bg_mode < 0 || j.bg_mode > 3) return QF_ERR_INVALID_ARGUMENT;
-        if (!j.out_packed && (!j.out_rgb || !j.out_alpha || !j.out_depth)) return QF_ERR_INVALID_ARGUMENT;
-        if (j.bg_mode == QF_BG_CUSTOM && !j.bkgd) return QF_ERR_INVALID_ARGUMENT;
+        if (image) {
+            if (j.bg_mode < 0 || j.bg_mode > 3) return QF_ERR_INVALID_ARGUMENT;
+            if (!j.out_packed && (!j.out_rgb || !j.out_alpha || !j.out_depth)) return QF_ERR_INVALID_ARGUMENT;
+            if (j.bg_mode == QF_BG_CUSTOM && !j.bkgd) return QF_ERR_INVALID_ARGUMENT;
+        }
     }
     const int64_t cap = j.n_rays * (int64_t)j.max_hits;
     int32_t *overflow = j.hit_count + j.n_rays;
@@ -107,6 +126,25 @@ extern "C" int qf_frame_render(qf_bvh *bvh, const qf_frame_job *job, void *strea
                  j.dirs_c, cap, j.total, nullptr, j.rgb_c, j.sigma_c, nullptr, stream);
     }
     if (rc != QF_OK) return rc;
+    if (prune)
+        return qf_composite_tiles_trimax(j.rgb_c, j.sigma_c, j.depth_c, j.delta_const, j.final_count, j.max_hits, j.tile_base, w,
+                                         h, j.bg_mode, j.bkgd, j.out_rgb, j.out_alpha, j.out_depth, j.out_packed, j.tri_c,
+                                         prune->tri_weight, prune->n_tri, prune->valid_threshold, prune->counts,
+                                         prune->bad_ids, stream);
     return qf_composite_tiles(j.rgb_c, j.sigma_c, j.depth_c, j.delta_const, j.final_count, j.max_hits, j.tile_base, w, h,
                               j.bg_mode, j.bkgd, j.out_rgb, j.out_alpha, j.out_depth, nullptr, j.out_packed, stream);
+}
+
+}  // namespace
+
+extern "C" int qf_frame_render(qf_bvh *bvh, const qf_frame_job *job, void *stream)
+{
+    return frame_sequence(bvh, job, nullptr, stream);
+}
+
+extern "C" int qf_frame_prune(qf_bvh *bvh, const qf_frame_job *job, float *tri_weight, int64_t n_tri, float valid_threshold,
+                              int64_t *counts, int32_t *bad_ids, void *stream)
+{
+    const PruneTarget prune = {tri_weight, n_tri, valid_threshold, counts, bad_ids};
+    return frame_sequence(bvh, job, &prune, stream);
 }

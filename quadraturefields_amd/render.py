@@ -161,14 +161,30 @@ class FrameRenderer:
         arguments, same pixels.  An fp16 field passes its fp16 copies and ``field_precision`` = fp16 (the job's field
         step is then qf_field_forward_f16)."""
         ri = self.mesh_intersect.rayintersector
-        rf = self.radiance_field
         # launch on the intersector's device (its index is resolved at construction, _C.resolve_device; one switch at most)
         if not _switched and torch._C._cuda_getDevice() != ri.device.index:
             with torch.cuda.device(ri.device):
                 return self._render_async_one_call(origins, viewdirs, camera, k, render_bkgd, packed, _switched=True)
-        prepared = ri.fused_frame_job(origins, viewdirs, k, camera)
+        prepared = self._one_call_job(origins, viewdirs, camera, k, render_bkgd, packed)
         if prepared is None:                  # the intersector's policy moved while settling an earlier frame
             return self.render_async(origins, viewdirs, camera, 0.0, render_bkgd, packed)
+        job, frame, token, keep, (rgb, alpha, depth, out5) = prepared
+        _C.check(_C.lib().qf_frame_render(ri._handle, ctypes.byref(job), _C.stream()), "qf_frame_render")
+        ri.fused_frame_done(frame, token)
+        frame._keep = frame._keep + keep      # referenced until their readers ran
+        return (out5, None, None, frame) if packed else (rgb, alpha, depth, frame)
+
+    def _one_call_job(self, origins, viewdirs, camera, k, render_bkgd, packed, want_tri=False, image=True):
+        """The complete ``qf_frame_job`` of a camera frame on the intersector's (current) device: the sampling half
+        (``RayIntersector.fused_frame_job``), this renderer's field and -- with ``image`` -- the image buffers.  Returns
+        (job, frame, token, keep, (rgb, alpha, depth, packed image)) with nothing enqueued, ``keep`` = what must stay
+        referenced until the frame's kernels ran; None when the intersector's policy has just moved off the plain pass.
+        ``qf_frame_render`` and ``qf_frame_prune`` (``pruning.MeshPruner``) take the job."""
+        ri = self.mesh_intersect.rayintersector
+        rf = self.radiance_field
+        prepared = ri.fused_frame_job(origins, viewdirs, k, camera, want_tri=want_tri)
+        if prepared is None:
+            return None
         job, frame, token = prepared
         dev = ri.device
         n, cap = frame.width * frame.height, frame.total
@@ -194,7 +210,9 @@ class FrameRenderer:
         mode = utils._BG.get(self.bg_color, _C.BG_CUSTOM)
         bk = _C.f32c(render_bkgd.detach().reshape(3).to(dev)) if mode == _C.BG_CUSTOM else None
         rgb = alpha = depth = out5 = None
-        if packed:
+        if not image:
+            pass
+        elif packed:
             out5 = torch.empty((n, 5), dtype=torch.float32, device=dev)
             job.out_packed = out5.data_ptr()
         else:
@@ -209,10 +227,8 @@ class FrameRenderer:
         job.rgb_c, job.sigma_c = rgbs.data_ptr(), sigmas.data_ptr()
         job.delta_const, job.bg_mode = float(self.render_step_size), mode
         job.bkgd = bk.data_ptr() if bk is not None else None
-        _C.check(_C.lib().qf_frame_render(ri._handle, ctypes.byref(job), _C.stream()), "qf_frame_render")
-        ri.fused_frame_done(frame, token)
-        frame._keep = frame._keep + (rgbs, sigmas, table, base_w, head_w, sg_params, half, bk)   # referenced until their readers ran
-        return (out5, None, None, frame) if packed else (rgb, alpha, depth, frame)
+        # desc and sg are host structs the job points at: they live as long as the caller holds ``keep``
+        return job, frame, token, (rgbs, sigmas, table, base_w, head_w, sg_params, half, bk, desc, sg), (rgb, alpha, depth, out5)
 
     @torch.no_grad()
     def render_baked_async(self, origins, viewdirs, uv, compressor, camera):
