@@ -545,6 +545,51 @@ int qf_grid_march_write(const float *aabb, const int32_t *resolution, const uint
                         int64_t n_rays, float near_plane, float far_plane, float step, const int64_t *offsets,
                         float *t_starts, float *t_ends, int64_t *ray_indices, void *stream);
 
+/* Volumetric frames with early ray termination: the reference's test-time renderer render_image_with_occgrid_test
+ * (examples/utils.py:176-350), one grid level, cone_angle = 0; rules in DESIGN.md section 3.14.  The frame is rendered in
+ * rounds.  In a round every ray with alive[r] != 0 marches on from near[r] under the rule of qf_grid_march_count (t0 = its
+ * box entry clipped to near[r], samples [t0 + k*step, t0 + (k+1)*step], kept iff the midpoint lies before the exit and in
+ * an occupied cell) and stops after n_samples = clamp(n_rays / n_alive, 1, 64) kept samples.  n_alive is DEVICE state:
+ * `state` is QF_VOLUMETRIC_STATE_WORDS int64 words; state[parity] holds the number of alive rays entering the round (the
+ * caller writes n_rays there before round 1, parity 0, and flips parity every round), state[1 - parity] receives the
+ * survivors.  All arrays are device memory; aabb and resolution are HOST pointers.
+ *   _count  count[r] (0 for dead rays), term[r] = t_end of the ray's last kept sample if it filled n_samples, else its
+ *           clipped exit (alive rays only); zeroes state[1 - parity], writes state[QF_VOLUMETRIC_ROUND_QUOTA]
+ *   caller  csum = inclusive scan of count (int64)
+ *   _write  t_starts / t_ends / ray_indices and the rows the field reads, xyz = o + d * (t_start + t_end) / 2 and dirs,
+ *           at csum[r] - count[r]: grouped by ray, front to back.  Rows at or beyond `capacity` are not written
+ *           (n_alive * n_samples <= n_rays, so n_rays rows always suffice).  Writes state[QF_VOLUMETRIC_ROUND_SAMPLES].
+ *   caller  sigmas [.], rgbs [.,3] of the first state[QF_VOLUMETRIC_ROUND_SAMPLES] rows
+ *   qf_volumetric_accumulate  per alive ray, over its run: alpha = 1 - exp(-sigma (t_end - t_start)), T = (1 - opacity[r])
+ *           exp(-sum of the run's earlier sigma dt), w = T alpha; samples with alpha < alpha_thre (when alpha_thre > 0)
+ *           contribute nothing but still attenuate; rgb += w c, opacity += w, depth += w (t_start + t_end) / 2,
+ *           near[r] = term[r], alive[r] = opacity <= 1 - early_stop_eps and count[r] == n_samples.  Adds the survivors to
+ *           state[1 - parity] and the contributing samples to state[QF_VOLUMETRIC_TOTAL_SAMPLES].                      */
+#define QF_VOLUMETRIC_STATE_WORDS 8
+#define QF_VOLUMETRIC_TOTAL_SAMPLES 2 /* running, after the alpha filter; the caller zeroes it before round 1 */
+#define QF_VOLUMETRIC_ROUND_SAMPLES 3 /* samples marched in the round = the field's device-side count           */
+#define QF_VOLUMETRIC_ROUND_QUOTA 4   /* n_samples of the round                                                  */
+int qf_grid_march_round_count(const float *aabb, const int32_t *resolution, const uint8_t *binaries,
+                              const float *rays_o, const float *rays_d, const float *near, const uint8_t *alive,
+                              int64_t n_rays, float near_plane, float far_plane, float step, int64_t *state,
+                              int32_t parity, int32_t *count, float *term, void *stream);
+int qf_grid_march_round_write(const float *aabb, const int32_t *resolution, const uint8_t *binaries,
+                              const float *rays_o, const float *rays_d, const float *near, const uint8_t *alive,
+                              int64_t n_rays, float near_plane, float far_plane, float step, int64_t *state,
+                              int32_t parity, const int32_t *count, const int64_t *csum, int64_t capacity,
+                              float *t_starts, float *t_ends, int64_t *ray_indices, float *xyz, float *dirs,
+                              void *stream);
+int qf_volumetric_accumulate(const float *t_starts, const float *t_ends, const float *sigmas, const float *rgbs,
+                             const int32_t *count, const int64_t *csum, const float *term, int64_t n_rays,
+                             int64_t capacity, float alpha_thre, double early_stop_eps, int64_t *state, int32_t parity,
+                             float *rgb, float *opacity, float *depth, float *near, uint8_t *alive, void *stream);
+
+/* The body of the reference's transmittance-mask loop (examples/mc_utils.py:555-560): for n positions p01 [n,3] already
+ * normalised to [0,1]^3, mask[floor(p * (m - 1))] = mask[ceil(p * (m - 1))] = 1 in the byte grid mask [m,m,m] (x-major,
+ * fp32 product, per component), 1 <= m <= 1024.  A position with a component outside [0,1] (or NaN) writes nothing and
+ * adds one to *out_of_range (device int64, may be NULL; the caller zeroes it).                                       */
+int qf_mark_visited_cells(const float *p01, int64_t n, int32_t m, uint8_t *mask, int64_t *out_of_range, void *stream);
+
 /* Full-image rays of a pinhole camera, row-major [H*W,3] origins and unit viewdirs, with the arithmetic of
  * SubjectLoader.fetch_data (datasets/nerf_synthetic.py:341-373).  opengl != 0: -y / -z camera axes (the
  * reference's NeRF-synthetic loader).                                                                            */

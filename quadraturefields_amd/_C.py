@@ -24,6 +24,8 @@ HEAD_NONE, HEAD_NGP, HEAD_SG, HEAD_SG_FEATURES = 0, 1, 2, 3
 FIELD_FP32, FIELD_BF16, FIELD_FP16 = 0, 1, 2          # qf_frame_job.field_precision
 UNTOUCHED_LAST_FACE, UNTOUCHED_ZERO = 0, 1            # qf_texel_positions
 BG_WHITE, BG_BLACK, BG_CUSTOM, BG_NONE = 0, 1, 2, 3
+# the device state block of the volumetric rounds (qf_grid_march_round_count)
+VOLUMETRIC_STATE_WORDS, VOLUMETRIC_TOTAL_SAMPLES, VOLUMETRIC_ROUND_SAMPLES, VOLUMETRIC_ROUND_QUOTA = 8, 2, 3, 4
 
 
 class GridDesc(Structure):
@@ -138,6 +140,13 @@ _SIGNATURES = {
                                     c_float, _P, _P]),
     "qf_grid_march_write": (c_int, [POINTER(c_float), POINTER(c_int32), _P, _P, _P, _P, _P, c_int64, c_float, c_float,
                                     c_float, _P, _P, _P, _P, _P]),
+    "qf_grid_march_round_count": (c_int, [POINTER(c_float), POINTER(c_int32), _P, _P, _P, _P, _P, c_int64, c_float, c_float,
+                                          c_float, _P, c_int32, _P, _P, _P]),
+    "qf_grid_march_round_write": (c_int, [POINTER(c_float), POINTER(c_int32), _P, _P, _P, _P, _P, c_int64, c_float, c_float,
+                                          c_float, _P, c_int32, _P, _P, c_int64, _P, _P, _P, _P, _P, _P]),
+    "qf_volumetric_accumulate": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int64, c_int64, c_float, c_double, _P, c_int32, _P, _P,
+                                         _P, _P, _P, _P]),
+    "qf_mark_visited_cells": (c_int, [_P, c_int64, c_int32, _P, _P, _P]),
     "qf_generate_rays": (c_int, [POINTER(Camera), c_int32, _P, _P, _P]),
     "qf_scatter_max": (c_int, [_P, _P, c_int64, c_int64, _P, _P]),
     "qf_texel_positions_workspace_bytes": (c_int64, [c_int64, c_int32, c_int32]),

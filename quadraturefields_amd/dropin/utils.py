@@ -4,4 +4,4 @@ from quadraturefields_amd.utils import (MIPNERF360_UNBOUNDED_SCENES, NERF_SYNTHE
                                         derive_properties, generate_splits, inverse_of_compressed_sigma,
                                         render_image_bake_texture_images_with_occgrid, render_image_field_with_occgrid,
                                         render_image_finetune_with_occgrid, render_image_fit_sg_with_occgrid,
-                                        render_image_with_occgrid, set_random_seed)
+                                        render_image_with_occgrid, render_image_with_occgrid_test, set_random_seed)

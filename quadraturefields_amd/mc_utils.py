@@ -4,6 +4,7 @@ The reference smooths and normalises its saved grids on the GPU, copies the 1024
 scikit-image's marching cubes there, twice: over ``sin(omega * q)`` for the nested quadrature surfaces and over the NeRF
 density.  Here the marching cubes is the HIP kernel of ``csrc/marching_cubes.hip`` (``qf_marching_cubes_count`` /
 ``qf_marching_cubes_emit``, rules in DESIGN.md section 3.8); the steps around it stay torch ops on the device.
+``transmittance_mask`` is the device form of ``grid_transmittance_synthetic`` (examples/mc_utils.py:462-570).
 """
 import math
 
@@ -221,3 +222,53 @@ def downsample_mesh(mesh: TriMesh, vx=0, device="cuda") -> TriMesh:
     v, f = simplify_vertex_clustering(torch.from_numpy(np.asarray(mesh.vertices, np.float64)).to(dev),
                                       torch.from_numpy(np.asarray(mesh.faces, np.int64)).to(dev), 1 / vx, "quadric")
     return TriMesh(v.cpu().numpy(), f.cpu().numpy())
+
+
+def mark_visited_cells(positions01: torch.Tensor, mask: torch.Tensor, out_of_range: torch.Tensor = None) -> None:
+    """``mask[floor(p * (M - 1))] = mask[ceil(p * (M - 1))] = True`` for every row ``p`` of ``positions01`` (device fp32
+    [n,3], already normalised to [0,1]^3), in place in the device ``mask`` [M,M,M] (uint8 or bool): the loop body of the
+    reference's ``grid_transmittance_synthetic`` (mc_utils.py:555-560) as one launch, no index tensors.  A row with a
+    component outside [0,1] writes nothing and adds one to ``out_of_range`` (device int64 [1], optional)."""
+    if not isinstance(positions01, torch.Tensor) or not isinstance(mask, torch.Tensor):
+        raise TypeError("positions01 and mask must be torch.Tensors")
+    if not positions01.is_cuda or not mask.is_cuda:
+        raise ValueError("mark_visited_cells needs device tensors (quadraturefields_amd has no CPU fallback)")
+    if mask.ndim != 3 or not (mask.shape[0] == mask.shape[1] == mask.shape[2]) or not mask.is_contiguous():
+        raise ValueError(f"mask must be a contiguous cube [M,M,M], got shape {tuple(mask.shape)}")
+    if mask.dtype not in (torch.uint8, torch.bool):
+        raise TypeError(f"mask must be uint8 or bool, got {mask.dtype}")
+    if positions01.ndim != 2 or positions01.shape[1] != 3:
+        raise ValueError(f"positions01 must be [n,3], got shape {tuple(positions01.shape)}")
+    if out_of_range is not None and (out_of_range.dtype != torch.int64 or out_of_range.numel() != 1
+                                     or out_of_range.device != mask.device):
+        raise ValueError("out_of_range must be one int64 on the mask's device")
+    p = _C.f32c(positions01)
+    with torch.cuda.device(mask.device):
+        _C.check(_C.lib().qf_mark_visited_cells(_C.ptr(p), p.shape[0], mask.shape[0], _C.ptr(mask.view(torch.uint8)),
+                                                _C.ptr(out_of_range), _C.stream()), "qf_mark_visited_cells")
+
+
+@torch.no_grad()
+def transmittance_mask(radiance_field, estimator, views, *, max_samples=1024, chunk_size=256, size=1024, **render_kwargs):
+    """The reference's ``grid_transmittance_synthetic`` (mc_utils.py:462-570) on the device: the cells that light reaches.
+    Every view is rendered by ``utils.render_image_with_occgrid_test`` (early ray termination, ``max_samples`` per ray),
+    the cells of a ``chunk_size``^3 grid that hold a marched position -- ``radiance_field.normalize(positions)``, floor
+    and ceil -- are marked, and the grid is upsampled trilinearly (``align_corners=False``) to ``size``^3 and thresholded
+    at 0.5.  ``views``: an iterable of ``Rays`` or of loader items (dicts with ``"rays"`` and optionally ``"color_bkgd"``,
+    which is the view's background unless ``render_bkgd`` is given).  ``render_kwargs`` go to the renderer
+    (``render_step_size``, ``near_plane``, ``alpha_thre``, ``early_stop_eps``, ...).  Returns the bool mask [size]^3 on
+    the device; naming and saving it is the caller's business."""
+    from .utils import render_image_with_occgrid_test
+    device = estimator.binaries.device
+    mask = torch.zeros((int(chunk_size),) * 3, dtype=torch.uint8, device=device)
+    for view in views:
+        kwargs = dict(render_kwargs)
+        rays = view
+        if isinstance(view, dict):
+            rays = view["rays"]
+            if "color_bkgd" in view:
+                kwargs.setdefault("render_bkgd", view["color_bkgd"])
+        positions = render_image_with_occgrid_test(max_samples, radiance_field, estimator, rays, **kwargs)[4]
+        mark_visited_cells(radiance_field.normalize(positions)[1], mask)
+    up = F.interpolate(mask[None, None].to(torch.float32), size=(int(size),) * 3, mode="trilinear", align_corners=False)
+    return up[0, 0] > 0.5

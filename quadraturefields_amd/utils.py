@@ -3,7 +3,8 @@
 Mirrors the hot-path functions of ``examples/utils.py`` of the reference with the same names, arguments and
 return tuples: ``derive_properties`` (:863-898), ``render_image_finetune_with_occgrid`` (:465-607),
 ``render_image_fit_sg_with_occgrid`` (:610-730), ``render_image_bake_texture_images_with_occgrid`` (:998-1095),
-``render_image_with_occgrid`` (:65-172), ``render_image_field_with_occgrid`` (:353-462), ``compress_sigma`` /
+``render_image_with_occgrid`` (:65-172), ``render_image_with_occgrid_test`` (:176-350),
+``render_image_field_with_occgrid`` (:353-462), ``compress_sigma`` /
 ``inverse_of_compressed_sigma`` (:54-63), plus ``generate_splits`` (``examples/train_finetune.py:419-439``).
 Every tensor stays on the device; the reference's 160 000-sample Python batch loops, its
 ``torch.cuda.empty_cache()`` calls and its host round trips (np.lexsort, trimesh barycentrics) are gone,
@@ -547,6 +548,109 @@ def render_image_with_occgrid(
     extras["t_origins"] = origins
     return (rgb.view((*rays_shape[:-1], -1)), opacity.view((*rays_shape[:-1], -1)), depth.view((*rays_shape[:-1], -1)),
             int(t_starts.shape[0]), extras)
+
+
+@torch.no_grad()
+def render_image_with_occgrid_test(
+    max_samples: int, radiance_field: torch.nn.Module, estimator, rays: Rays, near_plane: float = 0.0,
+    far_plane: float = 1e10, render_step_size: float = 1e-3, render_bkgd: Optional[torch.Tensor] = None,
+    cone_angle: float = 0.0, alpha_thre: float = 0.0, early_stop_eps: float = 1e-4,
+    timestamps: Optional[torch.Tensor] = None, trace: Optional[list] = None,
+):
+    """The test-time volumetric renderer with early ray termination -- utils.py:176-350 of the reference (the NeRF frame
+    of the paper's speed comparison; ``mc_utils.grid_transmittance_synthetic`` builds its mask from the positions).
+    Returns (colors, opacities, depths, total_samples, positions): the first three in the image shape of ``rays``,
+    ``depths`` NOT divided by the opacity (the reference has that line commented out), ``total_samples`` the samples left
+    by the alpha filter, ``positions`` every marched sample, round by round, within a round by ray and depth.
+
+    The frame is rendered in rounds (DESIGN.md section 3.14): the alive rays march ``max(min(num_rays // n_alive, 64), 1)``
+    kept samples on from their near planes (``qf_grid_march_round_count`` / ``_write``), the field shades exactly those,
+    ``qf_volumetric_accumulate`` composites them and retires every ray whose opacity has passed ``1 - early_stop_eps`` or
+    that left the box.  Round buffers are ``num_rays`` rows, allocated once.  The host reads one pinned block per round
+    (the alive count the round started with and its sample count), where the reference calls ``.item()``; the sample
+    quota itself never leaves the device.  ``NGPRadianceField`` / ``NGPRadianceFieldSGNew`` take their fused kernels with
+    the round's sample count read from device memory; any other module is called as ``radiance_field(positions, dirs)``
+    on the round's rows.  ``trace`` (extension): a list that receives one dict per round -- ``n_alive``, ``n_samples``,
+    ``ray_indices``, ``t_starts``, ``t_ends``, and the ``alive`` mask and ``near`` planes after the round."""
+    from .radiance_fields.ngp import NGPRadianceField, NGPRadianceFieldSGNew
+    if timestamps is not None:
+        raise NotImplementedError("dynamic (D-NeRF) fields are out of scope")
+    if cone_angle != 0.0:
+        raise NotImplementedError("cone_angle > 0 (unbounded scenes) is out of scope")
+    if int(max_samples) <= 0:
+        raise ValueError(f"max_samples must be positive, got {max_samples}")
+    if not (rays.origins.is_cuda and rays.viewdirs.is_cuda and estimator.binaries.is_cuda):
+        raise ValueError("render_image_with_occgrid_test needs device tensors (quadraturefields_amd has no CPU fallback)")
+    rays, rays_shape, num_rays = _flatten_rays(rays)
+    device = rays.origins.device
+    origins, viewdirs = _C.f32c(rays.origins), _C.f32c(rays.viewdirs)
+    new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=device)
+    rgb = torch.zeros((num_rays, 3), device=device)
+    opacity = torch.zeros((num_rays, 1), device=device)
+    depth = torch.zeros((num_rays, 1), device=device)
+    positions_all = []
+    total_samples = 0
+    if num_rays:
+        near = torch.full((num_rays,), float(near_plane), dtype=torch.float32, device=device)
+        alive = torch.ones((num_rays,), dtype=torch.uint8, device=device)
+        state = torch.zeros((_C.VOLUMETRIC_STATE_WORDS,), dtype=torch.int64, device=device)
+        state[0] = num_rays
+        host = torch.empty((_C.VOLUMETRIC_STATE_WORDS,), dtype=torch.int64).pin_memory()
+        count, term = new((num_rays,), torch.int32), new((num_rays,), torch.float32)
+        csum = new((num_rays,), torch.int64)
+        t_starts, t_ends = new((num_rays,), torch.float32), new((num_rays,), torch.float32)
+        ray_indices = new((num_rays,), torch.int64)
+        xyz, dirs = new((num_rays, 3), torch.float32), new((num_rays, 3), torch.float32)
+        n_round = state[_C.VOLUMETRIC_ROUND_SAMPLES:_C.VOLUMETRIC_ROUND_SAMPLES + 1]
+        fused = isinstance(radiance_field, (NGPRadianceField, NGPRadianceFieldSGNew))
+        aabb, res = estimator._host_geometry()
+        binaries = estimator.binaries[0].contiguous()
+        lib = _C.lib()
+        march = (aabb, res, _C.ptr(binaries), _C.ptr(origins), _C.ptr(viewdirs), _C.ptr(near), _C.ptr(alive), num_rays,
+                 float(near_plane), float(far_plane), float(render_step_size), _C.ptr(state))
+        iter_samples, parity = 0, 0
+        while iter_samples < max_samples:
+            # the round is marched before the host knows whether a ray is still alive: with none the launches write nothing
+            _C.check(lib.qf_grid_march_round_count(*march, parity, _C.ptr(count), _C.ptr(term), _C.stream()),
+                     "qf_grid_march_round_count")
+            torch.cumsum(count, dim=0, out=csum)
+            _C.check(lib.qf_grid_march_round_write(*march, parity, _C.ptr(count), _C.ptr(csum), num_rays, _C.ptr(t_starts),
+                                                   _C.ptr(t_ends), _C.ptr(ray_indices), _C.ptr(xyz), _C.ptr(dirs),
+                                                   _C.stream()), "qf_grid_march_round_write")
+            host.copy_(state, non_blocking=True)
+            torch.cuda.current_stream(device).synchronize()          # the round's one read-back
+            n_alive, n_marched = int(host[parity]), int(host[_C.VOLUMETRIC_ROUND_SAMPLES])
+            if n_alive == 0:
+                break
+            n_samples = max(min(num_rays // n_alive, 64), 1)
+            iter_samples += n_samples
+            if fused:
+                rgbs, sigmas = radiance_field(xyz, dirs, n_device=n_round)
+            elif n_marched:
+                rgbs, sigmas = radiance_field(xyz[:n_marched], dirs[:n_marched])
+            else:
+                rgbs, sigmas = xyz, term                             # no sample to shade: nothing reads them
+            rgbs, sigmas = _C.f32c(rgbs.reshape(-1, 3)), _C.f32c(sigmas.reshape(-1))
+            if rgbs.shape[0] != sigmas.shape[0] or (n_marched and rgbs.shape[0] < n_marched):
+                raise ValueError(f"the field returned {rgbs.shape[0]} colours and {sigmas.shape[0]} densities for "
+                                 f"{n_marched} samples")
+            _C.check(lib.qf_volumetric_accumulate(
+                _C.ptr(t_starts), _C.ptr(t_ends), _C.ptr(sigmas), _C.ptr(rgbs), _C.ptr(count), _C.ptr(csum), _C.ptr(term),
+                num_rays, max(min(num_rays, rgbs.shape[0]), 1), float(alpha_thre), float(early_stop_eps), _C.ptr(state),
+                parity, _C.ptr(rgb), _C.ptr(opacity), _C.ptr(depth), _C.ptr(near), _C.ptr(alive), _C.stream()),
+                "qf_volumetric_accumulate")
+            positions_all.append(xyz[:n_marched].clone())
+            if trace is not None:
+                trace.append({"n_alive": n_alive, "n_samples": n_samples, "ray_indices": ray_indices[:n_marched].clone(),
+                              "t_starts": t_starts[:n_marched].clone(), "t_ends": t_ends[:n_marched].clone(),
+                              "alive": alive.bool(), "near": near.clone()})
+            parity ^= 1
+        total_samples = int(state[_C.VOLUMETRIC_TOTAL_SAMPLES].item())
+    if render_bkgd is not None:
+        rgb = rgb + render_bkgd.to(device) * (1.0 - opacity)
+    positions = torch.cat(positions_all, dim=0) if positions_all else torch.zeros((0, 3), device=device)
+    return (rgb.view((*rays_shape[:-1], -1)), opacity.view((*rays_shape[:-1], -1)), depth.view((*rays_shape[:-1], -1)),
+            total_samples, positions)
 
 
 def render_image_field_with_occgrid(
