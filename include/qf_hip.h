@@ -355,6 +355,24 @@ int qf_render_from_density(const float *t_starts, const float *t_ends, const flo
                            float *weights, float *trans, float *alphas, float *colors,
                            float *opacities, float *depths, void *stream);
 
+/* Distortion loss of packed samples and its gradient w.r.t. the weights, ONE launch, no host wait
+ * (torch_efficient_distloss: flatten_eff_distloss / eff_distloss; train_ngp_nerf_sg_occ.py:327-334).  Per ray, samples in
+ * stored order:  L_ray = sum_i sum_{j<i} 2 w_i w_j (m_i - m_j) + (1/3) sum_i w_i^2 d_i;  loss = sum_rays L_ray / n_rays.
+ * The sum is ORDERED: it is the Mip-NeRF-360 loss (|m_i - m_j|) exactly when m is nondecreasing along every ray.
+ *   interval : [n] lengths d, or NULL: every length is interval_const.
+ *   ray_id   : [n] nondecreasing, >= 0 -- or NULL with uniform_count > 0: n / uniform_count rays of that many samples
+ *              (the batched [..., N] form; n must be a multiple).  Exactly one of the two.
+ *   n_rays   : the divisor; 0: read on the device as ray_id[n-1] + 1 (n / uniform_count).  Rays without samples count.
+ *   loss_out : one float.  grad_w: [n] = dloss/dw, or NULL: the stores are skipped.
+ *   workspace: QF_DISTORTION_WORKSPACE_BYTES of device memory, ZERO before its first use; the launch leaves it ready
+ *              for the next one on the same stream (a ticket and one fp64 partial per workgroup).
+ * fp64 scans and sums, one rounding at each store; the loss is reduced in a fixed order (bit-reproducible, no
+ * floating-point atomics).  n == 0: loss 0.                                                      */
+#define QF_DISTORTION_WORKSPACE_BYTES 16400
+int qf_distortion_loss(const float *w, const float *m, const float *interval, float interval_const,
+                       const int64_t *ray_id, int64_t uniform_count, int64_t n, int64_t n_rays, float *loss_out,
+                       float *grad_w, void *workspace, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Ray / mesh quadrature points.
  * Replaces trimesh RayMeshIntersector (mesh_utils.py:223,350-354), the OptiX module

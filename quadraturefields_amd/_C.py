@@ -25,6 +25,7 @@ FIELD_FP32, FIELD_BF16, FIELD_FP16 = 0, 1, 2          # qf_frame_job.field_preci
 UNTOUCHED_LAST_FACE, UNTOUCHED_ZERO = 0, 1            # qf_texel_positions
 BG_WHITE, BG_BLACK, BG_CUSTOM, BG_NONE = 0, 1, 2, 3
 # the device state block of the volumetric rounds (qf_grid_march_round_count)
+DISTORTION_WORKSPACE_BYTES = 16400                    # QF_DISTORTION_WORKSPACE_BYTES
 VOLUMETRIC_STATE_WORDS, VOLUMETRIC_TOTAL_SAMPLES, VOLUMETRIC_ROUND_SAMPLES, VOLUMETRIC_ROUND_QUOTA = 8, 2, 3, 4
 
 
@@ -113,6 +114,7 @@ _SIGNATURES = {
     "qf_exclusive_scan": (c_int, [_P, _P, c_int64, c_int64, c_int32, _P, _P]),
     "qf_accumulate_along_rays": (c_int, [_P, _P, c_int32, _P, c_int64, c_int64, _P, _P]),
     "qf_render_from_density": (c_int, [_P, _P, _P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "qf_distortion_loss": (c_int, [_P, _P, _P, c_float, _P, c_int64, c_int64, c_int64, _P, _P, _P, _P]),
     "qf_bvh_create": (c_int, [_P, c_int64, POINTER(c_void_p)]),
     "qf_bvh_create_ex": (c_int, [_P, c_int64, c_int32, POINTER(c_void_p)]),
     "qf_bvh_refit": (c_int, [_P, _P, c_int64]),

@@ -28,6 +28,7 @@ SOURCES = [
     ("mlp_train.hip", []),
     ("scan.hip", []),
     ("composite.hip", []),
+    ("distortion.hip", []),
     ("optim.hip", []),
     ("frame_metrics.hip", []),
     ("bvh_traverse.hip", ["-ffp-contract=off"]),
