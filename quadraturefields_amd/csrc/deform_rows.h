@@ -1,5 +1,6 @@
-// Table row types of the deformation-field kernels (deform_kernel in field_eval.hip, grid_extract_kernel in
-// grid_extract.hip) and the fp16 rounding of a blended feature pair.
+// What the deformation-field kernels share (deform_kernel in field_eval.hip, grid_extract_kernel in grid_extract.hip,
+// deform_mlp_backward_kernel in mlp_train.hip): table row types, the fp16 rounding of a blended feature pair and the
+// LDS weight image of the decoder.
 #pragma once
 #include "field_common.h"
 
@@ -35,6 +36,36 @@ __device__ __forceinline__ void round_f16_pair(float *f0, float *f1)
     const f16x2 h = {(_Float16)*f0, (_Float16)*f1};
     *f0 = (float)h.x;
     *f1 = (float)h.y;
+}
+
+// LDS weight image (plain: A operand tiles, [tile][lane]) of the decoder cat[x01(3), grid(32)] -> H -> H -> 1 for hidden
+// width H: S = H/4 k-steps over a hidden layer, MT = H/16 row tiles.  Forward: layer 1 (9 MT), layer 2 (S MT), lout (S);
+// then grid_extract_kernel's backward of the scalar output: W2^T (S MT), W1[:, 0:3]^T (S).
+template <int H>
+struct DeformImage {
+    static constexpr int MT = H / 16, S = H / 4;
+    static constexpr int L1 = 0, L2 = 9 * MT, LO = L2 + S * MT, L2T = LO + S, L1X = L2T + S * MT, N = L1X + S;
+};
+
+// A operand of forward MFMA m < L2T for lane `lane`.  k-steps of layer 1: 0..7 grid features of the lane's level
+// quartet, step 8: lane quartets 0..2 feed x01.{x,y,z}, quartet 3 feeds the constant 1 that carries b1.
+template <int H>
+__device__ __forceinline__ float deform_fwd_weight(const float *w1, const float *b1, const float *w2, const float *wout,
+                                                   int m, int lane)
+{
+    typedef DeformImage<H> I;
+    const int i = lane & 15, kq = lane >> 4;
+    if (m < I::L2) {                       // cat[grid(32), x01 | 1] -> H: s outer (9), mt inner
+        const int s = m / I::MT, mt = m % I::MT, row = 16 * mt + i;
+        if (s < 8) return w1[row * 35 + 3 + 2 * (4 * (s >> 1) + kq) + (s & 1)];
+        return kq < 3 ? w1[row * 35 + kq] : b1[row];
+    }
+    if (m < I::LO) {                       // H -> H
+        const int q = m - I::L2, s = q / I::MT, mt = q % I::MT;
+        return w2[(16 * mt + i) * H + hidden_col(s, kq)];
+    }
+    const int s = m - I::LO;               // H -> 1 (row 0 of a 16-row tile)
+    return i == 0 ? wout[hidden_col(s, kq)] : 0.0f;
 }
 
 }  // namespace

@@ -1,7 +1,10 @@
-// Device helpers shared by the fp32 and bf16 field kernels: hash-grid level table, corner indexing, trilinear
-// blend weights, SH basis, sigmoid.  tiny-cuda-nn semantics per SURVEY.md Appendix A.1 / A.3.
+// Device helpers shared by the fp32 and 16-bit field kernels: hash-grid level table (and its copy in LDS), corner
+// indexing, trilinear blend weights, SH basis, sigmoid.  tiny-cuda-nn semantics per SURVEY.md Appendix A.1 / A.3.
 #pragma once
 #include "qf_common.h"
+#include "field_dealing.h"
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #define QF_PRIME_Y 2654435761u
 #define QF_PRIME_Z 805459861u
@@ -23,6 +26,33 @@ struct LevelConst {
     uint32_t offset, rows, res, hashed;
     float scale;
 };
+
+// The level table in LDS, 8 words per level (5 used), staged once per workgroup by threads 0..15: the kernels re-read
+// it every pass instead of pinning four LevelConst (20 VGPRs) per lane for the whole point loop.
+__device__ __forceinline__ void stage_level_table(uint32_t *lvl_lds, const GridArgs &grid, int tid)
+{
+    if (tid < QF_MAX_LEVELS) {
+        lvl_lds[tid * 8 + 0] = grid.offset[tid];
+        lvl_lds[tid * 8 + 1] = grid.rows[tid];
+        lvl_lds[tid * 8 + 2] = grid.res[tid];
+        lvl_lds[tid * 8 + 3] = (grid.hashed_mask >> tid) & 1u;
+        lvl_lds[tid * 8 + 4] = __float_as_uint(grid.scale[tid]);
+    }
+}
+
+// Level 4j + g of lane quartet g, read back from LDS; goff = 8g, made opaque by the caller so that the reads stay
+// inside the point loop.
+__device__ __forceinline__ LevelConst load_level(const uint32_t *lvl_lds, int j, int goff)
+{
+    const uint32_t *lv = lvl_lds + 32 * j + goff;
+    LevelConst lc;
+    lc.offset = lv[0];
+    lc.rows = lv[1];
+    lc.res = lv[2];
+    lc.hashed = lv[3];
+    lc.scale = __uint_as_float(lv[4]);
+    return lc;
+}
 
 // Table rows of the 8 corners of the cell containing (x,y,z) at one level, and the fractional position in it.
 __device__ __forceinline__ void level_indices(const LevelConst &lc, float x, float y, float z,

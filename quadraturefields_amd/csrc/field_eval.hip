@@ -17,18 +17,12 @@
 //     activations never leave registers between layers (no LDS, no shuffles).  The k order of each
 //     layer is permuted to match; the permutation is folded into the LDS weight image.
 //   * workgroup = 8 waves, persistent: grid = CUs, waves stride over the 16-point groups of their XCD's share.
-#include "field_common.h"
+#include "mlp_tiles.h"
 #include "deform_rows.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
 constexpr int kBlock = 512;          // 8 waves
-constexpr int kBaseMfma = 48;        // 32 (32->64) + 16 (64->16)
-constexpr int kNgpHeadMfma = 112;    // 32 + 64 + 16
-constexpr int kSgHeadMfmaFixed = 80; // 16 (16->64) + 64 (64->64); + 16 per output tile
 
 struct FieldArgs {
     GridArgs grid;
@@ -54,68 +48,17 @@ struct FieldArgs {
     int32_t nt_out;     // ceil(n_out / 16)
 };
 
-__device__ __forceinline__ f32x4 mfma(float a, float b, f32x4 c)
-{
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ int img_index(int m, int lane)
-{
-    return ((((m >> 2) << 6) + lane) << 2) + (m & 3);
-}
-
-// Weight value that lane `lane` must feed as A operand of MFMA number m (program order).
 template <int HEAD>
 __device__ float weight_for(const FieldArgs &a, int m, int lane)
 {
-    const int i = lane & 15, kq = lane >> 4;
-    if (m < 32) {                       // base 32 -> 64: s outer, mt inner
-        const int s = m >> 2, mt = m & 3;
-        const int col = 2 * (4 * (s >> 1) + kq) + (s & 1);
-        return a.base_w[(16 * mt + i) * 32 + col];
-    }
-    if (m < kBaseMfma) {                // base 64 -> 16
-        const int s = m - 32;
-        return a.base_w[2048 + i * 64 + hidden_col(s, kq)];
-    }
-    m -= kBaseMfma;
-    if (HEAD == QF_HEAD_NGP) {
-        if (m < 32) {                   // [SH16 | geo15 | 1] -> 64
-            const int s = m >> 2, mt = m & 3;
-            int col;
-            if (s < 4) col = 4 * kq + s;
-            else { const int o = 4 * kq + (s - 4); col = (o == 0) ? 31 : 15 + o; }
-            return a.head_w[(16 * mt + i) * 32 + col];
-        }
-        if (m < 96) {                   // 64 -> 64
-            const int q = m - 32, s = q >> 2, mt = q & 3;
-            return a.head_w[2048 + (16 * mt + i) * 64 + hidden_col(s, kq)];
-        }
-        const int s = m - 96;           // 64 -> 16 (3 used)
-        return a.head_w[2048 + 4096 + i * 64 + hidden_col(s, kq)];
-    }
-    if (HEAD == QF_HEAD_SG || HEAD == QF_HEAD_SG_FEATURES) {
-        if (m < 16) {                   // [geo15 | bias] -> 64 ; slot of the density carries b1
-            const int s = m >> 2, mt = m & 3, row = 16 * mt + i;
-            const int o = 4 * kq + s;
-            return (o == 0) ? a.sg.b1[row] : a.sg.w1[row * 15 + (o - 1)];
-        }
-        if (m < 80) {
-            const int q = m - 16, s = q >> 2, mt = q & 3;
-            return a.sg.w2[(16 * mt + i) * 64 + hidden_col(s, kq)];
-        }
-        const int q = m - 80, mt = q >> 4, s = q & 15;   // output tiles: mt outer, s inner
-        const int row = 16 * mt + i;
-        return (row < a.n_out) ? a.sg.wout[row * 64 + hidden_col(s, kq)] : 0.0f;
-    }
-    return 0.0f;
+    return field_image_weight<HEAD>(a.base_w, a.head_w, a.sg, a.n_out, m, lane);
 }
 
 template <int HEAD>
 __device__ __forceinline__ int n_mfma(const FieldArgs &a)
 {
     if (HEAD == QF_HEAD_NGP) return kBaseMfma + kNgpHeadMfma;
-    if (HEAD == QF_HEAD_SG || HEAD == QF_HEAD_SG_FEATURES) return kBaseMfma + kSgHeadMfmaFixed + 16 * a.nt_out;
+    if (HEAD == QF_HEAD_SG || HEAD == QF_HEAD_SG_FEATURES) return kBaseMfma + kSgHiddenMfma + 16 * a.nt_out;
     return kBaseMfma;
 }
 
@@ -140,40 +83,17 @@ __global__ __launch_bounds__(kBlock, 4) void field_kernel(const FieldArgs a)
         if (tid < 64) bias_lds[tid] = a.sg.b2[tid];
         else if (tid < 128) bias_lds[tid] = (tid - 64 < a.n_out) ? a.sg.bout[tid - 64] : 0.0f;
     }
-    // level table (8 words per level) behind the biases: re-read from LDS every pass instead of pinning 20 VGPRs
+    // level table behind the biases
     uint32_t *lvl_lds = reinterpret_cast<uint32_t *>(bias_lds + 128);
-    if (tid < QF_MAX_LEVELS) {
-        lvl_lds[tid * 8 + 0] = a.grid.offset[tid];
-        lvl_lds[tid * 8 + 1] = a.grid.rows[tid];
-        lvl_lds[tid * 8 + 2] = a.grid.res[tid];
-        lvl_lds[tid * 8 + 3] = (a.grid.hashed_mask >> tid) & 1u;
-        lvl_lds[tid * 8 + 4] = __float_as_uint(a.grid.scale[tid]);
-    }
+    stage_level_table(lvl_lds, a.grid, tid);
     __syncthreads();
     const f32x4 *img_base = reinterpret_cast<const f32x4 *>(lds);   // img_base[(m>>2)*64 + lane]
 
-    // Workgroups are dealt round-robin to the 8 XCDs, each with its own L2.  Give every XCD one CONTIGUOUS eighth
-    // of the (spatially coherent) processing order instead of every eighth chunk of it: an L2 then only sees the
-    // table rows of its own slab of the scene, which is what lets the mid-resolution levels stay resident.
-    // a render-only frame's sample count is data dependent and stays on the device (qf_tile_offsets' total): no host
-    // wait between the tile pack and this kernel; a.n is then the capacity of the arrays
-    int64_t n_pts = a.n;
-    if (a.n_dev) { const int64_t nd = *a.n_dev; n_pts = nd < a.n ? (nd > 0 ? nd : 0) : a.n; }
-    const int64_t n_groups = (n_pts + 15) >> 4;
-    int64_t grp_begin, grp_end, wave_stride;
-    if ((gridDim.x & 7) == 0) {
-        const int64_t per_xcd = (n_groups + 7) >> 3;
-        grp_begin = (int64_t)(blockIdx.x & 7) * per_xcd;
-        grp_end = grp_begin + per_xcd < n_groups ? grp_begin + per_xcd : n_groups;
-        grp_begin += (int64_t)(blockIdx.x >> 3) * (kBlock / 64) + (tid >> 6);
-        wave_stride = (int64_t)(gridDim.x >> 3) * (kBlock / 64);
-    } else {
-        grp_begin = (int64_t)blockIdx.x * (kBlock / 64) + (tid >> 6);
-        grp_end = n_groups;
-        wave_stride = (int64_t)gridDim.x * (kBlock / 64);
-    }
+    // which groups this wave takes: field_dealing.h.  With a.n_dev, a.n is the capacity of the arrays
+    const int64_t n_pts = a.n_dev ? qf_clamp_count(*a.n_dev, a.n) : a.n;
+    const QfGroupRange deal = qf_group_range((n_pts + 15) >> 4, gridDim.x, blockIdx.x, tid >> 6, kBlock / 64);
 
-    for (int64_t grp = grp_begin; grp < grp_end; grp += wave_stride) {
+    for (int64_t grp = deal.begin; grp < deal.end; grp += deal.stride) {
         const int64_t pt_raw = grp * 16 + p;
         const bool valid = pt_raw < n_pts;
         int64_t pt = valid ? pt_raw : n_pts - 1;
@@ -197,15 +117,8 @@ __global__ __launch_bounds__(kBlock, 4) void field_kernel(const FieldArgs a)
         float2 val[4][8];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const uint32_t *lv = lvl_lds + 32 * j + goff;     // level 4j + g
-            LevelConst lc;
-            lc.offset = lv[0];
-            lc.rows = lv[1];
-            lc.res = lv[2];
-            lc.hashed = lv[3];
-            lc.scale = __uint_as_float(lv[4]);
             uint32_t idx[8];
-            level_indices(lc, x01, y01, z01, idx, frac[j]);
+            level_indices(load_level(lvl_lds, j, goff), x01, y01, z01, idx, frac[j]);
 #pragma unroll
             for (int c = 0; c < 8; ++c) val[j][c] = a.table[idx[c]];
         }
@@ -219,29 +132,11 @@ __global__ __launch_bounds__(kBlock, 4) void field_kernel(const FieldArgs a)
         }
 
         // ---- base MLP 32 -> 64 (ReLU) -> 16
-        f32x4 h[4];
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) h[mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int s = 0; s < 8; ++s) {
-            const f32x4 w4 = img[s * 64];
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) h[mt] = mfma(w4[mt], feat[s], h[mt]);
-        }
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) h[mt][r] = fmaxf(h[mt][r], 0.0f);
-        f32x4 oa = (f32x4){0.f, 0.f, 0.f, 0.f}, ob = oa;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const f32x4 w4 = img[(8 + q) * 64];
-            oa = mfma(w4[0], h[q][0], oa);
-            ob = mfma(w4[1], h[q][1], ob);
-            oa = mfma(w4[2], h[q][2], oa);
-            ob = mfma(w4[3], h[q][3], ob);
-        }
-        const f32x4 base_out = oa + ob;    // lane (g,p): outputs 4g .. 4g+3 of point p
+        const f32x4 zero = (f32x4){0.f, 0.f, 0.f, 0.f};
+        f32x4 h[4] = {zero, zero, zero, zero};
+        dense_layer<8>(img, feat, h);
+        relu<4>(h);
+        const f32x4 base_out = row_tile_layer(img + 8 * 64, h, zero);    // lane (g,p): outputs 4g .. 4g+3 of point p
 
         // density = exp(raw - 1) * selector, ngp.py:772-775 (B-5, B-6)
         const float density = selector ? expf(base_out[0] - 1.0f) : 0.0f;
@@ -266,42 +161,12 @@ __global__ __launch_bounds__(kBlock, 4) void field_kernel(const FieldArgs a)
 #pragma unroll
             for (int r = 0; r < 4; ++r) in[4 + r] = base_out[r];
             if (g == 0) in[4] = 1.0f;      // the density slot carries the constant-1 pad input
-            f32x4 h1[4];
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) h1[mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int s = 0; s < 8; ++s) {
-                const f32x4 w4 = img[(12 + s) * 64];
-#pragma unroll
-                for (int mt = 0; mt < 4; ++mt) h1[mt] = mfma(w4[mt], in[s], h1[mt]);
-            }
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) h1[mt][r] = fmaxf(h1[mt][r], 0.0f);
-            f32x4 h2[4];
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) h2[mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int s = 0; s < 16; ++s) {
-                const f32x4 w4 = img[(20 + s) * 64];
-#pragma unroll
-                for (int mt = 0; mt < 4; ++mt) h2[mt] = mfma(w4[mt], h1[s >> 2][s & 3], h2[mt]);
-            }
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) h2[mt][r] = fmaxf(h2[mt][r], 0.0f);
-            f32x4 ca = (f32x4){0.f, 0.f, 0.f, 0.f}, cb = ca;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const f32x4 w4 = img[(36 + q) * 64];
-                ca = mfma(w4[0], h2[q][0], ca);
-                cb = mfma(w4[1], h2[q][1], cb);
-                ca = mfma(w4[2], h2[q][2], ca);
-                cb = mfma(w4[3], h2[q][3], cb);
-            }
-            const f32x4 c = ca + cb;
+            f32x4 h1[4] = {zero, zero, zero, zero}, h2[4] = {zero, zero, zero, zero};
+            dense_layer<8>(img + 12 * 64, in, h1);
+            relu<4>(h1);
+            dense_layer<16>(img + 20 * 64, h1, h2);
+            relu<4>(h2);
+            const f32x4 c = row_tile_layer(img + 36 * 64, h2, zero);
             if (g == 0 && valid) {
                 a.rgb[pt * 3 + 0] = sigmoidf(c[0]);
                 a.rgb[pt * 3 + 1] = sigmoidf(c[1]);
@@ -314,51 +179,22 @@ __global__ __launch_bounds__(kBlock, 4) void field_kernel(const FieldArgs a)
 #pragma unroll
             for (int r = 0; r < 4; ++r) in[r] = base_out[r];
             if (g == 0) in[0] = 1.0f;      // bias slot
-            f32x4 h1[4];
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) h1[mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                const f32x4 w4 = img[(12 + s) * 64];
-#pragma unroll
-                for (int mt = 0; mt < 4; ++mt) h1[mt] = mfma(w4[mt], in[s], h1[mt]);
-            }
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) h1[mt][r] = fmaxf(h1[mt][r], 0.0f);
+            f32x4 h1[4] = {zero, zero, zero, zero};
+            dense_layer<4>(img + 12 * 64, in, h1);
+            relu<4>(h1);
             f32x4 h2[4];
             const f32x4 *b2v = reinterpret_cast<const f32x4 *>(bias_lds);
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt) h2[mt] = b2v[4 * mt + g];
-#pragma unroll
-            for (int s = 0; s < 16; ++s) {
-                const f32x4 w4 = img[(16 + s) * 64];
-#pragma unroll
-                for (int mt = 0; mt < 4; ++mt) h2[mt] = mfma(w4[mt], h1[s >> 2][s & 3], h2[mt]);
-            }
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) h2[mt][r] = fmaxf(h2[mt][r], 0.0f);
+            dense_layer<16>(img + 16 * 64, h1, h2);
+            relu<4>(h2);
             // output tiles: lane (g,p) register r of tile mt = head output 16mt + 4g + r
             f32x4 out[4];
             const f32x4 *bov = reinterpret_cast<const f32x4 *>(bias_lds + 64);
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt) {
-                out[mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                if (mt < a.nt_out) {
-                    f32x4 ea = bov[4 * mt + g], eb = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const f32x4 w4 = img[(32 + 4 * mt + q) * 64];
-                        ea = mfma(w4[0], h2[q][0], ea);
-                        eb = mfma(w4[1], h2[q][1], eb);
-                        ea = mfma(w4[2], h2[q][2], ea);
-                        eb = mfma(w4[3], h2[q][3], eb);
-                    }
-                    out[mt] = ea + eb;
-                }
+                out[mt] = zero;
+                if (mt < a.nt_out) out[mt] = row_tile_layer(img + (32 + 4 * mt) * 64, h2, bov[4 * mt + g]);
             }
             if (HEAD == QF_HEAD_SG_FEATURES) {
                 if (valid) {
@@ -456,8 +292,7 @@ __global__ void sg_features_to_rgb_kernel(const float *features, int64_t stride,
 }
 
 // Deformation field (examples/field.py:186-203): cat[x01(3), grid(32)] -> 32 -> 32 -> 1, ReLU, biases.
-// Same wave mapping as field_kernel.  k-steps of layer 1: 0..7 grid features of the lane's level quartet,
-// step 8: lane quartets 0..2 feed x01.{x,y,z}, quartet 3 feeds the constant 1 that carries b1.
+// Same wave mapping as field_kernel; the weight image is deform_rows.h's.
 struct DeformArgs {
     GridArgs grid;
     const void *table;      // [rows] of the kernel's row type (DeformRowF32 / DeformRowF16)
@@ -471,23 +306,7 @@ struct DeformArgs {
     float *enc_out;     // optional [n,32], see FieldArgs
 };
 
-constexpr int kDeformMfma = 18 + 16 + 8;
-
-__device__ float deform_weight_for(const DeformArgs &a, int m, int lane)
-{
-    const int i = lane & 15, kq = lane >> 4;
-    if (m < 18) {                        // 36(pad) -> 32 : s outer (9), mt inner (2)
-        const int s = m >> 1, mt = m & 1, row = 16 * mt + i;
-        if (s < 8) return a.w1[row * 35 + 3 + 2 * (4 * (s >> 1) + kq) + (s & 1)];
-        return kq < 3 ? a.w1[row * 35 + kq] : a.b1[row];
-    }
-    if (m < 34) {                        // 32 -> 32 : s outer (8), mt inner (2); hidden col = 16*(s>>2) + 4kq + (s&3)
-        const int q = m - 18, s = q >> 1, mt = q & 1;
-        return a.w2[(16 * mt + i) * 32 + hidden_col(s, kq)];
-    }
-    const int s = m - 34;                // 32 -> 1 (row 0 of a 16-row tile)
-    return i == 0 ? a.wout[hidden_col(s, kq)] : 0.0f;
-}
+constexpr int kDeformMfma = DeformImage<32>::L2T;   // 18 + 16 + 8: the forward part of the image
 
 template <class R>
 __global__ __launch_bounds__(kBlock, 4) void deform_kernel(const DeformArgs a)
@@ -495,41 +314,20 @@ __global__ __launch_bounds__(kBlock, 4) void deform_kernel(const DeformArgs a)
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, p = lane & 15;
     // image: plain [m][lane] floats (ds_read_b32); + b2[32] + bout[1]
-    for (int e = tid; e < kDeformMfma * 64; e += kBlock) lds[e] = deform_weight_for(a, e >> 6, e & 63);
+    for (int e = tid; e < kDeformMfma * 64; e += kBlock) lds[e] = deform_fwd_weight<32>(a.w1, a.b1, a.w2, a.wout, e >> 6, e & 63);
     float *bias = lds + kDeformMfma * 64;
     if (tid < 32) bias[tid] = a.b2[tid];
     if (tid == 32) bias[32] = a.bout[0];
-    // the per-level constants live in LDS next to the weights, as in field_kernel (round 2 kept four LevelConst per lane
-    // in registers for the whole point loop: 128 VGPRs + 6 spilled, 28 B/lane of scratch)
+    // the level table lives in LDS next to the weights (stage_level_table; round 2 kept four LevelConst per lane in
+    // registers for the whole point loop: 128 VGPRs + 6 spilled, 28 B/lane of scratch)
     uint32_t *lvl_lds = reinterpret_cast<uint32_t *>(bias + 64);
-    if (tid < QF_MAX_LEVELS) {
-        lvl_lds[tid * 8 + 0] = a.grid.offset[tid];
-        lvl_lds[tid * 8 + 1] = a.grid.rows[tid];
-        lvl_lds[tid * 8 + 2] = a.grid.res[tid];
-        lvl_lds[tid * 8 + 3] = (a.grid.hashed_mask >> tid) & 1u;
-        lvl_lds[tid * 8 + 4] = __float_as_uint(a.grid.scale[tid]);
-    }
+    stage_level_table(lvl_lds, a.grid, tid);
     __syncthreads();
 
-    // one contiguous eighth of the processing order per XCD (see field_kernel)
-    // a render-only frame's sample count is data dependent and stays on the device (qf_tile_offsets' total): no host
-    // wait between the tile pack and this kernel; a.n is then the capacity of the arrays
-    int64_t n_pts = a.n;
-    if (a.n_dev) { const int64_t nd = *a.n_dev; n_pts = nd < a.n ? (nd > 0 ? nd : 0) : a.n; }
-    const int64_t n_groups = (n_pts + 15) >> 4;
-    int64_t grp_begin, grp_end, wave_stride;
-    if ((gridDim.x & 7) == 0) {
-        const int64_t per_xcd = (n_groups + 7) >> 3;
-        grp_begin = (int64_t)(blockIdx.x & 7) * per_xcd;
-        grp_end = grp_begin + per_xcd < n_groups ? grp_begin + per_xcd : n_groups;
-        grp_begin += (int64_t)(blockIdx.x >> 3) * (kBlock / 64) + (tid >> 6);
-        wave_stride = (int64_t)(gridDim.x >> 3) * (kBlock / 64);
-    } else {
-        grp_begin = (int64_t)blockIdx.x * (kBlock / 64) + (tid >> 6);
-        grp_end = n_groups;
-        wave_stride = (int64_t)gridDim.x * (kBlock / 64);
-    }
-    for (int64_t grp = grp_begin; grp < grp_end; grp += wave_stride) {
+    // which groups this wave takes: field_dealing.h
+    const int64_t n_pts = a.n_dev ? qf_clamp_count(*a.n_dev, a.n) : a.n;
+    const QfGroupRange deal = qf_group_range((n_pts + 15) >> 4, gridDim.x, blockIdx.x, tid >> 6, kBlock / 64);
+    for (int64_t grp = deal.begin; grp < deal.end; grp += deal.stride) {
         const int64_t pt_raw = grp * 16 + p;
         const bool valid = pt_raw < n_pts;
         int64_t pt = valid ? pt_raw : n_pts - 1;
@@ -547,15 +345,8 @@ __global__ __launch_bounds__(kBlock, 4) void deform_kernel(const DeformArgs a)
         asm volatile("" : "+v"(loff), "+v"(goff));
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const uint32_t *lv = lvl_lds + 32 * j + goff;     // level 4j + g
-            LevelConst lc;
-            lc.offset = lv[0];
-            lc.rows = lv[1];
-            lc.res = lv[2];
-            lc.hashed = lv[3];
-            lc.scale = __uint_as_float(lv[4]);
             uint32_t idx[8];
-            level_indices(lc, x01, y01, z01, idx, frac[j]);
+            level_indices(load_level(lvl_lds, j, goff), x01, y01, z01, idx, frac[j]);
 #pragma unroll
             for (int c = 0; c < 8; ++c) val[j][c] = R::unpack(static_cast<const typename R::row *>(a.table)[idx[c]]);
         }
@@ -571,30 +362,22 @@ __global__ __launch_bounds__(kBlock, 4) void deform_kernel(const DeformArgs a)
         }
         const float *wl = lds + loff;
         in[8] = g == 0 ? x01 : (g == 1 ? y01 : (g == 2 ? z01 : 1.0f));
+        typedef DeformImage<32> I;
         f32x4 h1[2] = {(f32x4){0.f, 0.f, 0.f, 0.f}, (f32x4){0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-        for (int s = 0; s < 9; ++s)
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt) h1[mt] = mfma(wl[(2 * s + mt) * 64], in[s], h1[mt]);
+        dense_layer<2, 9>(wl + I::L1 * 64, in, h1);
+        relu<2>(h1);
         f32x4 h2[2];
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) { h1[mt][r] = fmaxf(h1[mt][r], 0.0f); h2[mt][r] = bias[16 * mt + 4 * g + r]; }
-        }
-#pragma unroll
-        for (int s = 0; s < 8; ++s)
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt) h2[mt] = mfma(wl[(18 + 2 * s + mt) * 64], h1[s >> 2][s & 3], h2[mt]);
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) h2[mt][r] = fmaxf(h2[mt][r], 0.0f);
+            for (int r = 0; r < 4; ++r) h2[mt][r] = bias[16 * mt + 4 * g + r];
+        dense_layer<2, 8>(wl + I::L2 * 64, h1, h2);
+        relu<2>(h2);
         f32x4 oa = (f32x4){0.f, 0.f, 0.f, 0.f}, ob = oa;
 #pragma unroll
         for (int s = 0; s < 8; s += 2) {
-            oa = mfma(wl[(34 + s) * 64], h2[s >> 2][s & 3], oa);
-            ob = mfma(wl[(35 + s) * 64], h2[(s + 1) >> 2][(s + 1) & 3], ob);
+            oa = mfma(wl[(I::LO + s) * 64], h2[s >> 2][s & 3], oa);
+            ob = mfma(wl[(I::LO + s + 1) * 64], h2[(s + 1) >> 2][(s + 1) & 3], ob);
         }
         if (g == 0 && valid) a.out[pt] = (oa[0] + ob[0]) + bias[32];
     }
@@ -605,16 +388,9 @@ int launch_field(const FieldArgs &a, hipStream_t st)
 {
     int n_m = kBaseMfma;
     if (HEAD == QF_HEAD_NGP) n_m += kNgpHeadMfma;
-    if (HEAD == QF_HEAD_SG || HEAD == QF_HEAD_SG_FEATURES) n_m += kSgHeadMfmaFixed + 16 * a.nt_out;
+    if (HEAD == QF_HEAD_SG || HEAD == QF_HEAD_SG_FEATURES) n_m += kSgHiddenMfma + 16 * a.nt_out;
     const size_t lds_bytes = (size_t)(n_m * 64 + 128 + 8 * QF_MAX_LEVELS) * sizeof(float);
-    const int64_t n_groups = (a.n + 15) / 16;
-    int64_t blocks = qf_div_up(n_groups, kBlock / 64);
-    // ONE 8-wave workgroup per CU.  The kernel is bound by the fabric's sector-request rate, not by latency hiding:
-    // measured on the bench frame, 4 / 6 / 8 / 10 / 12 / 16 waves per CU -> 2.17 / 1.54 / 1.39 / 1.60 / 1.52 / 1.53 ms
-    // (fewer points in flight per XCD = a smaller L2 working set; below 8 waves the gathers no longer cover the latency).
-    const int64_t cap = (int64_t)qf_cu_count_cached();
-    if (blocks > cap) blocks = cap;
-    if (blocks >= 64) blocks &= ~(int64_t)7;          // a multiple of 8: the XCD-contiguous mapping of field_kernel
+    const int64_t blocks = qf_field_blocks((a.n + 15) / 16, kBlock / 64, qf_cu_count_cached());
     if (a.enc_out)
         hipLaunchKernelGGL((field_kernel<HEAD, true>), dim3((unsigned)blocks), dim3(kBlock), lds_bytes, st, a);
     else
@@ -736,10 +512,7 @@ int deform_forward(const qf_grid_desc *grid, const void *table, float scale, int
     a.out = out;
     a.enc_out = enc_out;
     const size_t lds_bytes = (size_t)(kDeformMfma * 64 + 64 + 8 * QF_MAX_LEVELS) * sizeof(float);
-    int64_t blocks = qf_div_up((n + 15) / 16, kBlock / 64);
-    const int64_t cap = (int64_t)qf_cu_count_cached();     // one workgroup per CU, see launch_field
-    if (blocks > cap) blocks = cap;
-    if (blocks >= 64) blocks &= ~(int64_t)7;
+    const int64_t blocks = qf_field_blocks((n + 15) / 16, kBlock / 64, qf_cu_count_cached());
     hipLaunchKernelGGL(deform_kernel<R>, dim3((unsigned)blocks), dim3(kBlock), lds_bytes, qf_stream(stream), a);
     QF_LAUNCH_CHECK();
     return QF_OK;

@@ -14,7 +14,6 @@
 // shape, lane maps and C/D layout.
 #include "field_common.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -162,33 +161,16 @@ __global__ __launch_bounds__(kBlockB, 4) void field_kernel_16(const FieldArgsB a
         else if (tid < 128) bias_lds[tid] = (tid - 64 < a.n_out) ? a.sg_bout[tid - 64] : 0.0f;
     }
     uint32_t *lvl_lds = reinterpret_cast<uint32_t *>(bias_lds + 128);
-    if (tid < QF_MAX_LEVELS) {
-        lvl_lds[tid * 8 + 0] = a.grid.offset[tid];
-        lvl_lds[tid * 8 + 1] = a.grid.rows[tid];
-        lvl_lds[tid * 8 + 2] = a.grid.res[tid];
-        lvl_lds[tid * 8 + 3] = (a.grid.hashed_mask >> tid) & 1u;
-        lvl_lds[tid * 8 + 4] = __float_as_uint(a.grid.scale[tid]);
-    }
+    stage_level_table(lvl_lds, a.grid, tid);
     __syncthreads();
     const uint4 *img_base = reinterpret_cast<const uint4 *>(ldsb);
 
-    // one contiguous eighth of the processing order per XCD (see field_kernel in field_eval.hip)
     int64_t n_pts = a.n;
-    if (a.n_dev) { const int64_t nd = *a.n_dev; n_pts = nd < a.n ? (nd > 0 ? nd : 0) : a.n; }
-    const int64_t n_groups = (n_pts + 15) >> 4;
-    int64_t grp_begin, grp_end, wave_stride;
-    if ((gridDim.x & 7) == 0) {
-        const int64_t per_xcd = (n_groups + 7) >> 3;
-        grp_begin = (int64_t)(blockIdx.x & 7) * per_xcd;
-        grp_end = grp_begin + per_xcd < n_groups ? grp_begin + per_xcd : n_groups;
-        grp_begin += (int64_t)(blockIdx.x >> 3) * (kBlockB / 64) + (tid >> 6);
-        wave_stride = (int64_t)(gridDim.x >> 3) * (kBlockB / 64);
-    } else {
-        grp_begin = (int64_t)blockIdx.x * (kBlockB / 64) + (tid >> 6);
-        grp_end = n_groups;
-        wave_stride = (int64_t)gridDim.x * (kBlockB / 64);
-    }
-    for (int64_t grp = grp_begin; grp < grp_end; grp += wave_stride) {
+    // which groups this wave takes: field_dealing.h.  (An `if`, not the conditional expression of field_kernel: with that
+    // one the <Bf16Elem, SG> instantiation takes 4 more VGPRs.)
+    if (a.n_dev) n_pts = qf_clamp_count(*a.n_dev, a.n);
+    const QfGroupRange deal = qf_group_range((n_pts + 15) >> 4, gridDim.x, blockIdx.x, tid >> 6, kBlockB / 64);
+    for (int64_t grp = deal.begin; grp < deal.end; grp += deal.stride) {
         const int64_t pt_raw = grp * 16 + p;
         const bool valid = pt_raw < n_pts;
         int64_t pt = valid ? pt_raw : n_pts - 1;
@@ -207,12 +189,8 @@ __global__ __launch_bounds__(kBlockB, 4) void field_kernel_16(const FieldArgsB a
         uint32_t raw[4][8];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const uint32_t *lv = lvl_lds + 32 * j + goff;
-            LevelConst lc;
-            lc.offset = lv[0]; lc.rows = lv[1]; lc.res = lv[2]; lc.hashed = lv[3];
-            lc.scale = __uint_as_float(lv[4]);
             uint32_t idx[8];
-            level_indices(lc, x01, y01, z01, idx, frac[j]);
+            level_indices(load_level(lvl_lds, j, goff), x01, y01, z01, idx, frac[j]);
 #pragma unroll
             for (int c = 0; c < 8; ++c) raw[j][c] = a.table[idx[c]];
         }
@@ -353,10 +331,7 @@ int launch_field_b(const FieldArgsB &a, hipStream_t st)
     if (HEAD == QF_HEAD_NGP) n_m = 20;
     if (HEAD == QF_HEAD_SG) n_m = 18 + 2 * a.nt_out;
     const size_t lds_bytes = (size_t)n_m * 1024 + (128 + 8 * QF_MAX_LEVELS) * sizeof(float);
-    int64_t blocks = qf_div_up((a.n + 15) / 16, kBlockB / 64);
-    const int64_t cap = (int64_t)qf_cu_count_cached();   // one workgroup per CU, see launch_field in field_eval.hip
-    if (blocks > cap) blocks = cap;
-    if (blocks >= 64) blocks &= ~(int64_t)7;
+    const int64_t blocks = qf_field_blocks((a.n + 15) / 16, kBlockB / 64, qf_cu_count_cached());
     hipLaunchKernelGGL((field_kernel_16<E, HEAD>), dim3((unsigned)blocks), dim3(kBlockB), lds_bytes, st, a);
     QF_LAUNCH_CHECK();
     return QF_OK;

@@ -17,13 +17,12 @@
 // the waves of an XCD sweep x at fixed (y, z), the table's contiguous axis.  Pool 2: the brick holds two voxels
 // (lanes with the same p>>1 & 1); lane e of a voxel's 8 is fetched with a cross-lane read and summed in torch's CPU
 // AvgPool3d order (dx outer, dz inner, from 0, then / 8).
+#include "mlp_tiles.h"
 #include "deform_rows.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
-constexpr int kBlock = 512;   // 8 waves, one workgroup per CU (see launch_field in field_eval.hip)
+constexpr int kBlock = 512;   // 8 waves, one workgroup per CU (qf_field_blocks)
 constexpr int kTileZ = 16;    // z bricks per tile of the lattice walk
 
 enum GxSource { GX_LIST = 0, GX_LATTICE_1 = 1, GX_LATTICE_2 = 2 };
@@ -48,37 +47,13 @@ struct GridExtractArgs {
     uint16_t *grad;     // fp16 bits, or NULL
 };
 
-__device__ __forceinline__ f32x4 mfma(float a, float b, f32x4 c)
-{
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
-// LDS weight image (A operand tiles, [tile][lane]) for hidden width H: S = H/4 k-steps over a hidden layer, MT = H/16
-// row tiles.  layer 1 (9 MT), layer 2 (S MT), lout (S), W2^T (S MT), W1[:, 0:3]^T (S).
-template <int H>
-struct Image {
-    static constexpr int MT = H / 16, S = H / 4;
-    static constexpr int L1 = 0, L2 = 9 * MT, LO = L2 + S * MT, L2T = LO + S, L1X = L2T + S * MT, N = L1X + S;
-};
-
+// A operand of MFMA m of DeformImage<H>: the forward part, then the backward of the scalar output
 template <int H>
 __device__ float weight_for(const GridExtractArgs &a, int m, int lane)
 {
-    typedef Image<H> I;
+    typedef DeformImage<H> I;
+    if (m < I::L2T) return deform_fwd_weight<H>(a.w1, a.b1, a.w2, a.wout, m, lane);
     const int i = lane & 15, kq = lane >> 4;
-    if (m < I::L2) {                       // cat[grid(32), x01 | 1] -> H: s outer (9), mt inner
-        const int s = m / I::MT, mt = m % I::MT, row = 16 * mt + i;
-        if (s < 8) return a.w1[row * 35 + 3 + 2 * (4 * (s >> 1) + kq) + (s & 1)];
-        return kq < 3 ? a.w1[row * 35 + kq] : a.b1[row];
-    }
-    if (m < I::LO) {                       // H -> H
-        const int q = m - I::L2, s = q / I::MT, mt = q % I::MT;
-        return a.w2[(16 * mt + i) * H + hidden_col(s, kq)];
-    }
-    if (m < I::L2T) {                      // H -> 1 (row 0 of a 16-row tile)
-        const int s = m - I::LO;
-        return i == 0 ? a.wout[hidden_col(s, kq)] : 0.0f;
-    }
     if (m < I::L1X) {                      // backward of layer 2: W2^T
         const int q = m - I::L2T, s = q / I::MT, mt = q % I::MT;
         return a.w2[hidden_col(s, kq) * H + 16 * mt + i];
@@ -104,7 +79,7 @@ __device__ __forceinline__ float act_fwd(float z, float *d)
 template <class R, int ACT, int H, int SRC>
 __global__ __launch_bounds__(kBlock) void grid_extract_kernel(const GridExtractArgs a)
 {
-    typedef Image<H> I;
+    typedef DeformImage<H> I;
     constexpr int MT = I::MT, S = I::S;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, p = lane & 15;
@@ -113,39 +88,21 @@ __global__ __launch_bounds__(kBlock) void grid_extract_kernel(const GridExtractA
     if (tid < H) { bias[tid] = a.b2[tid]; bias[64 + tid] = a.wout[tid]; }
     if (tid == 32) bias[32] = a.bout[0];
     uint32_t *lvl_lds = reinterpret_cast<uint32_t *>(bias + 128);
-    if (tid < QF_MAX_LEVELS) {
-        lvl_lds[tid * 8 + 0] = a.grid.offset[tid];
-        lvl_lds[tid * 8 + 1] = a.grid.rows[tid];
-        lvl_lds[tid * 8 + 2] = a.grid.res[tid];
-        lvl_lds[tid * 8 + 3] = (a.grid.hashed_mask >> tid) & 1u;
-        lvl_lds[tid * 8 + 4] = __float_as_uint(a.grid.scale[tid]);
-    }
+    stage_level_table(lvl_lds, a.grid, tid);
     __syncthreads();
 
     int64_t n_groups;
     int64_t n_pts = 0;
     if (SRC == GX_LIST) {
-        n_pts = a.n_points;
-        if (a.n_dev) { const int64_t nd = *a.n_dev; n_pts = nd < a.n_points ? (nd > 0 ? nd : 0) : a.n_points; }
+        n_pts = a.n_dev ? qf_clamp_count(*a.n_dev, a.n_points) : a.n_points;
         n_groups = (n_pts + 15) >> 4;
     } else {
         n_groups = a.n_groups;
     }
-    // one contiguous eighth of the groups per XCD (deform_kernel)
-    int64_t grp_begin, grp_end, wave_stride;
-    if ((gridDim.x & 7) == 0) {
-        const int64_t per_xcd = (n_groups + 7) >> 3;
-        grp_begin = (int64_t)(blockIdx.x & 7) * per_xcd;
-        grp_end = grp_begin + per_xcd < n_groups ? grp_begin + per_xcd : n_groups;
-        grp_begin += (int64_t)(blockIdx.x >> 3) * (kBlock / 64) + (tid >> 6);
-        wave_stride = (int64_t)(gridDim.x >> 3) * (kBlock / 64);
-    } else {
-        grp_begin = (int64_t)blockIdx.x * (kBlock / 64) + (tid >> 6);
-        grp_end = n_groups;
-        wave_stride = (int64_t)gridDim.x * (kBlock / 64);
-    }
+    // which groups this wave takes: field_dealing.h
+    const QfGroupRange deal = qf_group_range(n_groups, gridDim.x, blockIdx.x, tid >> 6, kBlock / 64);
     const float two_s = a.scale + a.scale;
-    for (int64_t grp = grp_begin; grp < grp_end; grp += wave_stride) {
+    for (int64_t grp = deal.begin; grp < deal.end; grp += deal.stride) {
         bool valid;
         int64_t out_idx;
         float x, y, z;
@@ -184,15 +141,8 @@ __global__ __launch_bounds__(kBlock) void grid_extract_kernel(const GridExtractA
         asm volatile("" : "+v"(loff), "+v"(goff));
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const uint32_t *lv = lvl_lds + 32 * j + goff;     // level 4j + g
-            LevelConst lc;
-            lc.offset = lv[0];
-            lc.rows = lv[1];
-            lc.res = lv[2];
-            lc.hashed = lv[3];
-            lc.scale = __uint_as_float(lv[4]);
             uint32_t idx[8];
-            level_indices(lc, x01, y01, z01, idx, frac[j]);
+            level_indices(load_level(lvl_lds, j, goff), x01, y01, z01, idx, frac[j]);
 #pragma unroll
             for (int c = 0; c < 8; ++c) val[j][c] = R::unpack(static_cast<const typename R::row *>(a.table)[idx[c]]);
         }
@@ -207,10 +157,7 @@ __global__ __launch_bounds__(kBlock) void grid_extract_kernel(const GridExtractA
         f32x4 h1[MT], d1[MT];
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) h1[mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int s = 0; s < 9; ++s)
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) h1[mt] = mfma(wl[(I::L1 + MT * s + mt) * 64], in[s], h1[mt]);
+        dense_layer<MT, 9>(wl + I::L1 * 64, in, h1);
         f32x4 h2[MT], d2[MT];
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
@@ -222,10 +169,7 @@ __global__ __launch_bounds__(kBlock) void grid_extract_kernel(const GridExtractA
                 h2[mt][r] = bias[16 * mt + 4 * g + r];
             }
         }
-#pragma unroll
-        for (int s = 0; s < S; ++s)
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) h2[mt] = mfma(wl[(I::L2 + MT * s + mt) * 64], h1[s >> 2][s & 3], h2[mt]);
+        dense_layer<MT, S>(wl + I::L2 * 64, h1, h2);
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
@@ -234,6 +178,8 @@ __global__ __launch_bounds__(kBlock) void grid_extract_kernel(const GridExtractA
                 h2[mt][r] = act_fwd<ACT>(h2[mt][r], &d);
                 d2[mt][r] = d;
             }
+        // (the two split-accumulator row tiles of this kernel stay written out: as a shared template the ELU list
+        // instantiations allocate their scalar registers differently)
         f32x4 oa = (f32x4){0.f, 0.f, 0.f, 0.f}, ob = oa;
 #pragma unroll
         for (int s = 0; s < S; s += 2) {
@@ -251,11 +197,7 @@ __global__ __launch_bounds__(kBlock) void grid_extract_kernel(const GridExtractA
             f32x4 da1[MT];
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) da1[mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int s = 0; s < S; ++s)
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt)
-                    da1[mt] = mfma(wl[(I::L2T + MT * s + mt) * 64], d2[s >> 2][s & 3], da1[mt]);
+            dense_layer<MT, S>(wl + I::L2T * 64, d2, da1);
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
@@ -296,11 +238,8 @@ __global__ __launch_bounds__(kBlock) void grid_extract_kernel(const GridExtractA
 template <class R, int ACT, int H>
 int launch_extract(const GridExtractArgs &a, int src, int64_t n_groups, hipStream_t st)
 {
-    const size_t lds_bytes = (size_t)(Image<H>::N * 64 + 128 + 8 * QF_MAX_LEVELS) * sizeof(float);
-    int64_t blocks = qf_div_up(n_groups, kBlock / 64);
-    const int64_t cap = (int64_t)qf_cu_count_cached();     // one workgroup per CU, see launch_field
-    if (blocks > cap) blocks = cap;
-    if (blocks >= 64) blocks &= ~(int64_t)7;
+    const size_t lds_bytes = (size_t)(DeformImage<H>::N * 64 + 128 + 8 * QF_MAX_LEVELS) * sizeof(float);
+    const int64_t blocks = qf_field_blocks(n_groups, kBlock / 64, qf_cu_count_cached());
     if (src == GX_LIST)
         hipLaunchKernelGGL((grid_extract_kernel<R, ACT, H, GX_LIST>), dim3((unsigned)blocks), dim3(kBlock), lds_bytes, st, a);
     else if (src == GX_LATTICE_1)

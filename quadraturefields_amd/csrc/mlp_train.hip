@@ -14,11 +14,10 @@
 //     transpose, and the 40 16x16 tiles of dW (10 240 parameters) stay in 160 accumulator registers per lane for the
 //     whole launch; at the end every wave adds its tiles to the fp32 gradient vectors with atomics.
 // v_mfma_f32_16x16x4_f32 throughout (exact fp32 products, fp32 accumulate).
-#include "field_common.h"
+#include "mlp_tiles.h"
+#include "deform_rows.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kTrainBlock = 256;     // 4 waves: one per SIMD, so that a lane may use up to 512 registers
 constexpr int kFwdMfma = 160;        // 48 base + 112 head, program order of field_kernel<NGP>
@@ -33,37 +32,14 @@ struct TrainArgs {
     float *d_enc, *g_base, *g_head;
 };
 
-__device__ __forceinline__ f32x4 mfma(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
 // Derivative of the density activation trunc_exp: the forward is exp(x), unclamped, but the
 // gradient is exp(min(x, 15)), so it stays finite where the forward overflows.  A NaN stays NaN, as torch.clamp keeps it.
 __device__ __forceinline__ float dtrunc_exp(float x) { return expf(x > 15.0f ? 15.0f : x); }
 
-__device__ __forceinline__ int img_index(int m, int lane) { return ((((m >> 2) << 6) + lane) << 2) + (m & 3); }
-
-// column of the head's first layer fed by register 4+r of lane quartet kq: [geo | 1] part of [SH16 | geo15 | 1]
-__device__ __forceinline__ int geo_col(int o) { return o == 0 ? 31 : 15 + o; }
-
 // A operand of forward MFMA m (identical to field_kernel<QF_HEAD_NGP>)
 __device__ float fwd_weight(const TrainArgs &a, int m, int lane)
 {
-    const int i = lane & 15, kq = lane >> 4;
-    if (m < 32) {
-        const int s = m >> 2, mt = m & 3;
-        return a.base_w[(16 * mt + i) * 32 + 2 * (4 * (s >> 1) + kq) + (s & 1)];
-    }
-    if (m < 48) return a.base_w[2048 + i * 64 + hidden_col(m - 32, kq)];
-    m -= 48;
-    if (m < 32) {
-        const int s = m >> 2, mt = m & 3;
-        const int col = s < 4 ? 4 * kq + s : geo_col(4 * kq + (s - 4));
-        return a.head_w[(16 * mt + i) * 32 + col];
-    }
-    if (m < 96) {
-        const int q = m - 32, s = q >> 2, mt = q & 3;
-        return a.head_w[2048 + (16 * mt + i) * 64 + hidden_col(s, kq)];
-    }
-    return a.head_w[2048 + 4096 + i * 64 + hidden_col(m - 96, kq)];
+    return field_image_weight<QF_HEAD_NGP>(a.base_w, a.head_w, qf_sg_head{}, 0, m, lane);
 }
 
 // A operand of backward MFMA bm (a layer's transposed weights): rows = the layer's inputs, k = its outputs, in the
@@ -155,26 +131,9 @@ __global__ __launch_bounds__(kTrainBlock, 1) void ngp_mlp_backward_kernel(const 
 #pragma unroll
         for (int s = 0; s < 8; ++s) feat[s] = a.enc[pt * 32 + 2 * (4 * (s >> 1) + g) + (s & 1)];
         f32x4 h[4] = {zero, zero, zero, zero};
-#pragma unroll
-        for (int s = 0; s < 8; ++s) {
-            const f32x4 w4 = im[s * 64];
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) h[mt] = mfma(w4[mt], feat[s], h[mt]);
-        }
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) h[mt][r] = fmaxf(h[mt][r], 0.0f);
-        f32x4 oa = zero, ob = zero;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const f32x4 w4 = im[(8 + q) * 64];
-            oa = mfma(w4[0], h[q][0], oa);
-            ob = mfma(w4[1], h[q][1], ob);
-            oa = mfma(w4[2], h[q][2], oa);
-            ob = mfma(w4[3], h[q][3], ob);
-        }
-        const f32x4 base_out = oa + ob;
+        dense_layer<8>(im, feat, h);
+        relu<4>(h);
+        const f32x4 base_out = row_tile_layer(im + 8 * 64, h, zero);
         const float ddensity = a.sel[pt] ? dtrunc_exp(base_out[0] - 1.0f) : 0.0f;
         const float dx = a.dirs[pt * 3 + 0], dy = a.dirs[pt * 3 + 1], dzv = a.dirs[pt * 3 + 2];
         const float ux = ((dx + 1.0f) / 2.0f) * 2.0f - 1.0f, uy = ((dy + 1.0f) / 2.0f) * 2.0f - 1.0f,
@@ -185,37 +144,12 @@ __global__ __launch_bounds__(kTrainBlock, 1) void ngp_mlp_backward_kernel(const 
         for (int r = 0; r < 4; ++r) in[4 + r] = base_out[r];
         if (g == 0) in[4] = 1.0f;
         f32x4 h1[4] = {zero, zero, zero, zero};
-#pragma unroll
-        for (int s = 0; s < 8; ++s) {
-            const f32x4 w4 = im[(12 + s) * 64];
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) h1[mt] = mfma(w4[mt], in[s], h1[mt]);
-        }
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) h1[mt][r] = fmaxf(h1[mt][r], 0.0f);
+        dense_layer<8>(im + 12 * 64, in, h1);
+        relu<4>(h1);
         f32x4 h2[4] = {zero, zero, zero, zero};
-#pragma unroll
-        for (int s = 0; s < 16; ++s) {
-            const f32x4 w4 = im[(20 + s) * 64];
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) h2[mt] = mfma(w4[mt], h1[s >> 2][s & 3], h2[mt]);
-        }
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) h2[mt][r] = fmaxf(h2[mt][r], 0.0f);
-        f32x4 ca = zero, cb = zero;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const f32x4 w4 = im[(36 + q) * 64];
-            ca = mfma(w4[0], h2[q][0], ca);
-            cb = mfma(w4[1], h2[q][1], cb);
-            ca = mfma(w4[2], h2[q][2], ca);
-            cb = mfma(w4[3], h2[q][3], cb);
-        }
-        const f32x4 c = ca + cb;
+        dense_layer<16>(im + 20 * 64, h1, h2);
+        relu<4>(h2);
+        const f32x4 c = row_tile_layer(im + 36 * 64, h2, zero);
 
         // ---------------------------------------------------------------- backward through the head
         f32x4 dz3 = zero;                      // rows 0..2 of the 16-row output tile live in lane quartet 0
@@ -227,37 +161,12 @@ __global__ __launch_bounds__(kTrainBlock, 1) void ngp_mlp_backward_kernel(const 
             }
         }
         f32x4 dz2[4] = {zero, zero, zero, zero};
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const f32x4 w4 = bi[s * 64];
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) dz2[mt] = mfma(w4[mt], dz3[s], dz2[mt]);
-        }
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) dz2[mt][r] = h2[mt][r] > 0.0f ? dz2[mt][r] : 0.0f;
+        dense_layer<4>(bi, &dz3, dz2);
+        relu_mask<4>(dz2, h2);
         f32x4 dz1[4] = {zero, zero, zero, zero};
-#pragma unroll
-        for (int s = 0; s < 16; ++s) {
-            const f32x4 w4 = bi[(4 + s) * 64];
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) dz1[mt] = mfma(w4[mt], dz2[s >> 2][s & 3], dz1[mt]);
-        }
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) dz1[mt][r] = h1[mt][r] > 0.0f ? dz1[mt][r] : 0.0f;
-        f32x4 da = zero, db = zero;            // d[1 | geo15]: lane (g,p) register r = d out16 row 4g + r (row 0 unused)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const f32x4 w4 = bi[(20 + q) * 64];
-            da = mfma(w4[0], dz1[q][0], da);
-            db = mfma(w4[1], dz1[q][1], db);
-            da = mfma(w4[2], dz1[q][2], da);
-            db = mfma(w4[3], dz1[q][3], db);
-        }
-        f32x4 dout = da + db;
+        dense_layer<16>(bi + 4 * 64, dz2, dz1);
+        relu_mask<4>(dz1, h1);
+        f32x4 dout = row_tile_layer(bi + 20 * 64, dz1, zero);   // d[1 | geo15]: lane (g,p) register r = d out16 row 4g + r (row 0 unused)
         if (g == 0) dout[0] = valid ? a.d_sigma[pt] * ddensity : 0.0f;   // d trunc_exp(raw - 1) * selector
         if (!valid) dout = zero;
 
@@ -290,16 +199,8 @@ __global__ __launch_bounds__(kTrainBlock, 1) void ngp_mlp_backward_kernel(const 
 
         // ---------------------------------------------------------------- backward through the base MLP
         f32x4 dzh[4] = {zero, zero, zero, zero};
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const f32x4 w4 = bi[(24 + s) * 64];
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) dzh[mt] = mfma(w4[mt], dout[s], dzh[mt]);
-        }
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) dzh[mt][r] = h[mt][r] > 0.0f ? dzh[mt][r] : 0.0f;
+        dense_layer<4>(bi + 24 * 64, &dout, dzh);
+        relu_mask<4>(dzh, h);
         f32x4 de[2] = {zero, zero};
 #pragma unroll
         for (int s = 0; s < 16; ++s) {
@@ -378,19 +279,7 @@ struct SgTrainArgs {
 
 __device__ float sg_fwd_weight(const SgTrainArgs &a, int m, int lane)
 {
-    const int i = lane & 15, kq = lane >> 4;
-    if (m < 32) {
-        const int s = m >> 2, mt = m & 3;
-        return a.base_w[(16 * mt + i) * 32 + 2 * (4 * (s >> 1) + kq) + (s & 1)];
-    }
-    if (m < 48) return a.base_w[2048 + i * 64 + hidden_col(m - 32, kq)];
-    m -= 48;
-    if (m < 16) {
-        const int s = m >> 2, mt = m & 3, row = 16 * mt + i, o = 4 * kq + s;
-        return o == 0 ? a.sg.b1[row] : a.sg.w1[row * 15 + (o - 1)];
-    }
-    const int q = m - 16, s = q >> 2, mt = q & 3;
-    return a.sg.w2[(16 * mt + i) * 64 + hidden_col(s, kq)];
+    return field_image_weight<QF_HEAD_SG>(a.base_w, nullptr, a.sg, a.n_out, m, lane);   // m < kSgFwdMfma: no output tiles
 }
 
 __device__ float sg_bwd_weight(const SgTrainArgs &a, int bm, int lane)
@@ -460,53 +349,20 @@ __global__ __launch_bounds__(kTrainBlock, 1) void sg_mlp_backward_kernel(const S
 #pragma unroll
         for (int s = 0; s < 8; ++s) feat[s] = a.enc[pt * 32 + 2 * (4 * (s >> 1) + g) + (s & 1)];
         f32x4 h[4] = {zero, zero, zero, zero};
-#pragma unroll
-        for (int s = 0; s < 8; ++s) {
-            const f32x4 w4 = im[s * 64];
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) h[mt] = mfma(w4[mt], feat[s], h[mt]);
-        }
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) h[mt][r] = fmaxf(h[mt][r], 0.0f);
-        f32x4 oa = zero, ob = zero;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const f32x4 w4 = im[(8 + q) * 64];
-            oa = mfma(w4[0], h[q][0], oa);
-            ob = mfma(w4[1], h[q][1], ob);
-            oa = mfma(w4[2], h[q][2], oa);
-            ob = mfma(w4[3], h[q][3], ob);
-        }
-        const f32x4 base_out = oa + ob;
+        dense_layer<8>(im, feat, h);
+        relu<4>(h);
+        const f32x4 base_out = row_tile_layer(im + 8 * 64, h, zero);
         const float ddensity = a.sel[pt] ? dtrunc_exp(base_out[0] - 1.0f) : 0.0f;
         f32x4 in = base_out;
         if (g == 0) in[0] = 1.0f;                  // bias slot
         f32x4 h1[4] = {zero, zero, zero, zero};
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const f32x4 w4 = im[(12 + s) * 64];
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) h1[mt] = mfma(w4[mt], in[s], h1[mt]);
-        }
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) h1[mt][r] = fmaxf(h1[mt][r], 0.0f);
+        dense_layer<4>(im + 12 * 64, &in, h1);
+        relu<4>(h1);
         f32x4 h2[4];
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) h2[mt] = b2v[4 * mt + goff];
-#pragma unroll
-        for (int s = 0; s < 16; ++s) {
-            const f32x4 w4 = im[(16 + s) * 64];
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) h2[mt] = mfma(w4[mt], h1[s >> 2][s & 3], h2[mt]);
-        }
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) h2[mt][r] = fmaxf(h2[mt][r], 0.0f);
+        dense_layer<16>(im + 16 * 64, h1, h2);
+        relu<4>(h2);
 
         // ---------------------------------------------------------------- backward through the decoder
         f32x4 dzo[4];
@@ -524,40 +380,13 @@ __global__ __launch_bounds__(kTrainBlock, 1) void sg_mlp_backward_kernel(const S
         f32x4 dz2[4] = {zero, zero, zero, zero};
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-            if (t < a.nt_out) {
-#pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    const f32x4 w4 = bi[(4 * t + s) * 64];
-#pragma unroll
-                    for (int mt = 0; mt < 4; ++mt) dz2[mt] = mfma(w4[mt], dzo[t][s], dz2[mt]);
-                }
-            }
+            if (t < a.nt_out) dense_layer<4>(bi + 4 * t * 64, &dzo[t], dz2);
         }
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) dz2[mt][r] = h2[mt][r] > 0.0f ? dz2[mt][r] : 0.0f;
+        relu_mask<4>(dz2, h2);
         f32x4 dz1[4] = {zero, zero, zero, zero};
-#pragma unroll
-        for (int s = 0; s < 16; ++s) {
-            const f32x4 w4 = bi[(16 + s) * 64];
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) dz1[mt] = mfma(w4[mt], dz2[s >> 2][s & 3], dz1[mt]);
-        }
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) dz1[mt][r] = h1[mt][r] > 0.0f ? dz1[mt][r] : 0.0f;
-        f32x4 da = zero, db = zero;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const f32x4 w4 = bi[(32 + q) * 64];
-            da = mfma(w4[0], dz1[q][0], da);
-            db = mfma(w4[1], dz1[q][1], db);
-            da = mfma(w4[2], dz1[q][2], da);
-            db = mfma(w4[3], dz1[q][3], db);
-        }
-        f32x4 dout = da + db;                      // d out16 rows 4g + r (row 0: see below)
+        dense_layer<16>(bi + 16 * 64, dz2, dz1);
+        relu_mask<4>(dz1, h1);
+        f32x4 dout = row_tile_layer(bi + 32 * 64, dz1, zero);   // d out16 rows 4g + r (row 0: see below)
         if (g == 0) dout[0] = valid ? a.d_sigma[pt] * ddensity : 0.0f;
         if (!valid) dout = zero;
 
@@ -591,16 +420,14 @@ __global__ __launch_bounds__(kTrainBlock, 1) void sg_mlp_backward_kernel(const S
 
         // ---------------------------------------------------------------- base MLP
         f32x4 dzh[4] = {zero, zero, zero, zero};
+        // (written out: with dense_layer here as well, this kernel takes one more AGPR and spills 4 SGPRs)
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             const f32x4 w4 = bi[(36 + s) * 64];
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt) dzh[mt] = mfma(w4[mt], dout[s], dzh[mt]);
         }
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) dzh[mt][r] = h[mt][r] > 0.0f ? dzh[mt][r] : 0.0f;
+        relu_mask<4>(dzh, h);
         f32x4 de[2] = {zero, zero};
 #pragma unroll
         for (int s = 0; s < 16; ++s) {
@@ -678,17 +505,8 @@ struct DeformTrainArgs {
 
 __device__ float df_fwd_weight(const DeformTrainArgs &a, int m, int lane)
 {
-    const int i = lane & 15, kq = lane >> 4;
-    if (m < 18) {
-        const int s = m >> 1, mt = m & 1, row = 16 * mt + i;
-        if (s < 8) return a.w1[row * 35 + 3 + 2 * (4 * (s >> 1) + kq) + (s & 1)];
-        return kq < 3 ? a.w1[row * 35 + kq] : a.b1[row];
-    }
-    if (m < 34) {
-        const int q = m - 18, s = q >> 1, mt = q & 1;
-        return a.w2[(16 * mt + i) * 32 + hidden_col(s, kq)];
-    }
-    return 0.0f;                              // the output layer is not recomputed
+    // the output layer is not recomputed
+    return m < DeformImage<32>::LO ? deform_fwd_weight<32>(a.w1, a.b1, a.w2, a.wout, m, lane) : 0.0f;
 }
 
 __device__ float df_bwd_weight(const DeformTrainArgs &a, int bm, int lane)
@@ -742,23 +560,15 @@ __global__ __launch_bounds__(kTrainBlock, 1) void deform_mlp_backward_kernel(con
         for (int s = 0; s < 8; ++s) in[s] = a.enc[pt * 32 + 2 * (4 * (s >> 1) + g) + (s & 1)];
         in[8] = g < 3 ? a.x01[pt * 3 + g] : 1.0f;
         f32x4 h1[2] = {zero, zero};
-#pragma unroll
-        for (int s = 0; s < 9; ++s)
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt) h1[mt] = mfma(wl[(2 * s + mt) * 64], in[s], h1[mt]);
+        dense_layer<2, 9>(wl, in, h1);
+        relu<2>(h1);
         f32x4 h2[2];
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) { h1[mt][r] = fmaxf(h1[mt][r], 0.0f); h2[mt][r] = bias[16 * mt + 4 * g + r]; }
-#pragma unroll
-        for (int s = 0; s < 8; ++s)
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt) h2[mt] = mfma(wl[(18 + 2 * s + mt) * 64], h1[s >> 2][s & 3], h2[mt]);
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) h2[mt][r] = fmaxf(h2[mt][r], 0.0f);
+            for (int r = 0; r < 4; ++r) h2[mt][r] = bias[16 * mt + 4 * g + r];
+        dense_layer<2, 8>(wl + 18 * 64, h1, h2);
+        relu<2>(h2);
 
         // ---- backward
         const float v = (g == 0 && valid) ? a.d_out[pt] : 0.0f;       // row 0 of the 16-row output tile
@@ -769,14 +579,8 @@ __global__ __launch_bounds__(kTrainBlock, 1) void deform_mlp_backward_kernel(con
 #pragma unroll
             for (int r = 0; r < 4; ++r) dz2[mt][r] = h2[mt][r] > 0.0f ? dz2[mt][r] : 0.0f;
         }
-#pragma unroll
-        for (int s = 0; s < 8; ++s)
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt) dz1[mt] = mfma(bl[(2 + 2 * s + mt) * 64], dz2[s >> 2][s & 3], dz1[mt]);
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) dz1[mt][r] = h1[mt][r] > 0.0f ? dz1[mt][r] : 0.0f;
+        dense_layer<2, 8>(bl + 2 * 64, dz2, dz1);
+        relu_mask<2>(dz1, h1);
 #pragma unroll
         for (int s = 0; s < 8; ++s) {
 #pragma unroll

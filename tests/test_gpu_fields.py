@@ -323,3 +323,42 @@ def test_bf16_field_at_the_config3_table_size(device):
     rgb, den = f(x.to(device), d.to(device))
     _close(rgb, rgb_o, 2e-3, 2e-3)
     _close(den, den_o, 1e-6, 1e-2)
+
+
+@pytest.mark.parametrize("case", ["ngp_fp32", "ngp_fp16", "deform_fp32", "extract_list"])
+def test_dealing_routes_agree(device, case):
+    """A point's result does not depend on which wave computes it (csrc/field_dealing.h): 8197 points in one call
+    (513 groups -> 64 workgroups: one contiguous eighth of the groups per XCD) against the same points in two calls of
+    4101 and 4096 (33 and 32 workgroups: the plain stride), bit for bit.  2^14-row tables."""
+    from quadraturefields_amd import synthetic
+    from quadraturefields_amd.field import Field
+    from quadraturefields_amd.radiance_fields.ngp import NGPRadianceField
+    n, cut = 8197, 4101
+    if case.startswith("ngp"):
+        f = _make(NGPRadianceField, device, log2_T=14)
+        if case == "ngp_fp16":
+            f.compute_dtype = "fp16"
+        x, d = helpers.random_points(n, seed=81)
+        x, d = x.to(device), d.to(device)
+
+        def run(lo, hi):
+            return torch.cat(f(x[lo:hi], d[lo:hi]), 1)
+    else:
+        nl, hidden = ("relu", 32) if case == "deform_fp32" else ("elu", 16)
+        torch.manual_seed(0)
+        f = Field(scale=1.5, precision=16, log2_T=14, L=16, max_res=512, min_res=16, output_dim=1, hidden_size=hidden,
+                  num_features=2, back_prop=False, nl=nl)
+        if hidden == 32:
+            f.load_state_dict(synthetic.seeded_deform_state(f.xyz_encoder.grid.n_params), strict=False)
+        assert f.deform_kernel == (case == "deform_fp32")
+        f = f.to(device)
+        x, _ = helpers.random_points(n, seed=82, outside_frac=0.0)
+        x = x.to(device)
+
+        def run(lo, hi):
+            return f(x[lo:hi], return_grad=False)[0]
+    with torch.no_grad():
+        whole = run(0, n)
+        parts = torch.cat([run(0, cut), run(cut, n)], 0)
+    assert whole.shape[0] == n and bool(torch.isfinite(whole).all()) and float(whole.std()) > 0
+    assert torch.equal(whole, parts)
