@@ -412,6 +412,12 @@ int32_t qf_bvh_max_stack(const qf_bvh *bvh);
 int qf_bvh_copy_nodes(const qf_bvh *bvh, float *nodes_host, int64_t capacity_nodes);
 int qf_bvh_copy_wide_nodes(const qf_bvh *bvh, float *nodes_host, int64_t capacity_nodes);
 int qf_bvh_copy_tri_ids(const qf_bvh *bvh, int32_t *ids_host, int64_t capacity);
+/* Host copy, for inspection/tests, of the visible-chunk list the LAST culled qf_raster_intersect /
+ * qf_raster_intersect_wide call on this handle produced (chunk = 64 consecutive triangles in leaf order).  Waits
+ * for `stream`.  Returns the number of visible chunks (also when it exceeds capacity; then only `capacity`
+ * entries are written), or a negative status if no culled call has run -- or a qf_raster_intersect_slabs call, which
+ * reuses the list's memory, has run since.  Order unspecified.  Read-only: the handle's state is left alone.  */
+int64_t qf_bvh_copy_visible_chunks(const qf_bvh *bvh, int32_t *chunks_host, int64_t capacity, void *stream);
 
 /* The reference's multi-hit rule (trimesh 3.23.5 ray_pyembree.RayMeshIntersector.intersects_id, called at
  * mesh_utils.py:350-354): after every hit the ray is re-originated `min_separation` past it and

@@ -131,6 +131,7 @@ _SIGNATURES = {
     "qf_bvh_max_depth": (c_int32, [_P]),
     "qf_bvh_copy_nodes": (c_int, [_P, _P, c_int64]),
     "qf_bvh_copy_tri_ids": (c_int, [_P, _P, c_int64]),
+    "qf_bvh_copy_visible_chunks": (c_int64, [_P, _P, c_int64, _P]),
     "qf_bvh_intersect": (c_int, [_P, _P, _P, c_int64, c_int32, c_int32, _P, _P, _P, _P]),
     "qf_bvh_repair_overflow": (c_int, [_P, _P, _P, c_int64, c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "qf_raster_intersect": (c_int, [_P, POINTER(Camera), _P, _P, c_int64, c_int32, _P, _P, _P, _P, c_int32, c_int32, _P, _P]),

@@ -40,6 +40,7 @@ struct qf_bvh {
     int32_t *d_visible = nullptr;
     bool chunk_dirty = true;         // the triangles changed (build / refit): boxes are recomputed before the next use
     int cull_parity = 0;
+    int cull_last = -1;              // counter parity the last culled call appended to; -1: none yet, or the list was reused since
     // depth-slab pass (qf_raster_intersect_slabs): per-chunk distance range, per-slab chunk lists, control block
     float *d_slab_range = nullptr;
     int32_t *d_slab_lists = nullptr;

@@ -962,6 +962,7 @@ static int raster_launch(qf_bvh *bvh, const qf_camera *cam, const float *rays_o,
         int32_t *counters = bvh->d_visible, *visible = bvh->d_visible + 2;
         const int parity = bvh->cull_parity;
         bvh->cull_parity ^= 1;
+        bvh->cull_last = parity;
         hipLaunchKernelGGL(cull_chunks_kernel, dim3((unsigned)qf_div_up(n_chunks, 256)), dim3(256), 0, st, boxes,
                            (int)n_chunks, rc, visible, counters, parity, reinterpret_cast<const uint32_t *>(rays_o), rays_d,
                            n_rays, origin_flag);
@@ -1102,6 +1103,7 @@ extern "C" int qf_raster_intersect_slabs(qf_bvh *bvh, const qf_camera *cam, cons
     const float4 *tris4 = reinterpret_cast<const float4 *>(bvh->d_tris);
     const float4 *boxes = reinterpret_cast<const float4 *>(bvh->d_chunk_box);
     int32_t *visible = bvh->d_visible + 2;
+    bvh->cull_last = -1;                     // slab_cull_kernel overwrites the culled passes' list (its count is the control block's)
     float2 *range = reinterpret_cast<float2 *>(bvh->d_slab_range);
     SlabCtl *ctl = reinterpret_cast<SlabCtl *>(bvh->d_slab_ctl);
     camera_check_launch(rc, rays_o, rays_d, n_rays, origin_flag, st);
@@ -1146,4 +1148,18 @@ extern "C" int qf_raster_intersect_slabs(qf_bvh *bvh, const qf_camera *cam, cons
                        wide_keys, hit_tri, hit_t, hit_count);
     QF_LAUNCH_CHECK();
     return QF_OK;
+}
+
+extern "C" int64_t qf_bvh_copy_visible_chunks(const qf_bvh *bvh, int32_t *chunks_host, int64_t capacity, void *stream)
+{
+    if (!bvh || capacity < 0 || (capacity > 0 && !chunks_host)) return QF_ERR_INVALID_ARGUMENT;
+    if (!bvh->d_visible || bvh->cull_last < 0) return QF_ERR_INVALID_ARGUMENT;     // no culled call whose list is still there
+    QF_HIP_TRY(hipStreamSynchronize(qf_stream(stream)));
+    int32_t n = 0;
+    QF_HIP_TRY(hipMemcpy(&n, bvh->d_visible + bvh->cull_last, sizeof(int32_t), hipMemcpyDeviceToHost));
+    const int64_t n_chunks = qf_div_up(bvh->n_tri, kCullChunk);
+    if (n < 0 || n > n_chunks) return QF_ERR_HIP;                                  // (the list holds n_chunks entries)
+    const int64_t take = n < capacity ? n : capacity;
+    if (take > 0) QF_HIP_TRY(hipMemcpy(chunks_host, bvh->d_visible + 2, (size_t)take * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return n;
 }

@@ -171,6 +171,8 @@ class RayIntersector:
             min_separation = trimesh_ray_offset(mesh.vertices)
         self.min_separation = max(float(min_separation), 0.0)
         self.last_order = None           # coherent processing order of the most recent image-shaped sample_device()
+        self.last_route = None           # the ABI call that answered the most recent intersection: "bvh", "plain", "plain+cull",
+                                         # "bins", "wide", "wide+cull", "slabs", "frame" or "frame+cull" (recorded, never read)
         self._raster_backoff = 0         # frames left to skip the camera-coherent intersector after an overflow
         self.repaired_frames = 0         # frames on which some pixels overflowed K and were repaired through the BVH
         self.camera_mismatch_frames = 0  # frames whose rays were not their camera's pixel grid (see camera_mismatch)
@@ -358,6 +360,7 @@ class RayIntersector:
     def _hits_bvh(self, o, d, k, image_width):
         n = o.shape[0]
         hit_tri, hit_t, hit_count = self._alloc_hits(n, k)
+        self.last_route = "bvh"
         _C.check(_C.lib().qf_bvh_intersect(self._handle, _C.ptr(o), _C.ptr(d), n, k, int(image_width),
                                            _C.ptr(hit_tri), _C.ptr(hit_t), _C.ptr(hit_count), _C.stream()),
                  "qf_bvh_intersect")
@@ -373,6 +376,7 @@ class RayIntersector:
         counts = torch.empty((n + 2,), dtype=torch.int32, device=self.device)
         hit_count, overflow = counts[:n], counts[n:n + 1]
         self._raster_words = counts[n:]                       # (overflow counter, ray flag): ``hits`` reads both at once
+        self.last_route = "plain"
         _C.check(_C.lib().qf_raster_intersect(self._handle, ctypes.byref(camera), _C.ptr(o), _C.ptr(d), n, k,
                                               _C.ptr(hit_tri), _C.ptr(hit_t), _C.ptr(hit_count), _C.ptr(overflow),
                                               1 if sort_lists else 0, 0, _C.ptr(counts[n + 1:]), _C.stream()),
@@ -494,6 +498,7 @@ class RayIntersector:
         cull = 1 if getattr(camera, "cull", False) else 0
         if bins:
             cursor, mask, records = self._bin_scratch(camera, k)
+            self.last_route = "bins"
             _C.check(_C.lib().qf_raster_intersect_tiles(self._handle, ctypes.byref(camera), _C.ptr(o), _C.ptr(d), n, k,
                                                         _C.ptr(cursor), _C.ptr(mask), _C.ptr(records), records.numel() * 8,
                                                         _C.ptr(hit_count), _C.ptr(overflow), _C.ptr(origin_flag),
@@ -509,6 +514,7 @@ class RayIntersector:
             if keys is None:
                 self._wide_scratch.clear()
                 keys = self._wide_scratch[key] = torch.empty((wide_s, n), dtype=torch.int64, device=self.device)
+            self.last_route = "slabs"
             _C.check(_C.lib().qf_raster_intersect_slabs(self._handle, ctypes.byref(camera), _C.ptr(o), _C.ptr(d), n, k, wide_s,
                                                         int(self.raster_slabs), _C.ptr(keys), _C.ptr(hit_tri), _C.ptr(hit_t),
                                                         _C.ptr(hit_count), _C.ptr(overflow), _C.ptr(origin_flag), _C.stream()),
@@ -520,12 +526,14 @@ class RayIntersector:
                 self._wide_scratch.clear()
                 lists = self._wide_scratch[key] = (torch.empty((wide, n), dtype=torch.int32, device=self.device),
                                                    torch.empty((wide, n), dtype=torch.float32, device=self.device))
+            self.last_route = "wide+cull" if cull else "wide"
             _C.check(_C.lib().qf_raster_intersect_wide(self._handle, ctypes.byref(camera), _C.ptr(o), _C.ptr(d), n, k, wide,
                                                        _C.ptr(lists[0]), _C.ptr(lists[1]), _C.ptr(hit_tri), _C.ptr(hit_t),
                                                        _C.ptr(hit_count), _C.ptr(overflow), cull, _C.ptr(origin_flag),
                                                        _C.stream()),
                      "qf_raster_intersect_wide")
         else:
+            self.last_route = "plain+cull" if cull else "plain"
             _C.check(_C.lib().qf_raster_intersect(self._handle, ctypes.byref(camera), _C.ptr(o), _C.ptr(d), n, k,
                                                   _C.ptr(hit_tri), _C.ptr(hit_t), _C.ptr(hit_count), _C.ptr(overflow),
                                                   0, cull, _C.ptr(origin_flag), _C.stream()), "qf_raster_intersect")

@@ -88,6 +88,7 @@ class MeshPruner:
             prepared = fr._one_call_job(origins, viewdirs, camera, k, None, False, want_tri=True, image=False) if one_call else None
             if prepared is not None:
                 job, frame, token, keep, _ = prepared
+                ri.last_route = "frame+cull" if job.cull_chunks & 1 else "frame"
                 _C.check(_C.lib().qf_frame_prune(ri._handle, ctypes.byref(job), _C.ptr(self.triangle_weights), self.n_faces,
                                                  self.valid_threshold, _C.ptr(counts), _C.ptr(self._bad_ids), _C.stream()),
                          "qf_frame_prune")

@@ -169,6 +169,7 @@ class FrameRenderer:
         if prepared is None:                  # the intersector's policy moved while settling an earlier frame
             return self.render_async(origins, viewdirs, camera, 0.0, render_bkgd, packed)
         job, frame, token, keep, (rgb, alpha, depth, out5) = prepared
+        ri.last_route = "frame+cull" if job.cull_chunks & 1 else "frame"
         _C.check(_C.lib().qf_frame_render(ri._handle, ctypes.byref(job), _C.stream()), "qf_frame_render")
         ri.fused_frame_done(frame, token)
         frame._keep = frame._keep + keep      # referenced until their readers ran
@@ -243,6 +244,7 @@ class FrameRenderer:
             prepared = None
         if prepared is not None:
             job, frame, token = prepared
+            ri.last_route = "frame+cull" if job.cull_chunks & 1 else "frame"
             _C.check(_C.lib().qf_frame_render(ri._handle, ctypes.byref(job), _C.stream()), "qf_frame_render")
             ri.fused_frame_done(frame, token)
         else:

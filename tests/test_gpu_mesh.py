@@ -214,7 +214,7 @@ def test_full_size_mesh_sampled_against_bruteforce(device):
     k = np.arange(25)[None, :]
     valid = k < cnt_h[:, None]
     assert np.isinf(t_h[~valid]).all() and (tri.cpu().numpy()[~valid] == -1).all()
-    tt = np.where(valid, t_h, np.inf)
+    tt = np.where(valid, t_h, 0.0)                                  # (the inf padding out of the subtraction)
     assert (np.diff(tt, axis=1)[valid[:, 1:]] >= 0).all()          # ascending within each ray
     rng = np.random.default_rng(1)
     pick = np.concatenate([rng.choice(640000, 192, replace=False), np.flatnonzero(cnt_h == cnt_h.max())[:64]])
@@ -245,7 +245,11 @@ def test_raster_intersector_identical_to_bvh(device, w, h, max_hits):
         o, d = synthetic.camera_rays(c2w, focal, w, h)
         cam = make_camera(c2w, focal, w, h)
         a = ri.hits(o, d, image_width=w)
+        assert ri.last_route == "bvh"
+        ri._raster_backoff = 0                             # (seed 7 must not find the back-off seed 0's overflow left)
         b = ri.hits(o, d, camera=cam)                      # max_hits=3 overflows -> exercises the fallback
+        # 25: the plain pass answered; 3: it was issued, reported its overflow (the back-off is set) and the BVH answered
+        assert (ri.last_route, ri._raster_backoff > 0) == (("plain", False) if max_hits == 25 else ("bvh", True))
         for x, y in zip(a[:3], b[:3]):
             assert torch.equal(x, y)
         tri_o, t_o, cnt_o = om.BruteForceIntersector(mesh.vertices, mesh.faces).hits(o.numpy(), d.numpy(), max_hits)
@@ -255,7 +259,9 @@ def test_raster_intersector_identical_to_bvh(device, w, h, max_hits):
             raw = ri._hits_raster(a[3], a[4], max_hits, cam)
             assert int(raw[3].item()) == 0
             s1 = ri.sample_device(o, d, image_width=w)
+            assert ri.last_route == "bvh"
             s2 = ri.sample_device(o, d, camera=cam)
+            assert ri.last_route == "plain" and ri.repaired_frames == 0
             for x, y in zip(s1, s2):
                 assert torch.equal(x, y)
         else:
@@ -264,7 +270,9 @@ def test_raster_intersector_identical_to_bvh(device, w, h, max_hits):
             ri._raster_backoff = 0
             before = ri.repaired_frames
             s1 = ri.sample_device(o, d, image_width=w)
+            assert ri.last_route == "bvh"
             s2 = ri.sample_device(o, d, camera=cam)
+            assert ri.last_route == "plain"                # (RASTER_WIDE_FACTOR = 1: never the wide lists)
             assert ri.repaired_frames == before + 1
             for x, y in zip(s1, s2):
                 assert torch.equal(x, y)
@@ -274,9 +282,12 @@ def test_raster_intersector_identical_to_bvh(device, w, h, max_hits):
     focal = 30.0
     o, d = synthetic.camera_rays(c2w, focal, w, h)
     a = ri.hits(o, d, image_width=w)
+    ri._raster_backoff = 0
     b = ri.hits(o, d, camera=make_camera(c2w, focal, w, h))
+    assert (ri.last_route, ri._raster_backoff > 0) == (("plain", False) if max_hits == 25 else ("bvh", True))
     for x, y in zip(a[:3], b[:3]):
         assert torch.equal(x, y)
+    assert ri.camera_mismatch_frames == 0
 
 
 @pytest.mark.parametrize("k,wide,slabs,room", [(5, 24, 0, 32), (5, 7, 0, 32), (5, 0, 0, 32), (64, 128, 0, 32),
@@ -297,14 +308,19 @@ def test_wide_raster_selects_the_k_nearest_like_the_bvh(device, k, wide, slabs, 
     ri.raster_wide = wide
     ri.raster_slabs, ri.SLAB_ROOM = slabs, room
     brute = om.BruteForceIntersector(mesh.vertices, mesh.faces)
+    # the pass every camera frame must take.  wide = 0: the mesh's depth complexity (3.8 crossings per ray, more than K / 2)
+    # seeds the dense mode before the first frame; wide = 7 grows to 4 K after its first frame, on the same entry point
+    route = "slabs" if slabs >= 2 else "wide"
     for seed in (1, 5, 9):
         c2w = synthetic.orbit_cameras(1, seed=seed)[0]
         focal = synthetic.lego_focal(800) * w / 800.0
         o, d = synthetic.camera_rays(c2w, focal, w, h)
         cam = make_camera(c2w, focal, w, h)
         s1 = ri.sample_device(o, d, image_width=w)
+        assert ri.last_route == "bvh"
         ri._raster_backoff = 0
         s2 = ri.sample_device(o, d, camera=cam)
+        assert ri.last_route == route and ri.raster_wide > k
         for x, y in zip(s1, s2):
             assert torch.equal(x, y)
         counts = brute.hits(o.numpy(), d.numpy(), 64)[2]
@@ -317,6 +333,7 @@ def test_wide_raster_selects_the_k_nearest_like_the_bvh(device, k, wide, slabs, 
         assert ri.raster_wide == 4 * k and ri._raster_streak == 0       # switched on, never backed off to the BVH
     if wide == 7:
         assert ri._raster_streak > 0 or ri.repaired_frames > 0
+    assert ri.camera_mismatch_frames == 0
 
 
 def test_last_order_is_the_tile_rank_pixel_permutation(device):

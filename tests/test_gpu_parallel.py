@@ -89,27 +89,38 @@ def test_bands_equal_the_frame_for_any_cuts_and_for_the_bvh_route(device):
     from quadraturefields_amd.mesh_utils import make_camera
     fr, cams, focal = _build(device)
     o, d = synthetic.camera_rays(cams[0], focal, W, H, device=device)
+    ri = fr.mesh_intersect.rayintersector
     rgb, alpha, depth, n = fr.render(o, d, camera=make_camera(cams[0], focal, W, H))
+    assert ri.last_route == "plain"
     whole = torch.cat([rgb, alpha, depth], dim=1)
     assert n > 1000
     sharded = parallel.ShardedFrameRenderer(fr, 0, 1)
     for cuts in ([0, 8, 72, 120, H], [0, 64, H], [0, 40, 40, H]):
-        parts = [sharded.render_band(o, d, cams[0], focal, W, H, a, b) for a, b in zip(cuts[:-1], cuts[1:])]
+        parts = []
+        for a, b in zip(cuts[:-1], cuts[1:]):
+            ri.last_route = None
+            parts.append(sharded.render_band(o, d, cams[0], focal, W, H, a, b))
+            # a band camera: the one-call frame with the chunk-culled pass (an empty band issues nothing)
+            assert ri.last_route == ("frame+cull" if b > a else None), (cuts, a, b)
         assert torch.equal(torch.cat(parts), whole), cuts
+    ri._settle_deferred_policy()
+    assert ri.camera_mismatch_frames == 0 and ri.repaired_frames == 0 and ri._raster_backoff == 0
     parts = []
     for a, b in ((0, 56), (56, H)):
         r, al, de, _ = fr.render(o[a * W:b * W], d[a * W:b * W], image_width=W)             # BVH traversal
+        assert ri.last_route == "bvh"
         parts.append(torch.cat([r, al, de], dim=1))
     assert torch.equal(torch.cat(parts), whole)
 
 
 def test_band_triangle_culling_keeps_every_hit(device):
     """qf_raster_intersect(cull_chunks=1): the chunk-culled camera-coherent pass of a band camera returns exactly the
-    samples of the unculled pass -- for ordinary bands, a one-tile-row band, a band that sees nothing, a close-up from
-    inside the shells (box corners behind the camera plane) and after a vertex update (chunk boxes recomputed).  The
-    visible-chunk count must really shrink with the band (the point of the exercise)."""
+    samples of the unculled pass -- for ordinary bands, a one-tile-row band, a close-up from inside the shells (box corners
+    behind the camera plane), after a vertex update (chunk boxes recomputed) and for a band that sees nothing.  Every
+    compared call is checked to have taken the pass it is about (``last_route``); that the visible-chunk list shrinks
+    with the band is tests/test_gpu_raster_passes.py's (must <= visible <= may)."""
     from quadraturefields_amd import parallel, synthetic
-    from quadraturefields_amd.mesh_utils import MeshIntersection, make_camera
+    from quadraturefields_amd.mesh_utils import MeshIntersection
     mesh = synthetic.shell_mesh(n_shells=4, subdivisions=5)             # 81 920 triangles = 1 280 chunks
     mi = MeshIntersection(mesh, simplify_mesh=False, scale=1.0, num_intersections=25, device=device)
     ri = mi.rayintersector
@@ -118,7 +129,9 @@ def test_band_triangle_culling_keeps_every_hit(device):
 
     def samples(o, d, cam, cull):
         cam.cull = cull
+        ri._raster_backoff = 0                                           # the route must not depend on earlier frames
         data = ri.sample_device(o, d, 25, camera=cam, layout=False)
+        assert ri.last_route == ("plain+cull" if cull else "plain")
         return None if data is None else [t.clone() for t in data]
 
     cams = list(synthetic.orbit_cameras(2, seed=31))
@@ -135,10 +148,7 @@ def test_band_triangle_culling_keeps_every_hit(device):
             assert (a is None) == (b is None)
             if a is not None:
                 assert all(torch.equal(x, y) for x, y in zip(a, b))
-    # a band far off the object: nothing visible, nothing hit
-    o, d = synthetic.camera_rays(cams[0], focal, w, h, device=device)
-    cam = parallel.band_camera(cams[0], focal, w, h, 0, 8)
-    assert samples(o[:8 * w] + 50.0, d[:8 * w], cam, True) is None
+    assert ri.camera_mismatch_frames == 0 and ri.repaired_frames == 0
     # vertex update (device refit): the chunk boxes are recomputed before the next culled pass -- stale boxes would lose
     # the hits of every chunk that moved out of its old box
     v2 = torch.from_numpy(mesh.vertices.astype("float32")).to(device)
@@ -149,10 +159,16 @@ def test_band_triangle_culling_keeps_every_hit(device):
         ob, db = o[y0 * w:y1 * w], d[y0 * w:y1 * w]
         a = samples(ob, db, parallel.band_camera(cams[1], focal, w, h, y0, y1), True)
         b = samples(ob, db, parallel.band_camera(cams[1], focal, w, h, y0, y1), False)
-        assert (a is None) == (b is None)
-        if a is not None:
-            assert all(torch.equal(x, y) for x, y in zip(a, b))
-    assert a is not None or b is not None or True
+        assert a is not None and b is not None
+        assert all(torch.equal(x, y) for x, y in zip(a, b))
+    assert ri.camera_mismatch_frames == 0
+    # a band far off the object: nothing visible, nothing hit.  (Its origins are not the camera's: the culled pass is
+    # issued, its ray check sends the frame through the BVH and the next frames would back off -- hence last.)
+    o, d = synthetic.camera_rays(cams[0], focal, w, h, device=device)
+    cam = parallel.band_camera(cams[0], focal, w, h, 0, 8)
+    with pytest.warns(UserWarning, match="not that camera's pixel grid"):
+        assert samples(o[:8 * w] + 50.0, d[:8 * w], cam, True) is None
+    assert ri.camera_mismatch_frames == 1
 
 
 def _rccl_one_rank_worker(port, q):
