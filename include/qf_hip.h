@@ -269,6 +269,33 @@ int qf_deform_mlp_backward(const float *enc, const float *x01, const float *d_ou
                            float *d_enc, float *d_x01, float *g_w1, float *g_b1, float *g_w2, float *g_b2,
                            float *g_wout, float *g_bout, void *stream);
 
+/* Stage 2's training step (train_field.py:297-372 over field.py:206-259), fused: the quadrature loss of the scalar
+ * Field of qf_field_grid_extract and its gradients in one launch.  Per point, with s = scale, u = [x01 | grid(x01)],
+ * phi = ELU: f = wout . phi(W2 phi(W1 u + b1) + b2) + bout; g = d f / d x through the three x01 columns (the encoder
+ * sees x01.detach()), divided by 2 s; p = g . dirs/|dirs|; r = max(weights, weights_rev) - |p|;
+ * loss = (1/n) sum |r| (Field.compute_field_loss).  sign(0) = 0 as torch.abs's backward.
+ *   xyz, dirs [n,3], weights, weights_rev [n]; dirs need not be normalised.
+ *   upstream: device float[1] = d(objective)/d(loss), or NULL for 1; it scales d_enc and the weight gradients.
+ *   loss: device double[1], or NULL; summed in fp64 in a fixed order (bit-identical run to run); NaN when n = 0 (torch's
+ *     mean of an empty tensor), which needs no launch.  workspace: QF_FIELD_LOSS_WORKSPACE_BYTES of device memory
+ *     (workspace_bytes says how much there is; it needs no initialisation), required with loss.
+ *   value [n], grad [n,3] (= g, fp32), d_enc [n,32] (= d loss / d grid(x01), for qf_grid_encode_backward): each or NULL.
+ *   g_w1 [16,35], g_b1 [16], g_w2 [16,16], g_b2 [16], g_wout [16]: all five or none; ACCUMULATED into.  bout does not
+ *     enter the loss and has no gradient.
+ *   With loss, d_enc and the gradients all NULL the call is the inference of (value, grad) alone and dirs, weights,
+ *   weights_rev and upstream are not read (upstream must be NULL).
+ * Errors (before any launch): QF_ERR_UNSUPPORTED unless hidden = 16, activation = QF_ACT_ELU and the grid is one that
+ * qf_field_grid_extract takes; QF_ERR_INVALID_ARGUMENT for NULL arrays, n < 0, scale not in (0, 3e38], some but not all
+ * of the five gradients, or loss without workspace.                                                  */
+#define QF_FIELD_LOSS_WORKSPACE_BYTES 8192
+int qf_field_quadrature_loss(const qf_grid_desc *grid /* host */, const float *table, float scale, int32_t hidden,
+                             int32_t activation, const float *w1, const float *b1, const float *w2, const float *b2,
+                             const float *wout, const float *bout, const float *xyz, const float *dirs,
+                             const float *weights, const float *weights_rev, int64_t n, const float *upstream,
+                             double *loss, float *value, float *grad, float *d_enc, float *g_w1, float *g_b1,
+                             float *g_w2, float *g_b2, float *g_wout, void *workspace, int64_t workspace_bytes,
+                             void *stream);
+
 /* One step of torch.optim.Adam (the reference's optimiser, train_finetune.py:402-417; amsgrad off) on one flat fp32
  * parameter tensor, in ONE launch: the update of torch's foreach implementation element for element --
  *   m += (1-b1)(g-m); v = v b2 + (1-b2) g g; p += -(lr/(1-b1^t)) * m / (sqrt(v)/sqrt(1-b2^t) + eps)

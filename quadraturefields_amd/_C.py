@@ -26,6 +26,7 @@ UNTOUCHED_LAST_FACE, UNTOUCHED_ZERO = 0, 1            # qf_texel_positions
 BG_WHITE, BG_BLACK, BG_CUSTOM, BG_NONE = 0, 1, 2, 3
 # the device state block of the volumetric rounds (qf_grid_march_round_count)
 DISTORTION_WORKSPACE_BYTES = 16400                    # QF_DISTORTION_WORKSPACE_BYTES
+FIELD_LOSS_WORKSPACE_BYTES = 8192                     # QF_FIELD_LOSS_WORKSPACE_BYTES
 VOLUMETRIC_STATE_WORDS, VOLUMETRIC_TOTAL_SAMPLES, VOLUMETRIC_ROUND_SAMPLES, VOLUMETRIC_ROUND_QUOTA = 8, 2, 3, 4
 
 
@@ -98,6 +99,8 @@ _SIGNATURES = {
     "qf_field_grid_extract": (c_int, [POINTER(GridDesc), _P, c_float, c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, c_int64, _P, _P, _P, _P]),
     "qf_field_grid_extract_f16": (c_int, [POINTER(GridDesc), _P, c_float, c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, c_int64, _P, _P, _P, _P]),
     "qf_deform_mlp_backward": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "qf_field_quadrature_loss": (c_int, [POINTER(GridDesc), _P, c_float, c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                         c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, _P]),
     "qf_adam_step": (c_int, [_P, _P, _P, _P, c_int64, c_double, c_double, c_double, c_double, c_double, c_int32, c_int64, _P]),
     "qf_apply_deformation": (c_int, [_P, c_float, _P, _P, _P, c_int64, _P, _P, _P, _P]),
     "qf_mark_pack_boundaries": (c_int, [_P, c_int64, _P, _P]),

@@ -26,6 +26,7 @@ SOURCES = [
     ("grid_extract.hip", []),
     ("grid_backward.hip", []),
     ("mlp_train.hip", []),
+    ("field_train.hip", []),
     ("scan.hip", []),
     ("composite.hip", []),
     ("distortion.hip", []),

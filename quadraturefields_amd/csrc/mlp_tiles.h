@@ -1,6 +1,6 @@
 // The fp32 matrix-core pieces shared by the fused field kernels and their training-side backward kernels
-// (field_eval.hip, grid_extract.hip, mlp_train.hip): the MFMA, the LDS weight images of the layers that more than one
-// kernel computes, and the layer idioms over them.
+// (field_eval.hip, grid_extract.hip, mlp_train.hip, field_train.hip): the MFMA, the LDS weight images of the layers that
+// more than one kernel computes, the layer idioms over them and the weight-gradient tiles of the training kernels.
 //
 // Every layer is computed transposed, H^T[neuron][point] = W . X^T, with v_mfma_f32_16x16x4_f32: W tiles are the A
 // operand, one value per lane (i = lane & 15: row of the tile, kq = lane >> 4: k of the step), X^T the B operand.  The
@@ -137,6 +137,30 @@ __device__ __forceinline__ void relu_mask(f32x4 dz[MT], const f32x4 h[MT])
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
         for (int r = 0; r < 4; ++r) dz[mt][r] = h[mt][r] > 0.0f ? dz[mt][r] : 0.0f;
+}
+
+// ---- weight-gradient tiles of the training-side kernels (mlp_train.hip, field_train.hip)
+// D layout (lane (g,p): rows 4g..4g+3 of column p) -> A/B layout (lane (i,kq): row i, columns 4s+kq for s = 0..3),
+// through a 16 x 17 float scratch private to the wave.
+__device__ __forceinline__ f32x4 to_operand(const f32x4 d, volatile float *scratch, int lane)
+{
+    const int g = lane >> 4, p = lane & 15;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) scratch[(4 * g + r) * 17 + p] = d[r];
+    __builtin_amdgcn_wave_barrier();
+    f32x4 o;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) o[s] = scratch[p * 17 + 4 * s + g];   // row i = p, column 4s + kq, kq = g
+    __builtin_amdgcn_wave_barrier();
+    return o;
+}
+
+// acc += dz^T-tile x a^T-tile over the 16 points of the group (4 k-steps of 4 points)
+__device__ __forceinline__ f32x4 outer_acc(const f32x4 dz_op, const f32x4 a_op, f32x4 acc)
+{
+#pragma unroll
+    for (int s = 0; s < 4; ++s) acc = mfma(dz_op[s], a_op[s], acc);
+    return acc;
 }
 
 }  // namespace

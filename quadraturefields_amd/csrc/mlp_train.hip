@@ -67,29 +67,6 @@ __device__ float bwd_weight(const TrainArgs &a, int bm, int lane)
     return a.base_w[hidden_col(s, kq) * 32 + 16 * mt + i];
 }
 
-// D layout (lane (g,p): rows 4g..4g+3 of column p) -> A/B layout (lane (i,kq): row i, columns 4s+kq for s = 0..3),
-// through a 16 x 17 float scratch private to the wave.
-__device__ __forceinline__ f32x4 to_operand(const f32x4 d, volatile float *scratch, int lane)
-{
-    const int g = lane >> 4, p = lane & 15;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) scratch[(4 * g + r) * 17 + p] = d[r];
-    __builtin_amdgcn_wave_barrier();
-    f32x4 o;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) o[s] = scratch[p * 17 + 4 * s + g];   // row i = p, column 4s + kq, kq = g
-    __builtin_amdgcn_wave_barrier();
-    return o;
-}
-
-// acc += dz^T-tile x a^T-tile over the 16 points of the group (4 k-steps of 4 points)
-__device__ __forceinline__ f32x4 outer_acc(const f32x4 dz_op, const f32x4 a_op, f32x4 acc)
-{
-#pragma unroll
-    for (int s = 0; s < 4; ++s) acc = mfma(dz_op[s], a_op[s], acc);
-    return acc;
-}
-
 __global__ __launch_bounds__(kTrainBlock, 1) void ngp_mlp_backward_kernel(const TrainArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];

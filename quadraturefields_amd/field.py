@@ -7,6 +7,7 @@ differentiable route (HIP grid forward/backward + library GEMMs) is taken, which
 including ``create_graph=True`` (the reference's default), through the second-order grid kernel.  The finetune
 configuration (relu, hidden 32) infers through the deformation kernel; stage 2's (elu, hidden 16, train_field.py:238-252)
 and the other two combinations through qf_field_grid_extract's point list (``field_utils`` uses its lattice source).
+Stage 2's training step is ``field_loss``: the quadrature loss with a fused backward (qf_field_quadrature_loss).
 """
 import numpy as np
 import torch
@@ -71,6 +72,37 @@ class _DeformTrainFn(torch.autograd.Function):
         return (None, g_table, *grads, None)
 
 
+class _FieldLossFn(torch.autograd.Function):
+    """Field.field_loss on qf_field_quadrature_loss: the forward launch gives the loss, the backward launch (with the
+    upstream scalar read on the device) the five decoder gradients and d_enc, which qf_grid_encode_backward scatters
+    into the table.  ``lout.bias`` is not an input: it does not enter the loss and keeps ``grad = None``."""
+
+    @staticmethod
+    def forward(ctx, table, w1, b1, w2, b2, wout, module, x, dirs, weights, weights_rev):
+        x, dirs = _C.f32c(x.detach().reshape(-1, 3)), _C.f32c(dirs.detach().reshape(-1, 3))
+        weights, weights_rev = _C.f32c(weights.detach().reshape(-1)), _C.f32c(weights_rev.detach().reshape(-1))
+        ctx.save_for_backward(table, w1, b1, w2, b2, wout, x, dirs, weights, weights_rev)
+        ctx.module = module
+        return module._quadrature_loss(x, dirs, weights, weights_rev)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_loss):
+        table, w1, b1, w2, b2, wout, x, dirs, weights, weights_rev = ctx.saved_tensors
+        m = ctx.module
+        n = x.shape[0]
+        grads = [torch.zeros_like(t, dtype=torch.float32) for t in (w1, b1, w2, b2, wout)]
+        g_table = torch.zeros_like(table, dtype=torch.float32)
+        if n:
+            table32 = _C.f32c(table.detach())
+            d_enc = torch.empty((n, 32), dtype=torch.float32, device=x.device)
+            m._quadrature_call(x, dirs, weights, weights_rev, upstream=_C.f32c(d_loss.detach().reshape(1)), d_enc=d_enc,
+                               grads=grads)
+            x01 = _C.f32c((x - m.xyz_min) / (m.xyz_max - m.xyz_min))
+            _C.grid_encode_backward(m.xyz_encoder.grid.desc, table32, x01, d_enc, n, g_table, None)
+        return (g_table, *grads, None, None, None, None, None)
+
+
 class Field(nn.Module):
     def __init__(self, scale, back_prop=0, precision=16, log2_T=19, L=16, max_res=512, output_dim=1, min_res=16,
                  hidden_size=32, num_features=2, nl="elu", bias=True, bias_last=True):
@@ -109,7 +141,7 @@ class Field(nn.Module):
     def deform_kernel(self) -> bool:
         """True for the finetune configuration (relu, hidden 32), which the deformation kernel (qf_deform_field_forward)
         and its fused backward serve; every other accepted configuration infers through qf_field_grid_extract's point
-        list and trains through the differentiable route."""
+        list and trains through the differentiable route (stage 2's loss has a fused step of its own: ``field_loss``)."""
         return self.nl == "relu" and self.hidden_size == 32
 
     #: Precision of the fused inference kernel: "fp32" (default; parity with the fp32 oracle to ~1e-6) or "fp16", the
@@ -166,6 +198,7 @@ class Field(nn.Module):
 
     #: Training route of ``density`` when only the parameters want gradients: True = fused HIP backward
     #: (``_DeformTrainFn``); the input-gradient / second-order route always goes through the hash-grid autograd Function.
+    #: Also selects ``field_loss``'s route for stage 2's configuration (``_FieldLossFn``).
     fused_backward = True
 
     def _density_fused(self, x, order=None, enc_out=None, n_device=None, compute_dtype=None):
@@ -243,6 +276,58 @@ class Field(nn.Module):
         view_dirs = view_dirs / torch.norm(view_dirs, dim=1, keepdim=True)
         return torch.abs(torch.maximum(weights.detach(), weights_rev.detach())
                          - torch.abs(torch.sum(field_norm * view_dirs.detach(), 1))).mean()
+
+    @property
+    def quadrature_kernel(self) -> bool:
+        """True for stage 2's configuration (elu, hidden 16, ``back_prop`` false), which qf_field_quadrature_loss
+        serves: ``field_loss`` with a fused backward and ``value_and_grad``."""
+        return self.nl == "elu" and self.hidden_size == 16 and not self.back_prop
+
+    def _quadrature_call(self, x, dirs=None, weights=None, weights_rev=None, upstream=None, loss=None, value=None,
+                         grad=None, d_enc=None, grads=None, workspace=None):
+        """qf_field_quadrature_loss on contiguous fp32 tensors (None -> NULL); the training routes are fp32."""
+        p = _C.ptr
+        _C.check(_C.lib().qf_field_quadrature_loss(
+            self.xyz_encoder.grid.desc, p(_C.f32c(self.xyz_encoder.params.detach())), float(self.scale),
+            self.hidden_size, self.activation_code, *[p(t) for t in self.decoder_arrays()], p(x), p(dirs), p(weights),
+            p(weights_rev), x.shape[0], p(upstream), p(loss, torch.float64), p(value), p(grad), p(d_enc),
+            *([p(t) for t in grads] if grads is not None else [None] * 5), p(workspace, torch.uint8),
+            0 if workspace is None else workspace.numel(), _C.stream()), "qf_field_quadrature_loss")
+
+    def _quadrature_loss(self, x, dirs, weights, weights_rev):
+        """The loss alone, as a 0-d fp32 tensor (summed in fp64 on the device, rounded once)."""
+        loss = torch.empty((1,), dtype=torch.float64, device=x.device)
+        ws = torch.empty((_C.FIELD_LOSS_WORKSPACE_BYTES,), dtype=torch.uint8, device=x.device)
+        self._quadrature_call(x, dirs, weights, weights_rev, loss=loss, workspace=ws)
+        return loss[0].to(torch.float32)
+
+    def field_loss(self, positions, weights, weights_rev, view_dirs):
+        """``compute_field_loss(weights, weights_rev, self(positions)[1], view_dirs)`` (train_field.py:346-350) as one
+        call (extension).  For stage 2's configuration with ``fused_backward`` it is one fused launch forward and one
+        backward (qf_field_quadrature_loss) plus the table scatter; otherwise exactly that expression on the
+        differentiable route.  ``positions`` is data: it gets no gradient on the fused route."""
+        if not (self.quadrature_kernel and self.fused_backward):
+            return self.compute_field_loss(weights, weights_rev, self(positions)[1], view_dirs)
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            d = self.decoder_field
+            return _FieldLossFn.apply(self.xyz_encoder.params, d.layers[0].weight, d.layers[0].bias, d.layers[1].weight,
+                                      d.layers[1].bias, d.lout.weight, self, positions, view_dirs, weights, weights_rev)
+        return self._quadrature_loss(_C.f32c(positions.detach().reshape(-1, 3)), _C.f32c(view_dirs.detach().reshape(-1, 3)),
+                                     _C.f32c(weights.detach().reshape(-1)), _C.f32c(weights_rev.detach().reshape(-1)))
+
+    def value_and_grad(self, x):
+        """(field [N,1], d field / dx [N,3]) for inspection and plotting (extension, inference only: nothing is
+        recorded).  Stage 2's configuration: one launch of qf_field_quadrature_loss with these two outputs; any other:
+        ``forward(return_grad=True)``, detached."""
+        if not self.quadrature_kernel:
+            with torch.enable_grad():
+                value, grad = self(x.detach().clone())
+            return value.detach(), grad.detach()
+        x = _C.f32c(x.detach().reshape(-1, 3))
+        value = torch.empty((x.shape[0],), dtype=torch.float32, device=x.device)
+        grad = torch.empty((x.shape[0], 3), dtype=torch.float32, device=x.device)
+        self._quadrature_call(x, value=value, grad=grad)
+        return value[:, None], grad
 
     def compute_abs_loss(self, field_norm):
         """field.py:261-264."""
