@@ -1073,6 +1073,38 @@ int qf_texture_shade_points(const uint8_t *records, int32_t texture_size, int32_
                             const int64_t *n_device, float *rgb, float *sigma, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Baking the texture set (stage 6c, bake_texture_images_shelly.py:270-294) as a fixed launch sequence per band of rows
+ * of the texel-position map V [T, T, 3] fp32: compact, the caller's two field launches bounded by the device count,
+ * encode.  Nothing here waits for the device and no launch depends on how many texels are valid.
+ *
+ * qf_bake_compact_texels handles the rows [row_begin, row_begin + rows) of V.  A texel is valid iff (x + y) + z != 0
+ * in fp32, in that order (numpy's V.sum(-1) == 0: (1, 1e8, -1e8) and (1, -1, 0) are EMPTY -- the reference's rule,
+ * restated).  It writes texel [<= rows*T] int32: the flat indices r * T + c of the valid texels in ascending order;
+ * positions [<= rows*T, 3]: their rows of V, contiguous; *count (device int64): how many; and, unless mask is NULL, the
+ * band's part of mask [T, T] (one byte per texel, 0 or 1).  Entries of texel / positions past *count are not written.
+ * Deterministic: counts per workgroup, then offsets from them -- no atomics.  workspace: device memory of
+ * qf_bake_compact_workspace_bytes(rows * T) bytes (-1: invalid size).  T <= 16384.
+ *
+ * qf_bake_encode_texels quantises min(*n_device, capacity) feature rows with the codecs of FeatureCompression.compress
+ * (texture_utils.py:67-98, ngp.py:239-273) and writes row i's 4 + 6L codes into the planes of tex (which it WRITES, the
+ * const of the struct notwithstanding) at texel[i]; no other byte is touched.  features [capacity, 3+7L+1] =
+ * [diffuse3 | (axis3, lambda, colour3)*L | ignored], sigma [capacity].  Every operation is one fp32 operation rounded
+ * on its own, python scalars rounded to fp32 first:
+ *   alpha = u8(clip((1 - exp(-sigma * 0.005)) * 255, 0, 255));
+ *   colour(x) = u8(((clip(x, -12, 12) + 12) / 2 / 12) * 255), or u8(sigmoid(x) * 255) when tex->sigmoid_codec;
+ *   lambda_axis = (u8(255 * clamp((log(clamp(|lambda|, 1e-5, inf)) + 2.5) / lambda_thres, 0, 1)),
+ *                  u8(atan2(v.y, v.x) * 128 / pi + 128), u8(acos(v.z) * 256 / pi)), v = axis / (|axis| + 1e-6);
+ *   u8 truncates toward zero and wraps mod 256 (azimuth 256 -> 0; the decoder treats 0 and 255 as neighbours).
+ * NaN features or densities are the caller's problem.  An index outside [0, T*T) is skipped.               */
+int64_t qf_bake_compact_workspace_bytes(int64_t n_texels);
+int qf_bake_compact_texels(const float *v, int32_t texture_size, int32_t row_begin, int32_t rows, int32_t *texel,
+                           float *positions, int64_t *count, uint8_t *mask /* or NULL */, void *workspace,
+                           int64_t workspace_bytes, void *stream);
+int qf_bake_encode_texels(const qf_texture_set *tex /* host */, const float *features, int32_t feature_width,
+                          const float *sigma, const int32_t *texel, int64_t capacity, const int64_t *n_device,
+                          void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Frame metrics: the tail of the reference's evaluation loops (train_finetune.py:620-667) without a host wait.
  *
  * qf_frame_score scores ONE frame into ONE slot of a device-resident table [capacity, 4] of fp64 records

@@ -191,6 +191,9 @@ _SIGNATURES = {
     "qf_texture_pack": (c_int, [POINTER(TextureSet), _P, _P]),
     "qf_texture_shade_packed": (c_int, [_P, c_int32, c_int32, c_int32, c_float, _P, _P, c_int64, _P, _P, _P]),
     "qf_texture_shade_points": (c_int, [_P, c_int32, c_int32, c_int32, c_float, _P, _P, _P, _P, _P, c_int64, _P, _P, _P, _P]),
+    "qf_bake_compact_workspace_bytes": (c_int64, [c_int64]),
+    "qf_bake_compact_texels": (c_int, [_P, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, c_int64, _P]),
+    "qf_bake_encode_texels": (c_int, [POINTER(TextureSet), _P, c_int32, _P, _P, c_int64, _P, _P]),
     "qf_frame_score_scratch_bytes": (c_int64, [c_int32, c_int32]),
     "qf_frame_score": (c_int, [_P, c_int32, c_int32, _P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, c_int64, c_int64, _P,
                                c_int64, _P]),

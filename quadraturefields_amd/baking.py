@@ -3,11 +3,16 @@
 * ``bake_texture_images``: ``examples/bake_texture_images_shelly.py:270-294`` -- evaluate the SG field's features
   and the density field at every valid texel of ``V`` (texel -> 3-D point, all-zero rows are empty), quantise with
   the reference's codecs and scatter into the uint8 texture set.
+* ``bake_texture_set``: the same stage as a fixed launch sequence per band of rows of a device ``V`` -- compact the
+  valid texels, the two field launches bounded by the device count, one encode launch into the planes -- without a
+  host wait (``qf_bake_compact_texels`` / ``qf_bake_encode_texels``).
 * ``texel_positions``: the texel-position map ``V`` itself from a UV-mapped mesh -- the fill of the reference's UV stage
   (``examples/parameterization_utils.py:97-153``), one HIP call (``qf_texel_positions``).
 * ``triangle_max_weights`` / ``prune_faces``: ``examples/prune_mesh_after_finetuning.py:323-373`` -- per-triangle
   maximum compositing weight over the training views, faces below 1e-3 dropped.
 """
+import ctypes
+
 import numpy as np
 import torch
 
@@ -98,6 +103,76 @@ def _bake_device(radiance_field_sg, radiance_field, V, compressor, batch_size):
         features[..., -1] = density.flatten()
         compressor.load_features_into_maps(features, rows)
     return mask
+
+
+def bake_chunk_rows(texture_size: int, num_lobes: int, workspace_bytes: int = 256 << 20) -> int:
+    """Rows of a ``[T, T, 3]`` map that ``bake_texture_set`` takes per band so that the band's buffers -- per texel an
+    int32 index, a position (3 floats), a feature row (3 + 7L + 1 floats) and a density -- fit in ``workspace_bytes``;
+    at least 1, at most T.  ValueError when a single row does not fit."""
+    t, lobes = int(texture_size), int(num_lobes)
+    if t < 1 or lobes < 1:
+        raise ValueError(f"texture_size and num_lobes must be positive, got {texture_size!r}, {num_lobes!r}")
+    row_bytes = t * (4 + 12 + 4 * (3 + 7 * lobes + 1) + 4)
+    rows = int(workspace_bytes) // row_bytes
+    if rows < 1:
+        raise ValueError(f"one row of a {t} x {t} map with {lobes} lobes needs {row_bytes} bytes, "
+                         f"workspace_bytes is {workspace_bytes}")
+    return min(rows, t)
+
+
+@torch.no_grad()
+def bake_texture_set(radiance_field_sg, radiance_field, V, compressor, rows_per_chunk: int = None):
+    """Fill ``compressor``'s texture maps in place from a device texel-position map ``V`` [T, T, 3] (fp32): returns
+    ``(mask, count)``, the device bool [T, T] texel mask ((x + y) + z != 0 in fp32) and a device int64 with the number of
+    valid texels.  The map is taken in ``ceil(T / rows_per_chunk)`` bands of rows (default: ``bake_chunk_rows``), each a
+    fixed sequence of launches -- compact the band's valid texels, the SG field's features and the other field's
+    density on them (both bounded by the count in device memory), encode into the planes -- so nothing here waits for
+    the device and the sequence depends only on T and ``rows_per_chunk``, never on how many texels are valid."""
+    if not isinstance(V, torch.Tensor) or V.dim() != 3 or V.shape[0] != V.shape[1] or V.shape[2] != 3:
+        raise ValueError(f"V must be a [T, T, 3] tensor, got {list(getattr(V, 'shape', []))}")
+    t = int(V.shape[0])
+    if t != compressor.texture_size:
+        raise ValueError(f"V is {t} x {t}, the texture set is {compressor.texture_size} x {compressor.texture_size}")
+    lobes = int(radiance_field_sg.num_g_lobes)
+    if lobes != compressor.num_lobes:
+        raise ValueError(f"the field has {lobes} lobes, the texture set {compressor.num_lobes}")
+    if rows_per_chunk is None:
+        rows_per_chunk = bake_chunk_rows(t, lobes)
+    if isinstance(rows_per_chunk, bool) or not isinstance(rows_per_chunk, (int, np.integer)) or rows_per_chunk < 1:
+        raise ValueError(f"rows_per_chunk must be an integer >= 1, got {rows_per_chunk!r}")
+    if t > MAX_TEXTURE_SIDE:
+        raise ValueError(f"texture size must be at most {MAX_TEXTURE_SIDE}, got {t}")
+    if not V.is_cuda or V.dtype != torch.float32:
+        raise ValueError("V must be a float32 tensor on the device (texel_positions' output)")
+    if V.device != compressor.device:
+        raise ValueError(f"V is on {V.device}, the texture set on {compressor.device}")
+    rows_per_chunk = min(int(rows_per_chunk), t)
+    dev = V.device
+    V = V.contiguous()
+    lib = _C.lib()
+    cap = rows_per_chunk * t
+    ws_bytes = int(lib.qf_bake_compact_workspace_bytes(cap))
+    texel = torch.empty((cap,), dtype=torch.int32, device=dev)
+    points = torch.empty((cap, 3), dtype=torch.float32, device=dev)
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    counts = torch.empty((-(-t // rows_per_chunk),), dtype=torch.int64, device=dev)
+    mask = torch.empty((t, t), dtype=torch.bool, device=dev)
+    width = 3 + 7 * lobes + 1
+    with torch.cuda.device(dev):
+        tex = compressor.texture_set()
+        for band, row in enumerate(range(0, t, rows_per_chunk)):
+            rows = min(rows_per_chunk, t - row)
+            n_dev = counts[band:band + 1]
+            _C.check(lib.qf_bake_compact_texels(_C.ptr(V), t, row, rows, _C.ptr(texel), _C.ptr(points), _C.ptr(n_dev),
+                                                _C.ptr(mask), _C.ptr(ws), ws_bytes, _C.stream()), "qf_bake_compact_texels")
+            pts = points[:rows * t]
+            features = radiance_field_sg.features(pts, n_device=n_dev)
+            density = radiance_field.query_density(pts, n_device=n_dev)
+            _C.check(lib.qf_bake_encode_texels(ctypes.byref(tex), _C.ptr(features), width, _C.ptr(density.reshape(-1)),
+                                               _C.ptr(texel), rows * t, _C.ptr(n_dev), _C.stream()),
+                     "qf_bake_encode_texels")
+    compressor._records = None            # the planes changed behind torch's version counters: rebuild on next use
+    return mask, counts.sum()
 
 
 def triangle_max_weights(weights: torch.Tensor, index_tri: torch.Tensor, out: torch.Tensor) -> torch.Tensor:

@@ -272,14 +272,16 @@ class _FusedFieldBase(nn.Module):
         density = trunc_exp(raw - 1.0) * selector.reshape(-1, 1)
         return density, feat
 
-    def query_density(self, x, return_feat: bool = False):
-        """density = trunc_exp(raw - 1) * selector, [..,1] (+ the 15 geometry features).  ngp.py:757-779."""
+    def query_density(self, x, return_feat: bool = False, n_device: torch.Tensor = None):
+        """density = trunc_exp(raw - 1) * selector, [..,1] (+ the 15 geometry features).  ngp.py:757-779.
+        ``n_device`` (extension, inference only): see ``NGPRadianceField.forward``."""
         lead = list(x.shape[:-1])
         if self._recording(x):
             density, feat = self._query_density_train(x)
             density = density.reshape(lead + [1])
             return (density, feat.reshape(lead + [self.geo_feat_dim])) if return_feat else density
-        _, sigma, geo, _ = self._launch(_C.HEAD_NONE, 0, x, None, want_sigma=True, want_geo=return_feat)
+        _, sigma, geo, _ = self._launch(_C.HEAD_NONE, 0, x, None, want_sigma=True, want_geo=return_feat,
+                                        n_device=n_device)
         density = sigma.reshape(lead + [1])
         if return_feat:
             return density, geo.reshape(lead + [self.geo_feat_dim])
@@ -553,14 +555,15 @@ class NGPRadianceFieldSGNew(_FusedFieldBase):
             return torch.sigmoid(out[:, :3] + self.spherical_gaussian_mixture(out[:, 3:], dir))
         return self.features_to_rgb(out, dir)
 
-    def features(self, x):
-        """[head(3+7L) | density], ngp.py:445-454."""
+    def features(self, x, n_device: torch.Tensor = None):
+        """[head(3+7L) | density], ngp.py:445-454.  ``n_device`` (extension, inference only): see
+        ``NGPRadianceField.forward``."""
         width = 3 + 7 * self.num_g_lobes + 1
         if self._recording(x):
             density, feat = self._query_density_train(x)
             return torch.cat([self.mlp_head(feat), density], dim=-1)
         _, _, _, feats = self._launch(_C.HEAD_SG_FEATURES, self.num_g_lobes, x, None, want_features=width,
-                                      head_sg=self._sg_params())
+                                      head_sg=self._sg_params(), n_device=n_device)
         return feats
 
     def features_to_rgb(self, features, dir):
