@@ -30,6 +30,8 @@ def main(argv=None):
     ap.add_argument("--shells", type=int, default=12)
     ap.add_argument("--subdivisions", type=int, default=6)
     ap.add_argument("--log2_hashmap_size", type=int, default=19)
+    ap.add_argument("--bvh_builder", choices=("host", "device"), default="host",
+                    help="where the ray-mesh BVH is built: host (binned SAH) or device (linear BVH on the GPU: faster build, slower traversal)")
     args = ap.parse_args(argv)
 
     from quadraturefields_amd import synthetic
@@ -45,7 +47,8 @@ def main(argv=None):
     scorer = FrameScorer(size, size, up_sample=args.up_sample, capacity=args.views, device=device)
     f = scorer.factor
     mesh = synthetic.shell_mesh(n_shells=args.shells, subdivisions=args.subdivisions)
-    mi = MeshIntersection(mesh, simplify_mesh=False, scale=1.0, num_intersections=25, render_step_size=5e-3, device=device)
+    mi = MeshIntersection(mesh, simplify_mesh=False, scale=1.0, num_intersections=25, render_step_size=5e-3, device=device,
+                          bvh_builder=args.bvh_builder)
 
     def field_of(perturbed):
         field = NGPRadianceField(aabb=[-1.5] * 3 + [1.5] * 3, log2_hashmap_size=log2_t)

@@ -31,6 +31,8 @@ def parse(argv):
     ap.add_argument("--ckpt_path", "--ckpt", dest="ckpt_path", type=str, default="")
     ap.add_argument("--mesh_path", type=str, default="")
     ap.add_argument("--max_hits", type=int, default=10)
+    ap.add_argument("--bvh_builder", choices=("host", "device"), default="host",
+                    help="where the ray-mesh BVH is built: host (binned SAH) or device (linear BVH on the GPU: faster build, slower traversal)")
     ap.add_argument("--up_sample", type=float, default=1.0)
     ap.add_argument("--log2_hashmap_size", type=int, default=19)
     ap.add_argument("--scale", type=float, default=1.5)
@@ -102,7 +104,7 @@ def main(argv=None):
             sys.exit("prune_mesh_after_finetuning.py: --mesh_path and --ckpt_path are required (or --synthetic OUT)")
         mesh_path, field, views = dataset_views(args, device)
     mi = MeshIntersection(mesh_path, simplify_mesh=False, scale=1.0, num_intersections=args.max_hits,
-                          render_step_size=5e-3, device=device)
+                          render_step_size=5e-3, device=device, bvh_builder=args.bvh_builder)
     pruner = MeshPruner(mi, field.to(device).eval())
     for origins, viewdirs, camera in views:
         pruner.add_view(origins, viewdirs, camera)

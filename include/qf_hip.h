@@ -417,6 +417,21 @@ int qf_bvh_create(const float *tri_verts /* host */, int64_t n_tri, qf_bvh **out
  * (qf_bvh_create uses 32).  Any value gives a valid tree and identical hits; small values trade traversal speed for
  * a shallower tree -- used by the tests to exercise the depth bound.                            */
 int qf_bvh_create_ex(const float *tri_verts /* host */, int64_t n_tri, int32_t sah_depth, qf_bvh **out);
+/* The same 8-wide tree built ON THE DEVICE from device triangles: Morton-sorted centroids split by range straight into
+ * wide nodes, level by level; no binary tree (qf_bvh_num_nodes is 0, qf_bvh_copy_nodes copies
+ * nothing, qf_bvh_max_depth is the number of wide levels).  Every entry that takes a qf_bvh works on the handle.
+ * d_tri_verts: DEVICE pointer, [n_tri][3][3] fp32.  Work is issued on `stream`; the call waits on that stream only and
+ * returns a complete handle (the input may be freed); it allocates the tree and its temporary memory with hipMalloc and
+ * frees the latter before it returns.  Non-finite vertices, n_tri >= 2^28, null input with n_tri > 0:
+ * QF_ERR_INVALID_ARGUMENT.  The host copies (qf_bvh_copy_wide_nodes) and the host refit (qf_bvh_refit) download the wide
+ * tree the first time they are used.  A tree built this way traverses more slowly than the SAH tree of qf_bvh_create and builds
+ * far faster (profiles/bvh_build).                                                              */
+int qf_bvh_create_device(const float *d_tri_verts, int64_t n_tri, void *stream, qf_bvh **out);
+/* The same build, measured: pass_ms_host (NULL or 7 floats) receives the HIP-event time of each pass -- reduce, keys, sort,
+ * gather, levels, boxes, stack bound -- and *peak_bytes_host (NULL allowed) the device memory the build holds at its
+ * peak, the returned tree included.                                                              */
+int qf_bvh_create_device_timed(const float *d_tri_verts, int64_t n_tri, void *stream, float *pass_ms_host,
+                               int64_t *peak_bytes_host, qf_bvh **out);
 /* Same topology, new vertex positions (Intersector.update_vertices / train_finetune.py:716-718), HOST vertices.
  * Waits for the device (hipDeviceSynchronize) before the upload, so no traversal still reads the old tree.   */
 int qf_bvh_refit(qf_bvh *bvh, const float *tri_verts /* host */, int64_t n_tri);
@@ -430,8 +445,15 @@ int64_t qf_bvh_num_triangles(const qf_bvh *bvh);
 int64_t qf_bvh_num_nodes(const qf_bvh *bvh);        /* binary build tree */
 int64_t qf_bvh_num_wide_nodes(const qf_bvh *bvh);   /* the 8-wide tree that is traversed */
 /* Depth of the deepest inner node of the binary tree (root = 1).  The builder guarantees <= 64 for any input: below
- * level 32 it halves the index range instead of taking the SAH split.                            */
+ * level 32 it halves the index range instead of taking the SAH split.  A handle of qf_bvh_create_device has no binary
+ * tree: the number of levels of its wide tree (<= 96).                                           */
 int32_t qf_bvh_max_depth(const qf_bvh *bvh);
+/* 2 area(mesh) / area(bounding box) of the build-time vertices in fp64: the mean number of crossings of a random line
+ * through the box, which picks the traversal's visiting order.                                    */
+double qf_bvh_depth_complexity(const qf_bvh *bvh);
+/* First node of every level of the wide tree, then the node count: up to `capacity` of the levels + 1 entries are
+ * written; returns levels + 1 (0 for an empty tree).                                              */
+int64_t qf_bvh_copy_level_starts(const qf_bvh *bvh, int32_t *starts_host, int64_t capacity);
 /* Exact bound of the wide traversal's per-ray stack for this tree (entries); the LDS stack is sized by it. */
 int32_t qf_bvh_max_stack(const qf_bvh *bvh);
 /* Host copies for inspection/tests: binary nodes as 16 floats each, wide nodes as 64 floats each (csrc/bvh.h),

@@ -120,6 +120,10 @@ _SIGNATURES = {
     "qf_distortion_loss": (c_int, [_P, _P, _P, c_float, _P, c_int64, c_int64, c_int64, _P, _P, _P, _P]),
     "qf_bvh_create": (c_int, [_P, c_int64, POINTER(c_void_p)]),
     "qf_bvh_create_ex": (c_int, [_P, c_int64, c_int32, POINTER(c_void_p)]),
+    "qf_bvh_create_device": (c_int, [_P, c_int64, _P, POINTER(c_void_p)]),
+    "qf_bvh_create_device_timed": (c_int, [_P, c_int64, _P, _P, _P, POINTER(c_void_p)]),
+    "qf_bvh_depth_complexity": (c_double, [_P]),
+    "qf_bvh_copy_level_starts": (c_int64, [_P, _P, c_int64]),
     "qf_bvh_refit": (c_int, [_P, _P, c_int64]),
     "qf_bvh_refit_device": (c_int, [_P, _P, c_int64, _P]),
     "qf_bvh_num_wide_nodes": (c_int64, [_P]),

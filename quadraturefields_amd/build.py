@@ -19,7 +19,8 @@ ARCH = "gfx950"
 # (source, extra flags).  No FMA contraction in the index-exact stages (exact_common.h: bvh_traverse, raster, sample_pack,
 # texture, grid_march and volumetric carry every integer-deciding comparison), bake.hip (the fp32 codecs), texel_fill.hip (the fp64 rules of the texel-position
 # map), marching_cubes.hip (the fp32 vertex rule and the fp64 face decider), vertex_clustering.hip (the fp64 cell, mean
-# and quadric rules) and uv_atlas.hip (the fp64 measure, class and corner rules).
+# and quadric rules), uv_atlas.hip (the fp64 measure, class and corner rules) and bvh_build_device.hip (the fp32 Morton
+# keys of the device BVH build).
 SOURCES = [
     ("field_eval.hip", []),
     ("field_eval_bf16.hip", []),
@@ -43,6 +44,7 @@ SOURCES = [
     ("marching_cubes.hip", ["-ffp-contract=off"]),
     ("vertex_clustering.hip", ["-ffp-contract=off"]),
     ("uv_atlas.hip", ["-ffp-contract=off"]),
+    ("bvh_build_device.hip", ["-ffp-contract=off"]),
     ("bvh_build.cpp", ["-x", "hip"]),
     ("misc.cpp", ["-x", "hip"]),
     ("frame.cpp", ["-x", "hip"]),

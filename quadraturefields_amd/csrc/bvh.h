@@ -2,6 +2,8 @@
 #pragma once
 #include <stdint.h>
 
+#include <algorithm>
+#include <cmath>
 #include <vector>
 
 #define QF_BVH_MAX_HITS 64
@@ -30,6 +32,8 @@
 // refit is one launch per level, bottom-up.
 // Triangle = 3 x float4 in leaf order: (v0.xyz, original id bits), (v1.xyz, 0), (v2.xyz, 0).
 #define QF_BVH8_EMPTY ((int32_t)0x80000000)
+// Passes of the device build whose times qf_bvh_create_device_timed reports (bvh_build_device.hip)
+#define QF_BVH_BUILD_PASSES 7
 
 struct qf_bvh {
     float *d_nodes8 = nullptr;
@@ -58,8 +62,30 @@ struct qf_bvh {
     // the build-time vertices: with fewer than max_hits / 2 the K-lists (almost) never fill and the general traversal
     // visits the hit children in ANY order (bvh_traverse.hip, bvh_launch)
     float depth_complexity = 0.f;
+    double depth_complexity64 = 0.0; // the same quotient before its rounding to fp32 (qf_bvh_depth_complexity)
+    // false on a handle of qf_bvh_create_device until the wide nodes are first asked for on the host (inspection, host
+    // refit): the device build keeps no binary tree (h_nodes empty, n_nodes 0) and downloads the wide tree on demand
+    bool nodes8_mirrored = true;
     std::vector<float> h_nodes;      // binary tree (build, host refit, inspection)
     std::vector<float> h_nodes8;     // wide tree mirror
     std::vector<int32_t> level_start8;   // [levels + 1]
     std::vector<int32_t> h_tri_ids;  // leaf order -> original triangle id
 };
+
+// Box inflation of a build or host refit from the bounds of all vertices (bvh_build.cpp: scene_eps)
+static inline float qf_bvh_eps_from_bounds(const float lo[3], const float hi[3])
+{
+    float ext = 0.f, mag = 0.f;
+    for (int k = 0; k < 3; ++k) {
+        ext = std::max(ext, hi[k] - lo[k]);
+        mag = std::max(mag, std::max(std::fabs(lo[k]), std::fabs(hi[k])));
+    }
+    if (!(ext >= 0.f) || !std::isfinite(ext)) ext = 0.f;
+    return 2e-5f * std::max(ext, mag) + 1e-30f;
+}
+
+// Every child box of the wide tree again from d_tris, bottom-up with one refit_level_kernel launch per level, on
+// `stream` (bvh_build.cpp): leaf child = its triangles' box +- eps, inner child = union of the child node's boxes.
+int qf_bvh_refit_boxes(qf_bvh *bvh, float eps, void *stream);
+// Fills h_nodes8 of a device-built handle from the device (waits for the device); no-op otherwise (bvh_build.cpp).
+int qf_bvh_mirror_nodes(const qf_bvh *bvh);

@@ -133,13 +133,7 @@ float scene_eps(const float *tri_verts, int64_t n_tri)
     Box all;
     all.reset();
     for (int64_t i = 0; i < n_tri * 3; ++i) all.grow(tri_verts + 3 * i);
-    float ext = 0.f, mag = 0.f;
-    for (int k = 0; k < 3; ++k) {
-        ext = std::max(ext, all.hi[k] - all.lo[k]);
-        mag = std::max(mag, std::max(std::fabs(all.lo[k]), std::fabs(all.hi[k])));
-    }
-    if (!(ext >= 0.f) || !std::isfinite(ext)) ext = 0.f;
-    return 2e-5f * std::max(ext, mag) + 1e-30f;
+    return qf_bvh_eps_from_bounds(all.lo, all.hi);
 }
 
 int upload(qf_bvh *bvh, const float *tri_verts)
@@ -479,7 +473,8 @@ extern "C" int qf_bvh_create_ex(const float *tri_verts, int64_t n_tri, int32_t s
         }
         const double ex = hi[0] - lo[0], ey = hi[1] - lo[1], ez = hi[2] - lo[2];
         const double box = n_tri > 0 ? 2.0 * (ex * ey + ey * ez + ex * ez) : 0.0;
-        bvh->depth_complexity = box > 0.0 ? (float)(2.0 * area / box) : 0.f;
+        bvh->depth_complexity64 = box > 0.0 ? 2.0 * area / box : 0.0;
+        bvh->depth_complexity = (float)bvh->depth_complexity64;
     }
     if (bvh->max_depth > QF_BVH_MAX_DEPTH) { qf_bvh_destroy(bvh); return QF_ERR_UNSUPPORTED; }   // cannot happen, see bvh.h
     int rc = collapse8(bvh);
@@ -489,7 +484,43 @@ extern "C" int qf_bvh_create_ex(const float *tri_verts, int64_t n_tri, int32_t s
     return QF_OK;
 }
 
+int qf_bvh_refit_boxes(qf_bvh *bvh, float eps, void *stream)
+{
+    hipStream_t st = qf_stream(stream);
+    const int levels = (int)bvh->level_start8.size() - 1;
+    for (int l = levels - 1; l >= 0; --l) {
+        const int n0 = bvh->level_start8[(size_t)l], n1 = bvh->level_start8[(size_t)l + 1];
+        if (n1 <= n0) continue;
+        const int64_t threads = (int64_t)(n1 - n0) * 8;
+        hipLaunchKernelGGL(refit_level_kernel, dim3((unsigned)qf_div_up(threads, 256)), dim3(256), 0, st, bvh->d_nodes8,
+                           reinterpret_cast<const float4 *>(bvh->d_tris), n0, n1, eps);
+        QF_LAUNCH_CHECK();
+    }
+    return QF_OK;
+}
+
+int qf_bvh_mirror_nodes(const qf_bvh *cbvh)
+{
+    if (cbvh->nodes8_mirrored) return QF_OK;
+    qf_bvh *bvh = const_cast<qf_bvh *>(cbvh);      // the mirror is a cache: filling it does not change the tree
+    QF_HIP_TRY(hipDeviceSynchronize());            // a device refit may be in flight on a non-blocking stream
+    bvh->h_nodes8.resize((size_t)bvh->n_nodes8 * 64);
+    if (bvh->n_nodes8 > 0)
+        QF_HIP_TRY(hipMemcpy(bvh->h_nodes8.data(), bvh->d_nodes8, bvh->h_nodes8.size() * sizeof(float), hipMemcpyDeviceToHost));
+    bvh->nodes8_mirrored = true;
+    return QF_OK;
+}
+
 extern "C" int32_t qf_bvh_max_depth(const qf_bvh *bvh) { return bvh ? bvh->max_depth : -1; }
+extern "C" double qf_bvh_depth_complexity(const qf_bvh *bvh) { return bvh ? bvh->depth_complexity64 : -1.0; }
+
+extern "C" int64_t qf_bvh_copy_level_starts(const qf_bvh *bvh, int32_t *starts_host, int64_t capacity)
+{
+    if (!bvh || (capacity > 0 && !starts_host)) return QF_ERR_INVALID_ARGUMENT;
+    const int64_t n = (int64_t)bvh->level_start8.size();
+    for (int64_t i = 0; i < n && i < capacity; ++i) starts_host[i] = bvh->level_start8[(size_t)i];
+    return n;
+}
 extern "C" int32_t qf_bvh_max_stack(const qf_bvh *bvh) { return bvh ? bvh->max_stack8 : -1; }
 extern "C" int64_t qf_bvh_num_wide_nodes(const qf_bvh *bvh) { return bvh ? bvh->n_nodes8 : -1; }
 
@@ -506,6 +537,7 @@ extern "C" int qf_bvh_refit(qf_bvh *bvh, const float *tri_verts, int64_t n_tri)
 {
     if (!bvh || n_tri != bvh->n_tri || (n_tri > 0 && !tri_verts)) return QF_ERR_INVALID_ARGUMENT;
     if (n_tri == 0) return QF_OK;
+    if (int rc = qf_bvh_mirror_nodes(bvh)) return rc;      // a device-built handle: the wide tree comes down first
     refit_host(bvh, tri_verts);
     refit8_host(bvh, tri_verts);
     return upload(bvh, tri_verts);      // waits for the device first: no traversal may still be reading the old tree
@@ -519,15 +551,7 @@ extern "C" int qf_bvh_refit_device(qf_bvh *bvh, const float *d_tri_verts, int64_
     hipLaunchKernelGGL(refit_tris_kernel, dim3(qf_grid_1d(n_tri, 256)), dim3(256), 0, st,
                        reinterpret_cast<float4 *>(bvh->d_tris), d_tri_verts, n_tri);
     QF_LAUNCH_CHECK();
-    const int levels = (int)bvh->level_start8.size() - 1;
-    for (int l = levels - 1; l >= 0; --l) {
-        const int n0 = bvh->level_start8[(size_t)l], n1 = bvh->level_start8[(size_t)l + 1];
-        if (n1 <= n0) continue;
-        const int64_t threads = (int64_t)(n1 - n0) * 8;
-        hipLaunchKernelGGL(refit_level_kernel, dim3((unsigned)qf_div_up(threads, 256)), dim3(256), 0, st, bvh->d_nodes8,
-                           reinterpret_cast<const float4 *>(bvh->d_tris), n0, n1, bvh->eps * 1.25f);
-        QF_LAUNCH_CHECK();
-    }
+    if (int rc = qf_bvh_refit_boxes(bvh, bvh->eps * 1.25f, stream)) return rc;
     bvh->chunk_dirty = true;
     // eps was sized from the extent at build / host-refit time; 1.25x covers the bounded vertex motion of training.
     // The host mirrors (h_nodes, h_nodes8) are NOT updated: inspection copies show the build state.
@@ -568,6 +592,7 @@ extern "C" int qf_bvh_copy_tri_ids(const qf_bvh *bvh, int32_t *ids_host, int64_t
 extern "C" int qf_bvh_copy_wide_nodes(const qf_bvh *bvh, float *nodes_host, int64_t capacity_nodes)
 {
     if (!bvh || !nodes_host || capacity_nodes < bvh->n_nodes8) return QF_ERR_INVALID_ARGUMENT;
+    if (int rc = qf_bvh_mirror_nodes(bvh)) return rc;
     std::memcpy(nodes_host, bvh->h_nodes8.data(), (size_t)bvh->n_nodes8 * 64 * sizeof(float));
     return QF_OK;
 }

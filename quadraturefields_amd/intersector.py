@@ -15,6 +15,7 @@ defaults to 0 here -- every hit counts -- and can be set to the trimesh rule of 
     from quadraturefields_amd import intersector          # instead of: from build.lib import intersector
 """
 import numpy as np
+import torch
 
 from .mesh_io import TriMesh
 from .mesh_utils import RayIntersector
@@ -22,7 +23,11 @@ from .mesh_utils import RayIntersector
 
 class Intersector:
     def __init__(self, vertices, max_hits: int, device: int = 0, min_separation=0.0):
-        tri = np.ascontiguousarray(np.asarray(vertices, dtype=np.float32).reshape(-1))
+        # a device tensor takes the device build (qf_bvh_create_device): the tree never visits the host; only TriMesh's
+        # own copy of the vertices does
+        on_device = isinstance(vertices, torch.Tensor) and vertices.is_cuda
+        host = vertices.detach().cpu().numpy() if isinstance(vertices, torch.Tensor) else vertices
+        tri = np.ascontiguousarray(np.asarray(host, dtype=np.float32).reshape(-1))
         if tri.size == 0 or tri.size % 9 != 0:
             raise ValueError("vertices: a flat float array of 9 values per triangle")
         n_tri = tri.size // 9
@@ -30,7 +35,7 @@ class Intersector:
         self.max_hits = int(max_hits)
         self.device = int(device)
         self.core = RayIntersector(mesh, max_hits=self.max_hits, device=f"cuda:{self.device}",
-                                   min_separation=min_separation)
+                                   min_separation=min_separation, builder="device" if on_device else "host")
 
     @property
     def num_triangles(self) -> int:

@@ -154,9 +154,12 @@ class RayIntersector:
     ``trimesh_ray_offset(mesh.vertices)``, a float = that distance, ``0`` / ``None`` = every hit counts."""
 
     def __init__(self, mesh: TriMesh, max_hits: int = 10, device="cuda:0", sah_depth: int = 32,
-                 min_separation="trimesh"):
+                 min_separation="trimesh", builder: str = "host"):
         if max_hits < 1 or max_hits > _C.QF_BVH_MAX_HITS:
             raise ValueError(f"max_hits must be in 1..{_C.QF_BVH_MAX_HITS}")
+        if builder not in ("host", "device"):
+            raise ValueError("builder: 'host' (binned SAH, the default) or 'device' (linear BVH built on the GPU)")
+        self.builder = builder
         self.mesh = mesh
         self.max_hits = int(max_hits)
         self.device = _resolve_device(device)
@@ -206,9 +209,53 @@ class RayIntersector:
         self._handle = ctypes.c_void_p()
         tri = np.ascontiguousarray(mesh.vertices.astype(np.float32)[mesh.faces].reshape(-1, 9))
         with torch.cuda.device(self.device):
-            _C.check(_C.lib().qf_bvh_create_ex(tri.ctypes.data_as(ctypes.c_void_p), tri.shape[0], int(sah_depth),
-                                               ctypes.byref(self._handle)), "qf_bvh_create_ex")
+            if builder == "device":
+                self._handle = self._device_build(torch.from_numpy(tri).to(self.device))
+            else:
+                _C.check(_C.lib().qf_bvh_create_ex(tri.ctypes.data_as(ctypes.c_void_p), tri.shape[0], int(sah_depth),
+                                                   ctypes.byref(self._handle)), "qf_bvh_create_ex")
             _C.check(_C.lib().qf_bvh_set_min_separation(self._handle, self.min_separation), "qf_bvh_set_min_separation")
+
+    def _device_build(self, tri: torch.Tensor) -> ctypes.c_void_p:
+        """A fresh handle from device triangles [F, 9] fp32 (``qf_bvh_create_device``), on the current stream."""
+        handle = ctypes.c_void_p()
+        _C.check(_C.lib().qf_bvh_create_device(_C.ptr(tri, torch.float32), tri.shape[0], _C.stream(), ctypes.byref(handle)),
+                 "qf_bvh_create_device")
+        return handle
+
+    def _triangle_soup(self, vertices) -> torch.Tensor:
+        """``vertices`` ([V,3], or the flattened [F*9] soup; tensor or array) -> device triangles [F, 9] fp32."""
+        n_tri = self.mesh.faces.shape[0]
+        v = vertices.detach() if isinstance(vertices, torch.Tensor) else torch.from_numpy(
+            np.ascontiguousarray(np.asarray(vertices, dtype=np.float32)))
+        v = v.to(device=self.device, dtype=torch.float32)
+        if v.numel() == n_tri * 9 and tuple(v.shape) != tuple(self.mesh.vertices.shape):
+            return v.reshape(-1, 9).contiguous()
+        if getattr(self, "_faces_dev", None) is None:
+            self._faces_dev = torch.from_numpy(np.ascontiguousarray(self.mesh.faces, dtype=np.int64)).to(self.device)
+        return v.reshape(-1, 3)[self._faces_dev].reshape(-1, 9).contiguous()
+
+    def _vertex_extent(self, vertices) -> np.ndarray:
+        """[2,3] fp64 bounds of ``vertices``: two small reductions for a device tensor."""
+        if isinstance(vertices, torch.Tensor):
+            vv = vertices.detach().reshape(-1, 3)
+            return torch.stack([vv.min(dim=0).values, vv.max(dim=0).values]).double().cpu().numpy()
+        vv = np.asarray(vertices, dtype=np.float64).reshape(-1, 3)
+        return np.stack([vv.min(axis=0), vv.max(axis=0)])
+
+    @_on_device
+    def rebuild(self, vertices) -> None:
+        """New vertex positions, same faces, NEW topology: a fresh tree is built on the device
+        (``qf_bvh_create_device``) and swapped in the way the ``inter`` setter does it -- the old handle is destroyed,
+        the separation follows the mesh if it is ``"trimesh"``, the policy state is kept.  ``vertices``: the shapes
+        ``update_intersector`` accepts, device tensor or host array.  A refit (``update_intersector``) keeps the
+        topology of the build, whose boxes loosen as the mesh moves; this replaces it."""
+        new = self._device_build(self._triangle_soup(vertices))
+        old, self._handle = self._handle, new
+        if old is not None and old.value:
+            _C.lib().qf_bvh_destroy(old)
+        self._apply_min_separation(trimesh_ray_offset(self._vertex_extent(vertices)) if self._min_separation_auto
+                                   else self.min_separation)
 
     def __del__(self):
         h = getattr(self, "_handle", None)
@@ -274,21 +321,9 @@ class RayIntersector:
         if self._min_separation_auto:
             # trimesh's re-origin distance is 1e-4 * 100 / (bounding-box diagonal of the mesh it intersects): it moves
             # with the vertices.  Only the extent is needed: two small reductions for a device tensor.
-            if isinstance(vertices, torch.Tensor):
-                vv = vertices.detach().reshape(-1, 3)
-                ext = torch.stack([vv.min(dim=0).values, vv.max(dim=0).values]).double().cpu().numpy()
-            else:
-                vv = np.asarray(vertices, dtype=np.float64).reshape(-1, 3)
-                ext = np.stack([vv.min(axis=0), vv.max(axis=0)])
-            self._apply_min_separation(trimesh_ray_offset(ext))
+            self._apply_min_separation(trimesh_ray_offset(self._vertex_extent(vertices)))
         if isinstance(vertices, torch.Tensor) and vertices.is_cuda:
-            v = vertices.detach().to(device=self.device, dtype=torch.float32)
-            if v.numel() == n_tri * 9 and tuple(v.shape) != tuple(self.mesh.vertices.shape):
-                tri = v.reshape(-1, 9).contiguous()
-            else:
-                if getattr(self, "_faces_dev", None) is None:
-                    self._faces_dev = torch.from_numpy(np.ascontiguousarray(self.mesh.faces, dtype=np.int64)).to(self.device)
-                tri = v.reshape(-1, 3)[self._faces_dev].reshape(-1, 9).contiguous()
+            tri = self._triangle_soup(vertices)
             with torch.cuda.device(self.device):
                 _C.check(_C.lib().qf_bvh_refit_device(self._handle, _C.ptr(tri), n_tri, _C.stream()), "qf_bvh_refit_device")
             return
@@ -1166,7 +1201,8 @@ class MeshIntersection:
     ``TriMesh``.  ``optix`` is accepted and ignored: there is one intersector, the gfx950 BVH."""
 
     def __init__(self, mesh_path, simplify_mesh=True, scale=1.0, num_repeat=16, optix=False, voxel_size=512,
-                 num_intersections=20, render_step_size=0.005, device="cuda:0", min_hit_separation="trimesh"):
+                 num_intersections=20, render_step_size=0.005, device="cuda:0", min_hit_separation="trimesh",
+                 bvh_builder="host"):
         if isinstance(mesh_path, TriMesh):
             self.mesh = TriMesh(mesh_path.vertices.copy(), mesh_path.faces.copy(), mesh_path.visual.uv)
         else:
@@ -1186,8 +1222,9 @@ class MeshIntersection:
         self.vertices = torch.from_numpy(self.mesh.vertices.astype(np.float32)).to(self.device)
         # min_hit_separation: the re-origin distance of the reference's trimesh intersector (default), a distance in
         # world units, or 0 / None to count every hit (``RayIntersector``)
+        # bvh_builder: "host" (binned SAH) or "device" (linear BVH built on the GPU: far faster to build, slower to traverse)
         self.rayintersector = RayIntersector(self.mesh, max_hits=self.num_intersections, device=self.device,
-                                             min_separation=min_hit_separation)
+                                             min_separation=min_hit_separation, builder=bvh_builder)
 
     def find_deltas(self, boundary, depth):
         """Constant step for every sample (mesh_utils.py:225-231; B-4)."""
