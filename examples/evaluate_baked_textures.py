@@ -23,6 +23,9 @@ named, as in the reference; the script's other flags are accepted and unused.
 needs no data set: orbit cameras, and the ground truth of a view is the SG field itself (``--ckpt_path``'s
 ``radiance_field``, or the seeded state ``bake_texture_images.py --synthetic`` bakes) rendered on the same mesh at
 ``up_sample`` 1 -- the score is then exactly what baking costs.
+
+``--early_stop_eps EPS`` (default: not given) renders through the front-to-back route with early ray termination
+ and prints, beside PSNR / SSIM, the share of the views' samples that were shaded.
 """
 import argparse
 import json
@@ -57,6 +60,10 @@ def parse(argv):
     ap.add_argument("--scale", type=float, default=1.5)
     ap.add_argument("--lambda_thres", type=float, default=7.5)
     ap.add_argument("--compression_type", type=str, default="linear")
+    ap.add_argument("--early_stop_eps", type=float, default=None,
+                    help="render front to back in one launch and stop shading a pixel once its transmittance has fallen "
+                         "below this threshold, in [0, 1) (FrameRenderer.render_baked early_stop_eps; a pixel moves by less "
+                         "than 3 eps); not given: every sample is shaded, as in the reference")
     ap.add_argument("--synthetic", action="store_true", help="orbit cameras; ground truth rendered from the SG field")
     ap.add_argument("--size", type=int, default=200, help="--synthetic: ground-truth width and height")
     ap.add_argument("--views", type=int, default=4, help="--synthetic: orbit cameras")
@@ -147,12 +154,17 @@ def main(argv=None):
         field = NGPRadianceField(aabb=[-args.scale] * 3 + [args.scale] * 3, log2_hashmap_size=12).to(device)
         renderer = FrameRenderer(mesh_intersect, field, render_step_size=5e-3)
         scorer = None
+        shaded = samples = 0
         for i, (pixels, origins, viewdirs, camera) in enumerate(views):
             if scorer is None:
                 scorer = FrameScorer(height, width, up_sample=factor, capacity=256, device=device)
             elif len(scorer) == scorer.capacity:
                 raise RuntimeError(f"more than {scorer.capacity} views")
-            rgb, _, depth, _ = renderer.render_baked(origins, viewdirs, uv, compressor, camera=camera)
+            rgb, _, depth, n_samples = renderer.render_baked(origins, viewdirs, uv, compressor, camera=camera,
+                                                             early_stop_eps=args.early_stop_eps)
+            if args.early_stop_eps is not None and n_samples:
+                shaded += int(mesh_intersect.rayintersector.last_frame.shaded_count.sum())
+                samples += n_samples
             scorer.score(rgb, pixels, depth=normalised_depth(depth), images=True)
             rgb8 = scorer.last_images()[0]
             depth8 = (scorer.last_small()[1] * 255).to(torch.uint8)
@@ -165,6 +177,9 @@ def main(argv=None):
         json.dump(out, fh)
     print("before psnr: ", out["psnr"])
     print("before ssim: ", out["ssim"])
+    if args.early_stop_eps is not None:
+        out["shaded_share"] = shaded / max(samples, 1)
+        print(f"samples shaded (early_stop_eps {args.early_stop_eps}): {shaded} of {samples} = {out['shaded_share']:.4f}")
     return out
 
 

@@ -1094,6 +1094,44 @@ int qf_texture_shade_points(const uint8_t *records, int32_t texture_size, int32_
                             const int64_t *index_tri, const int32_t *index_tri32, const float *dirs, int64_t n,
                             const int64_t *n_device, float *rgb, float *sigma, void *stream);
 
+/* The baked-texture frame shaded and composited FRONT TO BACK in one launch, with early ray termination: the walk of
+ * qf_composite_tiles (one wave per 8x8 tile, lane = pixel, step k = the rank-k samples in depth order) in which every
+ * lane shades its own sample -- qf_texture_shade_points' texel lookup, decode and SG shading, the same bits -- instead
+ * of reading rgb_c / sigma_c, so neither array exists.  No reference counterpart (its evaluation shades every sample).
+ * The frame comes in the coherent tile order as qf_pack_tiles / qf_pack_tiles_bins leave it: xyz_c, dirs_c [n,3],
+ * depth_c [n], tri_c [n] int32, hit_count = the kept counts (final_count), tile_base; records / triangle_records and
+ * the four texture parameters as qf_texture_shade_points takes them.  dirs_c is read at a pixel's first slot only (the
+ * pack writes the same bits to all of them).
+ * The rule: the rank-k sample of a pixel (k < min(count, max_hits)) contributes iff the optical depth accumulated before
+ * it satisfies cum <= stop_tau, where cum is the fp32 value the compositor keeps (cum = cum + sigma * delta_const, each
+ * operation rounded on its own).  A sample that does not contribute is not shaded and adds nothing to any sum; a pixel
+ * that has stopped stays stopped; stop_tau = +inf never stops (even at cum = +inf) and then the image equals
+ * qf_texture_shade_points + qf_composite_tiles bit for bit.  stop_tau NaN or negative: QF_ERR_INVALID_ARGUMENT.
+ * Outputs as qf_composite_tiles (three arrays or out_packed [n_rays,5]; pixels without samples get their background);
+ * shaded_count [width*height] int32 or NULL: how many samples of the pixel contributed.                          */
+int qf_texture_composite_tiles(const uint8_t *records, int32_t texture_size, int32_t n_lobes, int32_t sigmoid_codec,
+                               float lambda_thres, const void *triangle_records, const float *xyz_c, const float *dirs_c,
+                               const float *depth_c, const int32_t *tri_c, const int32_t *hit_count, int32_t max_hits,
+                               const int64_t *tile_base, int32_t width, int32_t height, float delta_const, int32_t bg_mode,
+                               const float *bkgd, float stop_tau, float *out_rgb, float *out_alpha, float *out_depth,
+                               float *out_packed, int32_t *shaded_count, void *stream);
+
+/* One baked-texture camera frame as ONE host call: qf_frame_render's launch sequence up to and including the tile pack
+ * (per-ray lists: a job without a field has no room for hit bins) followed by qf_texture_composite_tiles on the job's
+ * samples, image pointers, delta_const, bg_mode and bkgd.  job->field must be NULL and job->tri_c set; the whole job,
+ * the shading parameters and stop_tau are validated before the first launch.  Same results as the separate calls, bit
+ * for bit.                                                                                                        */
+typedef struct qf_baked_shading {
+    const uint8_t *records;             /* qf_texture_pack's texel records [T*T, QF_TEXEL_RECORD_BYTES] */
+    const void *triangle_records;       /* qf_texel_records_pack's [n_faces * QF_TEXEL_TRIANGLE_RECORD_BYTES] */
+    int32_t texture_size;
+    int32_t n_lobes;
+    int32_t sigmoid_codec;
+    float lambda_thres;
+} qf_baked_shading;
+int qf_frame_render_baked(qf_bvh *bvh, const qf_frame_job *job /* host */, const qf_baked_shading *baked /* host */,
+                          float stop_tau, int32_t *shaded_count /* [n_rays] or NULL */, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Baking the texture set (stage 6c, bake_texture_images_shelly.py:270-294) as a fixed launch sequence per band of rows
  * of the texel-position map V [T, T, 3] fp32: compact, the caller's two field launches bounded by the device count,

@@ -73,6 +73,12 @@ class TextureSet(Structure):
                 ("sigmoid_codec", c_int32), ("lambda_thres", c_float)]
 
 
+class BakedShading(Structure):
+    """qf_baked_shading (include/qf_hip.h): the texture set of a baked frame as qf_frame_render_baked takes it."""
+    _fields_ = [("records", c_void_p), ("triangle_records", c_void_p), ("texture_size", c_int32), ("n_lobes", c_int32),
+                ("sigmoid_codec", c_int32), ("lambda_thres", c_float)]
+
+
 _P = c_void_p
 _SIGNATURES = {
     "qf_status_string": (c_char_p, [c_int]),
@@ -195,6 +201,9 @@ _SIGNATURES = {
     "qf_texture_pack": (c_int, [POINTER(TextureSet), _P, _P]),
     "qf_texture_shade_packed": (c_int, [_P, c_int32, c_int32, c_int32, c_float, _P, _P, c_int64, _P, _P, _P]),
     "qf_texture_shade_points": (c_int, [_P, c_int32, c_int32, c_int32, c_float, _P, _P, _P, _P, _P, c_int64, _P, _P, _P, _P]),
+    "qf_texture_composite_tiles": (c_int, [_P, c_int32, c_int32, c_int32, c_float, _P, _P, _P, _P, _P, _P, c_int32, _P, c_int32,
+                                           c_int32, c_float, c_int32, _P, c_float, _P, _P, _P, _P, _P, _P]),
+    "qf_frame_render_baked": (c_int, [_P, POINTER(FrameJob), POINTER(BakedShading), c_float, _P, _P]),
     "qf_bake_compact_workspace_bytes": (c_int64, [c_int64]),
     "qf_bake_compact_texels": (c_int, [_P, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, c_int64, _P]),
     "qf_bake_encode_texels": (c_int, [POINTER(TextureSet), _P, c_int32, _P, _P, c_int64, _P, _P]),

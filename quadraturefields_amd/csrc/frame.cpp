@@ -3,7 +3,9 @@
 // from the library's own entry points -- nothing here launches a kernel of its own.  Two sequences: the per-ray lists
 // (qf_raster_intersect ... qf_pack_tiles) and, for the plain pass with a field, the hit bins (qf_raster_intersect_tiles
 // ... qf_pack_tiles_bins); same frame bit for bit.  qf_frame_prune is the same sequence with the last launch replaced by
-// qf_composite_tiles_trimax (the tile compositor that folds its weights into the triangles).
+// qf_composite_tiles_trimax (the tile compositor that folds its weights into the triangles); qf_frame_render_baked is the
+// sampling half (no field) followed by qf_texture_composite_tiles (the baked-texture frame, shaded and composited front to
+// back in one launch).
 #include "qf_common.h"
 
 namespace {
@@ -147,4 +149,27 @@ extern "C" int qf_frame_prune(qf_bvh *bvh, const qf_frame_job *job, float *tri_w
 {
     const PruneTarget prune = {tri_weight, n_tri, valid_threshold, counts, bad_ids};
     return frame_sequence(bvh, job, &prune, stream);
+}
+
+extern "C" int qf_frame_render_baked(qf_bvh *bvh, const qf_frame_job *job, const qf_baked_shading *baked, float stop_tau,
+                                     int32_t *shaded_count, void *stream)
+{
+    if (!bvh || !job || !job->camera || !baked) return QF_ERR_INVALID_ARGUMENT;
+    const qf_frame_job &j = *job;
+    // The whole job is checked before the first launch, as in frame_sequence (which checks the sampling half): no field
+    // -- the colours come from the texture set --, the samples' triangle ids, then what qf_texture_composite_tiles tests.
+    if (j.field || !j.tri_c) return QF_ERR_INVALID_ARGUMENT;
+    if (!baked->records || !baked->triangle_records || baked->texture_size < 1) return QF_ERR_INVALID_ARGUMENT;
+    if (baked->n_lobes < 1 || baked->n_lobes > QF_MAX_LOBES) return QF_ERR_UNSUPPORTED;
+    if (j.bg_mode < 0 || j.bg_mode > 3) return QF_ERR_INVALID_ARGUMENT;
+    if (!j.out_packed && (!j.out_rgb || !j.out_alpha || !j.out_depth)) return QF_ERR_INVALID_ARGUMENT;
+    if (j.bg_mode == QF_BG_CUSTOM && !j.bkgd) return QF_ERR_INVALID_ARGUMENT;
+    if (!(stop_tau >= 0.0f)) return QF_ERR_INVALID_ARGUMENT;                  // NaN or negative
+    int rc = frame_sequence(bvh, job, nullptr, stream);                      // intersection ... tile pack (per-ray lists)
+    if (rc != QF_OK) return rc;
+    return qf_texture_composite_tiles(baked->records, baked->texture_size, baked->n_lobes, baked->sigmoid_codec,
+                                      baked->lambda_thres, baked->triangle_records, j.xyz_c, j.dirs_c, j.depth_c, j.tri_c,
+                                      j.final_count, j.max_hits, j.tile_base, j.camera->width, j.camera->height, j.delta_const,
+                                      j.bg_mode, j.bkgd, stop_tau, j.out_rgb, j.out_alpha, j.out_depth, j.out_packed,
+                                      shaded_count, stream);
 }

@@ -1,22 +1,13 @@
 // Baked textures: per-triangle texel records and the nearest-texel lookup, the feature fetch from the reference's
 // planes, the packed texel records and their decode / shade.
 #include "exact_common.h"
+#include "texture_device.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-// The nearest-texel lookup of utils.py:1055-1063: float64 Cramer barycentrics -> fp32 clamp / renormalise -> uv ->
-// floor -> clip.  Everything that depends on the triangle alone is computed once per mesh into a 128-byte record per
-// triangle -- corner a, edges e0 / e1, their three dot products and the reciprocal determinant (13 doubles), the three
-// corners' uv (6 floats) -- so that a sample reads ONE line instead of following faces -> 3 vertices -> 3 uv, and
-// evaluates two dot products instead of five and no division (texel_from_record).
-struct TexelRecord {
-    double ax, ay, az, e0x, e0y, e0z, e1x, e1y, e1z, d00, d01, d11, inv;
-    float uv[6];                     // (u, v) of corners a, b, c
-};
-static_assert(sizeof(TexelRecord) == 128, "one 128-byte line per triangle");
-
+// TexelRecord (the 128-byte record per triangle) and texel_from_record: texture_device.h.
 __global__ void texel_records_kernel(const double *vertices, const int64_t *faces, const float *uv, int64_t n_faces,
                                      TexelRecord *records)
 {
@@ -34,34 +25,6 @@ __global__ void texel_records_kernel(const double *vertices, const int64_t *face
         r.uv[2] = uv[ib * 2]; r.uv[3] = uv[ib * 2 + 1];
         r.uv[4] = uv[ic * 2]; r.uv[5] = uv[ic * 2 + 1];
         records[f] = r;
-    }
-}
-
-__device__ __forceinline__ void texel_from_record(const TexelRecord &r, float px, float py, float pz, int texture_size,
-                                                  int64_t out[2])
-{
-    const double wx = (double)px - r.ax, wy = (double)py - r.ay, wz = (double)pz - r.az;
-    const double d02 = (r.e0x * wx + r.e0y * wy) + r.e0z * wz;
-    const double d12 = (r.e1x * wx + r.e1y * wy) + r.e1z * wz;
-    const double b2d = (r.d00 * d12 - r.d01 * d02) * r.inv;
-    const double b1d = (r.d11 * d02 - r.d01 * d12) * r.inv;
-    const double b0d = 1.0 - b1d - b2d;
-    float b0 = fminf(fmaxf((float)b0d, 0.0f), 1.0f);
-    float b1 = fminf(fmaxf((float)b1d, 0.0f), 1.0f);
-    float b2 = fminf(fmaxf((float)b2d, 0.0f), 1.0f);
-    const float s = (b0 + b1) + b2;
-    b0 = b0 / s;
-    b1 = b1 / s;
-    b2 = b2 / s;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const float u = (r.uv[k] * b0 + r.uv[2 + k] * b1) + r.uv[4 + k] * b2;
-        float fl = floorf(u);
-        // torch: floor -> .long() -> clip(0, T-1); NaN (degenerate triangle) -> int64 min -> 0
-        int64_t q = (fl != fl) ? 0 : (fl <= -9.2e18f ? INT64_MIN : (fl >= 9.2e18f ? INT64_MAX : (int64_t)fl));
-        if (q < 0) q = 0;
-        if (q > texture_size - 1) q = texture_size - 1;
-        out[k] = q;
     }
 }
 
@@ -86,17 +49,7 @@ struct TexArgs {
     float lambda_thres;
 };
 
-__device__ __forceinline__ float decode_color(uint8_t c, int sigmoid_codec)
-{
-    const float v = (float)c / 255.0f;
-    if (sigmoid_codec) return logf(fminf(fmaxf(v / (1.0f - v), 1e-8f), 1e37f));   // ngp.py:277-278
-    return v * 2.0f * 12.0f - 12.0f;                                              // ngp.py:280 (B-7)
-}
-
-// Device-resident texel record: the 4 + 6L quantised bytes of one texel, contiguous and padded to one 64-byte
-// sector -- [alpha | diffuse rgb | (lambda, azimuth, elevation, colour rgb) * L].  The reference keeps 2 + 2L separate
-// planes (the PNG set of texture_utils.py:67-124), i.e. 2 + 2L scattered sector reads per sample; a record is ONE.
-constexpr int kTexelRecord = QF_TEXEL_RECORD_BYTES;
+// decode_color and the packed texel record (kTexelRecord bytes per texel): texture_device.h.
 
 // Gathers a texel's bytes from the reference's planes into record order.
 __device__ __forceinline__ void gather_record(const TexArgs &t, int64_t px, uint8_t *rec)
@@ -130,20 +83,11 @@ __global__ void texture_pack_kernel(TexArgs t, uint8_t *records)
     }
 }
 
-// Every quantity a record decodes to is a function of ONE uint8 code, so a workgroup first evaluates the reference's
-// dequantisers (the same expressions as decode_color / decode_lobe, hence the same bits) for all 256 codes into LDS
-// and then decodes by lookup: the 4L sin/cos, L exp and 3+3L colour decodes per sample become LDS reads.
+// The shading kernel: a workgroup first fills the 256-entry dequantiser tables in LDS (DequantTables), then every sample
+// is one record load and one decode by lookup (texel_record_load / texel_record_shade, texture_device.h: the record stays
+// in registers, no scratch).
 // kLookup: the texel is not read but looked up here, from the sample's position and triangle (texel_from_record): the
 // frame path's fusion of qf_texel_indices_packed and this kernel (no int64 [n,2] texel array written and read back).
-// The record stays in REGISTERS: sixteen 32-bit words addressed with compile-time indices only -- the lobe loop is fully
-// unrolled over QF_MAX_LOBES with a wave-uniform ``l < n_lobes`` guard, so ``word[(4 + 6 l + j) >> 2]`` is a constant
-// register and the byte comes out with one shift + mask (v_bfe).  Round 2 indexed a byte array with the run-time lobe
-// counter, which put the whole record in scratch: 80 B per lane written and read back per sample.
-__device__ __forceinline__ uint32_t rec_byte(const uint32_t (&w)[kTexelRecord / 4], int idx)   // idx: compile-time
-{
-    return (w[idx >> 2] >> ((idx & 3) * 8)) & 0xffu;
-}
-
 // TriT: int64_t (the reference's index_tri) or int32_t (the tile pack's ids).
 template <bool kLookup, typename TriT>
 __global__ __launch_bounds__(256) void texture_shade_packed_kernel(const uint8_t *__restrict__ records, int size, int n_lobes,
@@ -157,23 +101,10 @@ __global__ __launch_bounds__(256) void texture_shade_packed_kernel(const uint8_t
                                                                    const int64_t *__restrict__ n_dev)
 {
     if (n_dev) { const int64_t nd = *n_dev; n = nd < n ? (nd > 0 ? nd : 0) : n; }    // device-side count (render-only frame)
-    __shared__ float s_sigma[256], s_col[256], s_caz[256], s_saz[256], s_sel[256], s_cel[256], s_lam[256];
-    {
-        const int c = threadIdx.x;
-        const float pi = 3.14159274101257324f;   // float32(np.pi)
-        const float a = (float)c / 255.0f;
-        s_sigma[c] = -logf(fmaxf(1.0f - a, 1e-6f)) / 0.005f;
-        s_col[c] = decode_color((uint8_t)c, sigmoid_codec);
-        const float az = (float)(uint8_t)(c - 128) / 128.0f * pi;
-        const float el = (float)c / 256.0f * pi;
-        s_caz[c] = cosf(az);
-        s_saz[c] = sinf(az);
-        s_sel[c] = sinf(el);
-        s_cel[c] = cosf(el);
-        s_lam[c] = expf((float)c * lambda_thres / 255.0f - 2.5f);
-    }
+    __shared__ DequantTables s_tab;
+    dequant_tables_fill(s_tab, threadIdx.x, sigmoid_codec, lambda_thres);
     __syncthreads();
-    const int n16 = (4 + 6 * n_lobes + 15) / 16;       // 16-byte pieces of the record that carry data
+    const int n16 = texel_record_pieces(n_lobes);
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         int64_t px;
         if (kLookup) {
@@ -184,35 +115,10 @@ __global__ __launch_bounds__(256) void texture_shade_packed_kernel(const uint8_t
         } else {
             px = texel[i * 2] * size + texel[i * 2 + 1];
         }
-        const uint4 *src = reinterpret_cast<const uint4 *>(records + px * kTexelRecord);
         uint32_t w[kTexelRecord / 4];
-#pragma unroll
-        for (int k = 0; k < kTexelRecord / 16; ++k) {
-            uint4 q = make_uint4(0u, 0u, 0u, 0u);
-            if (k < n16) q = src[k];                   // wave-uniform
-            w[4 * k] = q.x; w[4 * k + 1] = q.y; w[4 * k + 2] = q.z; w[4 * k + 3] = q.w;
-        }
+        texel_record_load(records, px, n16, w);
         const float dx = dirs[i * 3], dy = dirs[i * 3 + 1], dz = dirs[i * 3 + 2];
-        float r = 0.0f, g = 0.0f, b = 0.0f;
-#pragma unroll
-        for (int l = 0; l < QF_MAX_LOBES; ++l) {
-            if (l < n_lobes) {                         // wave-uniform; every index below is a compile-time constant
-                const int o = 4 + 6 * l;
-                const uint32_t c_lam = rec_byte(w, o), c_az = rec_byte(w, o + 1), c_el = rec_byte(w, o + 2);
-                const float se = s_sel[c_el];
-                const float x0 = s_caz[c_az] * se, x1 = s_saz[c_az] * se, x2 = s_cel[c_el];
-                const float nrm = sqrtf((x0 * x0 + x1 * x1) + x2 * x2);
-                const float dotp = ((x0 / nrm) * dx + (x1 / nrm) * dy) + (x2 / nrm) * dz;
-                const float e = expf(fabsf(s_lam[c_lam]) * (dotp - 1.0f));
-                r += s_col[rec_byte(w, o + 3)] * e;
-                g += s_col[rec_byte(w, o + 4)] * e;
-                b += s_col[rec_byte(w, o + 5)] * e;
-            }
-        }
-        rgb[i * 3 + 0] = 1.0f / (1.0f + expf(-(s_col[rec_byte(w, 1)] + r)));
-        rgb[i * 3 + 1] = 1.0f / (1.0f + expf(-(s_col[rec_byte(w, 2)] + g)));
-        rgb[i * 3 + 2] = 1.0f / (1.0f + expf(-(s_col[rec_byte(w, 3)] + b)));
-        sigma[i] = s_sigma[rec_byte(w, 0)];
+        texel_record_shade(s_tab, w, n_lobes, dx, dy, dz, rgb + i * 3, sigma + i);
     }
 }
 

@@ -232,9 +232,14 @@ class FrameRenderer:
         return job, frame, token, (rgbs, sigmas, table, base_w, head_w, sg_params, half, bk, desc, sg), (rgb, alpha, depth, out5)
 
     @torch.no_grad()
-    def render_baked_async(self, origins, viewdirs, uv, compressor, camera):
+    def render_baked_async(self, origins, viewdirs, uv, compressor, camera, early_stop_eps=None):
         """``render_baked`` for a camera frame without a host wait (see ``render_async``): (rgb, alpha, depth, frame).
-        The texel lookup + shading launch reads the sample count from device memory (``n_device``)."""
+        The texel lookup + shading launch reads the sample count from device memory (``n_device``).
+        ``early_stop_eps`` (a transmittance threshold in [0, 1); None = the route above): the frame is shaded and
+        composited front to back in one launch instead (``_render_baked_front_to_back``)."""
+        if early_stop_eps is not None:
+            return self._render_baked_front_to_back(origins, viewdirs, uv, compressor, camera,
+                                                    utils.early_stop_tau(early_stop_eps))
         ri = self.mesh_intersect.rayintersector
         k = self.mesh_intersect.num_intersections
         if ri.fused_frame_ready(camera, k) and torch._C._cuda_getDevice() == ri.device.index:
@@ -255,13 +260,59 @@ class FrameRenderer:
         rgb, alpha, depth, _ = utils.composite_frame(rgbs, sigmas, frame, self.render_step_size, bg_color=self.bg_color)
         return rgb, alpha, depth, frame
 
+    def _render_baked_front_to_back(self, origins, viewdirs, uv, compressor, camera, stop_tau: float):
+        """A baked camera frame without a host wait, shaded inside the tile compositor's walk with early ray termination
+        (``qf_texture_composite_tiles``): (rgb, alpha, depth, frame), ``frame.shaded_count`` =
+        the samples of each pixel that contributed (int32 [H*W], device).  One bound call (``qf_frame_render_baked``)
+        when the frame is the library's fixed sequence, the separately bound launches otherwise; same pixels."""
+        if camera is None:
+            raise NotImplementedError("early_stop_eps needs a camera frame: the ray-major route shades every sample")
+        ri = self.mesh_intersect.rayintersector
+        k = self.mesh_intersect.num_intersections
+        prepared = None
+        if ri.fused_frame_ready(camera, k) and torch._C._cuda_getDevice() == ri.device.index:
+            prepared = ri.fused_frame_job(origins, viewdirs, k, camera, want_tri=True)
+        if prepared is not None:
+            job, frame, token = prepared
+            dev, n = ri.device, frame.width * frame.height
+            shading, keep = utils.baked_shading(self.mesh_intersect, uv, compressor)
+            rgb = torch.empty((n, 3), dtype=torch.float32, device=dev)
+            alpha = torch.empty((n, 1), dtype=torch.float32, device=dev)
+            depth = torch.empty((n, 1), dtype=torch.float32, device=dev)
+            shaded = torch.empty((n,), dtype=torch.int32, device=dev)
+            job.out_rgb, job.out_alpha, job.out_depth = rgb.data_ptr(), alpha.data_ptr(), depth.data_ptr()
+            job.delta_const, job.bg_mode = float(self.render_step_size), utils._BG.get(self.bg_color, _C.BG_CUSTOM)
+            ri.last_route = "frame+cull" if job.cull_chunks & 1 else "frame"
+            _C.check(_C.lib().qf_frame_render_baked(ri._handle, ctypes.byref(job), ctypes.byref(shading), stop_tau,
+                                                    _C.ptr(shaded), _C.stream()), "qf_frame_render_baked")
+            ri.fused_frame_done(frame, token)
+            frame._keep = frame._keep + keep      # referenced until their readers ran
+        else:
+            frame = ri.sample_frame_device(origins, viewdirs, k, camera, want_tri=True)
+            _, xyz_c, dirs_c = ri.last_layout
+            rgb, alpha, depth, shaded = utils.shade_composite_baked_frame(
+                self.mesh_intersect, uv, compressor, xyz_c, dirs_c, frame, self.render_step_size, stop_tau,
+                bg_color=self.bg_color)
+        frame.shaded_count = shaded
+        return rgb, alpha, depth, frame
+
     @torch.no_grad()
-    def render_baked(self, origins, viewdirs, uv, compressor, image_width: int = 0, camera=None):
+    def render_baked(self, origins, viewdirs, uv, compressor, image_width: int = 0, camera=None, early_stop_eps=None):
         """Baked-texture variant (test_baking_texture_images.py:355-371).  With a ``camera`` (the rays are its pixel
         grid) the frame never leaves the intersector's tile order: tile pack with triangle ids -> texel lookup +
         decode + SG shading in one launch -> tile compositor, every stage elementwise or tile-local; same pixels as
-        ``render_image_bake_texture_images_with_occgrid`` on the ray-major samples, bit for bit."""
+        ``render_image_bake_texture_images_with_occgrid`` on the ray-major samples, bit for bit.
+        ``early_stop_eps`` (camera frames only; None = the route above, a float in [0, 1) otherwise): shading and
+        compositing are ONE launch that walks each pixel front to back and stops fetching texels once the transmittance
+        in front of the next sample has fallen below it (``qf_texture_composite_tiles``; the pixel moves by less than
+        3 eps; 0 never stops and gives the route above bit for bit).  ``last_frame.shaded_count``
+        of the intersector then holds the samples of each pixel that contributed."""
         n_rays = origins.shape[0]
+        stop_tau = None
+        if early_stop_eps is not None:
+            stop_tau = utils.early_stop_tau(early_stop_eps)
+            if camera is None:
+                raise NotImplementedError("early_stop_eps needs a camera frame: the ray-major route shades every sample")
         if camera is not None:
             ri = self.mesh_intersect.rayintersector
             data = ri.sample_device(origins, viewdirs, self.mesh_intersect.num_intersections, camera.width, camera,
@@ -269,6 +320,11 @@ class FrameRenderer:
             if data is not None and ri.last_frame is not None and ri.last_frame.tri_c is not None:
                 frame = ri.last_frame
                 _, xyz_c, dirs_c = ri.last_layout
+                if stop_tau is not None:
+                    rgb, alpha, depth, frame.shaded_count = utils.shade_composite_baked_frame(
+                        self.mesh_intersect, uv, compressor, xyz_c, dirs_c, frame, self.render_step_size, stop_tau,
+                        bg_color=self.bg_color)
+                    return rgb, alpha, depth, ri.frame_samples()
                 rgbs, sigmas = utils.shade_baked_points(self.mesh_intersect, uv, compressor, xyz_c, frame.tri_c, dirs_c)
                 rgb, alpha, depth, _ = utils.composite_frame(rgbs, sigmas, frame, self.render_step_size,
                                                              bg_color=self.bg_color)
@@ -277,6 +333,8 @@ class FrameRenderer:
                 dev = origins.device
                 return (torch.ones((n_rays, 3), device=dev), torch.zeros((n_rays, 1), device=dev),
                         torch.zeros((n_rays, 1), device=dev), 0)
+            if stop_tau is not None:
+                raise NotImplementedError("early_stop_eps: this frame has no tile-order layout with triangle ids")
         data = self.mesh_intersect.sampling_raytrace_device(viewdirs, origins, image_width=image_width, camera=camera,
                                                             layout=False)     # no field evaluation: no processing order
         if data is None:

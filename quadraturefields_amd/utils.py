@@ -10,6 +10,7 @@ Every tensor stays on the device; the reference's 160 000-sample Python batch lo
 ``torch.cuda.empty_cache()`` calls and its host round trips (np.lexsort, trimesh barycentrics) are gone,
 the results do not depend on any chunk size.
 """
+import math
 import random
 from typing import Optional
 
@@ -505,6 +506,69 @@ def shade_baked_points(mesh_intersect, uv, compressor, points, index_tri, dirs, 
         _C.ptr(tri64), _C.ptr(tri32), _C.ptr(dirs), n, _C.ptr(n_device, torch.int64), _C.ptr(rgb), _C.ptr(sigma), _C.stream()),
         "qf_texture_shade_points")
     return rgb, sigma
+
+
+def early_stop_tau(early_stop_eps) -> float:
+    """The optical depth behind which a baked frame's pixel stops shading, from the transmittance threshold
+    ``early_stop_eps`` in [0, 1): ``float32(-log(eps))``, computed once on the host; ``+inf`` (never stop) for 0.
+    Anything else, NaN included, raises ValueError."""
+    eps = float(early_stop_eps)
+    if not (0.0 <= eps < 1.0):
+        raise ValueError(f"early_stop_eps must lie in [0, 1), got {early_stop_eps!r}")
+    return float("inf") if eps == 0.0 else float(np.float32(-math.log(eps)))
+
+
+def baked_shading(mesh_intersect, uv, compressor):
+    """The ``qf_baked_shading`` of a (mesh, uv, texture set): (struct, tensors it points at -- keep them referenced until
+    the launch that reads them ran)."""
+    tri_records = _triangle_records(mesh_intersect, uv)
+    records = compressor.records()
+    s = _C.BakedShading()
+    s.records, s.triangle_records = records.data_ptr(), tri_records.data_ptr()
+    s.texture_size, s.n_lobes = int(compressor.alpha.shape[0]), int(compressor.num_lobes)
+    s.sigmoid_codec = 1 if compressor.compression_type == "sigma" else 0
+    s.lambda_thres = float(compressor.lambda_thres)
+    return s, (records, tri_records)
+
+
+@torch.no_grad()
+def shade_composite_baked_frame(mesh_intersect, uv, compressor, xyz_c, dirs_c, frame, render_step_size: float,
+                                stop_tau: float, render_bkgd=None, bg_color="white", packed: bool = False):
+    """``shade_baked_points`` + ``composite_frame`` of a baked frame in the intersector's tile order as ONE launch that
+    walks every pixel front to back (``qf_texture_composite_tiles``): no colour / density arrays, and a pixel stops
+    fetching texels once the optical depth in front of its next sample exceeds ``stop_tau`` (``early_stop_tau``; ``inf``
+    never stops and gives the two calls' pixels bit for bit).  ``frame`` must carry the samples' triangle ids
+    (``want_tri``).  Returns (rgb [N,3], alpha [N,1], depth [N,1], shaded_count [N] int32: the samples of each pixel
+    that contributed) -- with ``packed`` ([N,5], None, None, shaded_count)."""
+    if getattr(frame, "band_rows", 0) or frame.tri_c is None:
+        raise ValueError("shade_composite_baked_frame: an unbanded frame with triangle ids (want_tri) is required")
+    shading, keep = baked_shading(mesh_intersect, uv, compressor)
+    xyz_c, dirs_c = _C.f32c(xyz_c), _C.f32c(dirs_c)
+    dev = xyz_c.device
+    n = frame.depth_c.shape[0]
+    if xyz_c.shape[0] != n or dirs_c.shape[0] != n or frame.tri_c.shape[0] != n:
+        raise ValueError(f"shade_composite_baked_frame: {n} slots in the frame, {xyz_c.shape[0]} positions, "
+                         f"{dirs_c.shape[0]} directions, {frame.tri_c.shape[0]} triangle ids")
+    n_rays = frame.width * frame.height
+    mode = _BG.get(bg_color, _C.BG_CUSTOM)
+    bk = _C.f32c(render_bkgd.detach().reshape(3).to(dev)) if (mode == _C.BG_CUSTOM and render_bkgd is not None) else None
+    rgb = alpha = depth = out5 = None
+    if packed:
+        out5 = torch.empty((n_rays, 5), dtype=torch.float32, device=dev)
+    else:
+        rgb = torch.empty((n_rays, 3), dtype=torch.float32, device=dev)
+        alpha = torch.empty((n_rays, 1), dtype=torch.float32, device=dev)
+        depth = torch.empty((n_rays, 1), dtype=torch.float32, device=dev)
+    shaded = torch.empty((n_rays,), dtype=torch.int32, device=dev)
+    _C.check(_C.lib().qf_texture_composite_tiles(
+        shading.records, shading.texture_size, shading.n_lobes, shading.sigmoid_codec, shading.lambda_thres,
+        shading.triangle_records, _C.ptr(xyz_c), _C.ptr(dirs_c), _C.ptr(frame.depth_c), _C.ptr(frame.tri_c, torch.int32),
+        _C.ptr(frame.hit_count), frame.max_hits, _C.ptr(frame.tile_base), frame.width, frame.height, float(render_step_size),
+        mode, _C.ptr(bk), float(stop_tau), _C.ptr(rgb), _C.ptr(alpha), _C.ptr(depth), _C.ptr(out5), _C.ptr(shaded),
+        _C.stream()), "qf_texture_composite_tiles")
+    if packed:
+        return out5, None, None, shaded
+    return rgb, alpha, depth, shaded
 
 
 def render_image_with_occgrid(
