@@ -2,7 +2,7 @@
 the device:
 
     python examples/evaluate_synthetic.py OUT_DIR [--size 800] [--up_sample 2] [--views 4] [--shells 12] [--subdivisions 6]
-                                                  [--log2_hashmap_size 19]
+                                                  [--log2_hashmap_size 19] [--early_stop_eps EPS] [--render_step_size 5e-3]
 
 Every view is rendered at ``up_sample`` times the ground-truth size, as the scripts do (run_nerfsynthetic_finetune.sh:9),
 and scored by ``metrics.FrameScorer``: INTER_AREA down-sample, PSNR, SSIM, the rgb / error / depth images, with no host
@@ -10,6 +10,11 @@ wait per frame; ``results()`` after the last view is the loop's one synchronisat
 set to load, so the ground truth of a view is the same scene rendered at ``up_sample 1`` by a field whose hash table is
 perturbed.  Writes ``results.json`` with the scripts' key names (``psnr``, ``ssim``; LPIPS is not computed) and
 ``rgb_test_after_{i}.png``, ``rgb_error_after_{i}.png``, ``depth_after_{i}.png``.
+
+``--early_stop_eps EPS`` renders the scored views front to back in rank windows with early ray termination
+(``FrameRenderer.render(..., early_stop_eps=EPS)``) and prints, per view, the share of the frame's
+samples the field evaluated; the ground truth stays on the default route.  The seeded field is thin: at the default
+``--render_step_size`` no ray ever stops, 0.5 makes the shells opaque.
 """
 import argparse
 import json
@@ -32,6 +37,9 @@ def main(argv=None):
     ap.add_argument("--log2_hashmap_size", type=int, default=19)
     ap.add_argument("--bvh_builder", choices=("host", "device"), default="host",
                     help="where the ray-mesh BVH is built: host (binned SAH) or device (linear BVH on the GPU: faster build, slower traversal)")
+    ap.add_argument("--early_stop_eps", type=float, default=None,
+                    help="transmittance threshold in [0, 1): render the scored views front to back with early ray termination")
+    ap.add_argument("--render_step_size", type=float, default=5e-3, help="the compositing step (optical depth = density * step)")
     args = ap.parse_args(argv)
 
     from quadraturefields_amd import synthetic
@@ -47,7 +55,7 @@ def main(argv=None):
     scorer = FrameScorer(size, size, up_sample=args.up_sample, capacity=args.views, device=device)
     f = scorer.factor
     mesh = synthetic.shell_mesh(n_shells=args.shells, subdivisions=args.subdivisions)
-    mi = MeshIntersection(mesh, simplify_mesh=False, scale=1.0, num_intersections=25, render_step_size=5e-3, device=device,
+    mi = MeshIntersection(mesh, simplify_mesh=False, scale=1.0, num_intersections=25, render_step_size=args.render_step_size, device=device,
                           bvh_builder=args.bvh_builder)
 
     def field_of(perturbed):
@@ -66,7 +74,13 @@ def main(argv=None):
         o, d = synthetic.camera_rays(c2w, focal, size, size, device=device)
         pixels = truth_renderer.render(o, d, camera=make_camera(c2w, focal, size, size))[0]
         o, d = synthetic.camera_rays(c2w, focal * f, size * f, size * f, device=device)
-        rgb, _, depth, _ = renderer.render(o, d, camera=make_camera(c2w, focal * f, size * f, size * f))
+        rgb, _, depth, n_samples = renderer.render(o, d, camera=make_camera(c2w, focal * f, size * f, size * f),
+                                                   early_stop_eps=args.early_stop_eps)
+        if args.early_stop_eps is not None:
+            frame = mi.rayintersector.last_frame
+            evaluated, shaded = int(frame.evaluated_count.sum()), int(frame.shaded_count.sum())
+            print(f"view {i}: {evaluated} of {n_samples} samples evaluated ({evaluated / max(n_samples, 1):.1%}), "
+                  f"{shaded} contribute")
         scorer.score(rgb, pixels, depth=depth, images=True)
         # the images live in reused buffers: they are copied out before the next frame is scored
         names = ("rgb_test_after_{}.png", "rgb_error_after_{}.png", "depth_after_{}.png")

@@ -1132,6 +1132,61 @@ typedef struct qf_baked_shading {
 int qf_frame_render_baked(qf_bvh *bvh, const qf_frame_job *job /* host */, const qf_baked_shading *baked /* host */,
                           float stop_tau, int32_t *shaded_count /* [n_rays] or NULL */, void *stream);
 
+/* The FIELD-evaluated frame front to back with early ray termination.  No reference counterpart (its evaluation runs the
+ * field at every quadrature point).  The field kernel is batched and cannot decide per sample, so the frame is evaluated
+ * in RANK WINDOWS: a schedule b_1 < b_2 < ... < b_m (1 <= m <= QF_FRONT_MAX_WINDOWS, b_1 >= 1, b_m >= max_hits); window j
+ * covers the ranks [b_{j-1}, b_j) of every pixel (b_0 = 0).  The rule is qf_texture_composite_tiles': the rank-k sample of
+ * a pixel contributes iff the optical depth accumulated before it satisfies cum <= stop_tau (cum = the compositor's fp32
+ * value); a pixel that has stopped stays stopped; stop_tau = +inf never stops; NaN or negative: QF_ERR_INVALID_ARGUMENT.
+ * A pixel is EVALUATED in window j iff it has a sample of rank b_{j-1} and the rule holds for that sample; the field then
+ * evaluates all of its samples in the window.  The compositor applies the rule per sample, so the pixels do not depend on
+ * the schedule -- only evaluated_count does -- and are those of qf_composite_tiles over the contributing samples, bit for
+ * bit (stop_tau = +inf: qf_field_forward + qf_composite_tiles).
+ * The frame comes in the coherent tile order (qf_pack_tiles / qf_pack_tiles_bins): depth_c [n], hit_count = the kept
+ * counts (final_count), tile_base; rgb_c [n,3] / sigma_c [n] are the field's outputs, filled window by window.
+ * state [width*height, 8] fp32, 16-byte aligned: the per-pixel sums, counts and flags between the launches (opaque).
+ *
+ * qf_front_select, for the window [rank_mid, rank_hi): composites the previous window [rank_lo, rank_mid) on top of the
+ * state (rank_mid == 0: the first window, rank_lo = 0, there is no state yet and rgb_c / sigma_c are not read), selects
+ * the pixels that enter the window and writes the window list: win_order [<= capacity] int32 = the slots of their
+ * samples in the window, in (tile, rank, pixel) order -- deterministic: counts per tile and per group of 16 tiles
+ * (win_count int32 [n_tiles + ceil(n_tiles / 16)]), their scan inside the writing launch, the write --, *win_total (device
+ * int64) = how many.  Two launches.  A frame of more than QF_FRONT_MAX_TILES 8x8 tiles (4096 x 4096 pixels) is refused:
+ * the writing launch's share of the scan grows with the square of the tile count.  The caller then runs
+ * qf_field_forward(..., n = capacity, n_device = win_total, order = win_order, rgb_c, sigma_c): the outputs land in place;
+ * an empty window is a launch that does nothing.  capacity = the slots of the frame's arrays (<= 2^31 - 1).
+ * qf_front_finish, after the last window [rank_lo, rank_hi) has been evaluated: composites it, blends, writes the image
+ * as qf_composite_tiles does (three arrays or out_packed; pixels without samples get their background) and, where not
+ * NULL, shaded_count [width*height] int32 = the samples of the pixel that contributed and evaluated_count = min(count,
+ * b_j) for the last window j the pixel entered (== count for a pixel that never stops).  One launch.               */
+#define QF_FRONT_MAX_WINDOWS 8
+#define QF_FRONT_MAX_TILES (1 << 18)
+int qf_front_select(const float *rgb_c, const float *sigma_c, const float *depth_c, float delta_const,
+                    const int32_t *hit_count, int32_t max_hits, const int64_t *tile_base, int32_t width, int32_t height,
+                    float stop_tau, int32_t rank_lo, int32_t rank_mid, int32_t rank_hi, float *state, int32_t *win_count,
+                    int64_t *win_total, int32_t *win_order, int64_t capacity, void *stream);
+int qf_front_finish(const float *rgb_c, const float *sigma_c, const float *depth_c, float delta_const,
+                    const int32_t *hit_count, int32_t max_hits, const int64_t *tile_base, int32_t width, int32_t height,
+                    float stop_tau, int32_t rank_lo, int32_t rank_hi, float *state, int32_t bg_mode, const float *bkgd,
+                    float *out_rgb, float *out_alpha, float *out_depth, float *out_packed, int32_t *shaded_count,
+                    int32_t *evaluated_count, void *stream);
+
+/* One such frame as ONE host call: qf_frame_render's launch sequence up to and including the tile pack (hit bins or
+ * per-ray lists, chosen exactly as there), then per window qf_front_select + the job's field launch over the window list,
+ * then qf_front_finish on the job's image pointers.  job->field and an image are required.  The whole job, the schedule
+ * (rank_windows [n_windows], host) and stop_tau are validated before the first launch: a refused job leaves every buffer
+ * and the pinned block untouched.  Same results as the separate calls, bit for bit.                              */
+typedef struct qf_front_scratch {
+    float *state;                       /* [n_rays, 8], 16-byte aligned */
+    int32_t *win_count;                 /* [n_tiles + ceil(n_tiles / 16)], n_tiles = ceil(w/8) * ceil(h/8) */
+    int64_t *win_total;                 /* [1] */
+    int32_t *win_order;                 /* [n_rays * K] */
+} qf_front_scratch;
+int qf_frame_render_front(qf_bvh *bvh, const qf_frame_job *job /* host */, float stop_tau,
+                          const int32_t *rank_windows /* host */, int32_t n_windows,
+                          const qf_front_scratch *scratch /* host */, int32_t *shaded_count /* [n_rays] or NULL */,
+                          int32_t *evaluated_count /* [n_rays] or NULL */, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Baking the texture set (stage 6c, bake_texture_images_shelly.py:270-294) as a fixed launch sequence per band of rows
  * of the texel-position map V [T, T, 3] fp32: compact, the caller's two field launches bounded by the device count,

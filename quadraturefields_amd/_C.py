@@ -20,6 +20,8 @@ QF_MAX_LOBES = 8
 QF_BVH_MAX_HITS = 64
 QF_TEXEL_RECORD_BYTES = 64
 QF_TEXEL_TRIANGLE_RECORD_BYTES = 128
+QF_FRONT_MAX_WINDOWS = 8
+QF_FRONT_MAX_TILES = 1 << 18
 HEAD_NONE, HEAD_NGP, HEAD_SG, HEAD_SG_FEATURES = 0, 1, 2, 3
 FIELD_FP32, FIELD_BF16, FIELD_FP16 = 0, 1, 2          # qf_frame_job.field_precision
 UNTOUCHED_LAST_FACE, UNTOUCHED_ZERO = 0, 1            # qf_texel_positions
@@ -77,6 +79,11 @@ class BakedShading(Structure):
     """qf_baked_shading (include/qf_hip.h): the texture set of a baked frame as qf_frame_render_baked takes it."""
     _fields_ = [("records", c_void_p), ("triangle_records", c_void_p), ("texture_size", c_int32), ("n_lobes", c_int32),
                 ("sigmoid_codec", c_int32), ("lambda_thres", c_float)]
+
+
+class FrontScratch(Structure):
+    """qf_front_scratch (include/qf_hip.h): what qf_frame_render_front keeps between its launches."""
+    _fields_ = [("state", c_void_p), ("win_count", c_void_p), ("win_total", c_void_p), ("win_order", c_void_p)]
 
 
 _P = c_void_p
@@ -204,6 +211,12 @@ _SIGNATURES = {
     "qf_texture_composite_tiles": (c_int, [_P, c_int32, c_int32, c_int32, c_float, _P, _P, _P, _P, _P, _P, c_int32, _P, c_int32,
                                            c_int32, c_float, c_int32, _P, c_float, _P, _P, _P, _P, _P, _P]),
     "qf_frame_render_baked": (c_int, [_P, POINTER(FrameJob), POINTER(BakedShading), c_float, _P, _P]),
+    "qf_front_select": (c_int, [_P, _P, _P, c_float, _P, c_int32, _P, c_int32, c_int32, c_float, c_int32, c_int32, c_int32, _P, _P,
+                                _P, _P, c_int64, _P]),
+    "qf_front_finish": (c_int, [_P, _P, _P, c_float, _P, c_int32, _P, c_int32, c_int32, c_float, c_int32, c_int32, _P, c_int32, _P,
+                                _P, _P, _P, _P, _P, _P, _P]),
+    "qf_frame_render_front": (c_int, [_P, POINTER(FrameJob), c_float, POINTER(c_int32), c_int32, POINTER(FrontScratch), _P, _P,
+                                      _P]),
     "qf_bake_compact_workspace_bytes": (c_int64, [c_int64]),
     "qf_bake_compact_texels": (c_int, [_P, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, c_int64, _P]),
     "qf_bake_encode_texels": (c_int, [POINTER(TextureSet), _P, c_int32, _P, _P, c_int64, _P, _P]),

@@ -5,7 +5,9 @@
 // ... qf_pack_tiles_bins); same frame bit for bit.  qf_frame_prune is the same sequence with the last launch replaced by
 // qf_composite_tiles_trimax (the tile compositor that folds its weights into the triangles); qf_frame_render_baked is the
 // sampling half (no field) followed by qf_texture_composite_tiles (the baked-texture frame, shaded and composited front to
-// back in one launch).
+// back in one launch); qf_frame_render_front is the sequence up to the tile pack followed by the rank windows of
+// front_frame.hip (select launches + one field launch per window) and their finish: the field frame front to back with
+// early ray termination.
 #include "qf_common.h"
 
 namespace {
@@ -19,8 +21,23 @@ struct PruneTarget {
     int32_t *bad_ids;
 };
 
-// The frame's launch sequence; prune == nullptr: qf_frame_render.
-int frame_sequence(qf_bvh *bvh, const qf_frame_job *job, const PruneTarget *prune, void *stream)
+// The field over min(*n_device, cap) points of the job's samples, in the job's precision; order as qf_field_forward's.
+int field_launch(const qf_frame_job &j, int64_t cap, const int64_t *n_device, const int32_t *order, void *stream)
+{
+    if (j.field_precision == QF_FIELD_FP32)
+        return qf_field_forward(j.field, static_cast<const float *>(j.table), static_cast<const float *>(j.base_w),
+                                static_cast<const float *>(j.head_ngp_w), static_cast<const qf_sg_head *>(j.head_sg),
+                                j.xyz_c, j.dirs_c, cap, n_device, order, j.rgb_c, j.sigma_c, nullptr, nullptr, nullptr,
+                                stream);
+    auto fwd = j.field_precision == QF_FIELD_BF16 ? qf_field_forward_bf16 : qf_field_forward_f16;
+    return fwd(j.field, static_cast<const uint16_t *>(j.table), static_cast<const uint16_t *>(j.base_w),
+               static_cast<const uint16_t *>(j.head_ngp_w), static_cast<const qf_sg_head_bf16 *>(j.head_sg), j.xyz_c,
+               j.dirs_c, cap, n_device, order, j.rgb_c, j.sigma_c, nullptr, stream);
+}
+
+// The frame's launch sequence; prune == nullptr: qf_frame_render.  samples_only: the job is validated as a whole, field
+// and image included, but the sequence ends with the tile pack (qf_frame_render_front goes on from there).
+int frame_sequence(qf_bvh *bvh, const qf_frame_job *job, const PruneTarget *prune, void *stream, bool samples_only = false)
 {
     if (!bvh || !job || !job->camera) return QF_ERR_INVALID_ARGUMENT;
     const qf_frame_job &j = *job;
@@ -113,20 +130,9 @@ int frame_sequence(qf_bvh *bvh, const qf_frame_job *job, const PruneTarget *prun
                            stream);
         if (rc != QF_OK) return rc;
     }
-    int rc = QF_OK;
-    if (!j.field) return QF_OK;                 // sampling only
+    if (!j.field || samples_only) return QF_OK; // sampling only
     // 5. the field over min(*total, cap) points, in the job's precision, 6. the tile compositor
-    if (j.field_precision == QF_FIELD_FP32) {
-        rc = qf_field_forward(j.field, static_cast<const float *>(j.table), static_cast<const float *>(j.base_w),
-                              static_cast<const float *>(j.head_ngp_w), static_cast<const qf_sg_head *>(j.head_sg),
-                              j.xyz_c, j.dirs_c, cap, j.total, nullptr, j.rgb_c, j.sigma_c, nullptr, nullptr, nullptr,
-                              stream);
-    } else {
-        auto fwd = j.field_precision == QF_FIELD_BF16 ? qf_field_forward_bf16 : qf_field_forward_f16;
-        rc = fwd(j.field, static_cast<const uint16_t *>(j.table), static_cast<const uint16_t *>(j.base_w),
-                 static_cast<const uint16_t *>(j.head_ngp_w), static_cast<const qf_sg_head_bf16 *>(j.head_sg), j.xyz_c,
-                 j.dirs_c, cap, j.total, nullptr, j.rgb_c, j.sigma_c, nullptr, stream);
-    }
+    int rc = field_launch(j, cap, j.total, nullptr, stream);
     if (rc != QF_OK) return rc;
     if (prune)
         return qf_composite_tiles_trimax(j.rgb_c, j.sigma_c, j.depth_c, j.delta_const, j.final_count, j.max_hits, j.tile_base, w,
@@ -172,4 +178,45 @@ extern "C" int qf_frame_render_baked(qf_bvh *bvh, const qf_frame_job *job, const
                                       j.final_count, j.max_hits, j.tile_base, j.camera->width, j.camera->height, j.delta_const,
                                       j.bg_mode, j.bkgd, stop_tau, j.out_rgb, j.out_alpha, j.out_depth, j.out_packed,
                                       shaded_count, stream);
+}
+
+extern "C" int qf_frame_render_front(qf_bvh *bvh, const qf_frame_job *job, float stop_tau, const int32_t *rank_windows,
+                                     int32_t n_windows, const qf_front_scratch *scratch, int32_t *shaded_count,
+                                     int32_t *evaluated_count, void *stream)
+{
+    if (!bvh || !job || !job->camera || !scratch) return QF_ERR_INVALID_ARGUMENT;
+    const qf_frame_job &j = *job;
+    // The whole job, the schedule and stop_tau are checked before the first launch: what frame_sequence does not test
+    // itself -- a field and an image are required here -- then the schedule, then the scratch.
+    if (!j.field || j.max_hits < 1) return QF_ERR_INVALID_ARGUMENT;
+    if ((int64_t)((job->camera->width + 7) / 8) * ((job->camera->height + 7) / 8) > QF_FRONT_MAX_TILES)
+        return QF_ERR_INVALID_ARGUMENT;
+    if (!j.out_packed && (!j.out_rgb || !j.out_alpha || !j.out_depth)) return QF_ERR_INVALID_ARGUMENT;
+    if (!(stop_tau >= 0.0f)) return QF_ERR_INVALID_ARGUMENT;                  // NaN or negative
+    if (!rank_windows || n_windows < 1 || n_windows > QF_FRONT_MAX_WINDOWS) return QF_ERR_INVALID_ARGUMENT;
+    for (int i = 0; i < n_windows; ++i)
+        if (rank_windows[i] <= (i ? rank_windows[i - 1] : 0)) return QF_ERR_INVALID_ARGUMENT;
+    if (rank_windows[n_windows - 1] < j.max_hits) return QF_ERR_INVALID_ARGUMENT;
+    if (!scratch->state || reinterpret_cast<uintptr_t>(scratch->state) % 16 != 0 || !scratch->win_count || !scratch->win_total ||
+        !scratch->win_order)
+        return QF_ERR_INVALID_ARGUMENT;
+    int rc = frame_sequence(bvh, job, nullptr, stream, true);                // intersection ... tile pack, either route
+    if (rc != QF_OK) return rc;
+    const int32_t w = j.camera->width, h = j.camera->height;
+    const int64_t cap = j.n_rays * (int64_t)j.max_hits;
+    int32_t lo = 0, mid = 0;
+    for (int i = 0; i < n_windows; ++i) {
+        const int32_t hi = rank_windows[i];
+        rc = qf_front_select(j.rgb_c, j.sigma_c, j.depth_c, j.delta_const, j.final_count, j.max_hits, j.tile_base, w, h, stop_tau,
+                             lo, mid, hi, scratch->state, scratch->win_count, scratch->win_total, scratch->win_order, cap,
+                             stream);
+        if (rc != QF_OK) return rc;
+        rc = field_launch(j, cap, scratch->win_total, scratch->win_order, stream);
+        if (rc != QF_OK) return rc;
+        lo = mid;
+        mid = hi;
+    }
+    return qf_front_finish(j.rgb_c, j.sigma_c, j.depth_c, j.delta_const, j.final_count, j.max_hits, j.tile_base, w, h, stop_tau,
+                           lo, mid, scratch->state, j.bg_mode, j.bkgd, j.out_rgb, j.out_alpha, j.out_depth, j.out_packed,
+                           shaded_count, evaluated_count, stream);
 }

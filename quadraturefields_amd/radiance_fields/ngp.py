@@ -216,7 +216,9 @@ class _FusedFieldBase(nn.Module):
         return selector, x
 
     def _launch(self, head, n_lobes, xyz, dirs, want_rgb=False, want_sigma=False, want_geo=False, want_features=0,
-                head_ngp=None, head_sg=None, order=None, enc_out=None, n_device=None):
+                head_ngp=None, head_sg=None, order=None, enc_out=None, n_device=None, out=None):
+        """``out`` (or None): (rgb [n,3], sigma [n]) fp32 buffers of the caller's that take the place of fresh ones -- with
+        ``order`` and ``n_device`` only the listed points are written, the rest keeps what it held."""
         if self.compute_dtype not in self.COMPUTE_DTYPES:
             raise ValueError(f"compute_dtype must be one of {', '.join(map(repr, self.COMPUTE_DTYPES))}, "
                              f"got {self.compute_dtype!r}")
@@ -234,6 +236,11 @@ class _FusedFieldBase(nn.Module):
             order = order.contiguous()
         rgb = torch.empty((n, 3), dtype=torch.float32, device=dev) if want_rgb else None
         sigma = torch.empty((n,), dtype=torch.float32, device=dev) if want_sigma else None
+        if out is not None:
+            rgb, sigma = out
+            for t, shape in ((rgb, (n, 3)), (sigma, (n,))):
+                if t.dtype != torch.float32 or tuple(t.shape) != shape or t.device != dev or not t.is_contiguous():
+                    raise ValueError(f"out must be contiguous float32 {shape} on {dev}, got {t.dtype} {tuple(t.shape)} on {t.device}")
         geo = torch.empty((n, 15), dtype=torch.float32, device=dev) if want_geo else None
         feats = torch.empty((n, want_features), dtype=torch.float32, device=dev) if want_features else None
         desc = self._field_desc(head, n_lobes)
@@ -258,6 +265,18 @@ class _FusedFieldBase(nn.Module):
             _C.ptr(enc_out), _C.stream()),
                  "qf_field_forward")
         return rgb, sigma, geo, feats
+
+    @torch.no_grad()
+    def forward_into(self, positions, directions, rgb, sigma, order=None, n_device=None):
+        """The fused inference kernel of ``forward`` writing into the caller's ``rgb`` [n,3] / ``sigma`` [n]: with
+        ``order`` (int32 [n]) and ``n_device`` only the points ``order[:n_device]`` are evaluated and written, in place
+        (a rank window of ``utils.render_field_front``).  Inference only; ``discretize`` has no such route."""
+        if getattr(self, "discretize", False) is not False:
+            raise NotImplementedError("forward_into: the discretised head is evaluated in torch")
+        sg = hasattr(self, "num_g_lobes")
+        self._launch(_C.HEAD_SG if sg else _C.HEAD_NGP, self.num_g_lobes if sg else 0, positions, directions,
+                     head_ngp=None if sg else self.mlp_head.params.detach(), head_sg=self._sg_params() if sg else None,
+                     order=order, n_device=n_device, out=(rgb, sigma))
 
     def _recording(self, *inputs) -> bool:
         """Autograd is recording and a parameter or input wants a gradient: take the differentiable route

@@ -63,8 +63,22 @@ class FrameRenderer:
 
     @torch.no_grad()
     def render(self, origins: torch.Tensor, viewdirs: torch.Tensor, image_width: int = 0, scaling: float = 0.0,
-               render_bkgd: Optional[torch.Tensor] = None, camera=None, _retry: bool = False):
-        """(rgb [R,3], alpha [R,1], depth [R,1], n_samples) for R rays."""
+               render_bkgd: Optional[torch.Tensor] = None, camera=None, _retry: bool = False, early_stop_eps=None,
+               rank_windows=None):
+        """(rgb [R,3], alpha [R,1], depth [R,1], n_samples) for R rays.
+        ``early_stop_eps`` (None = the route below, untouched; a transmittance threshold in [0, 1) otherwise): the frame is
+        evaluated front to back in rank windows and a pixel's samples behind the point where its transmittance has fallen
+        below the threshold are neither evaluated nor composited (``_render_front``; the pixel moves
+        by less than 3 eps; 0 never stops and gives the route below bit for bit).  ``rank_windows``: the schedule
+        (``utils.front_rank_windows``; None = the default).  ``last_frame.shaded_count`` / ``.evaluated_count`` of the
+        intersector then hold the samples of each pixel that contributed / were evaluated; ``n_samples`` stays the
+        frame's total."""
+        if early_stop_eps is not None:
+            rgb, alpha, depth, frame = self._render_front(origins, viewdirs, camera, scaling, render_bkgd, False,
+                                                          early_stop_eps, rank_windows)
+            return rgb, alpha, depth, self.mesh_intersect.rayintersector.frame_samples(frame)
+        if rank_windows is not None:
+            raise ValueError("rank_windows is the schedule of the early_stop_eps route: give both")
         n_rays = origins.shape[0]
         if camera is not None:
             image_width = camera.width
@@ -119,13 +133,19 @@ class FrameRenderer:
 
     @torch.no_grad()
     def render_async(self, origins: torch.Tensor, viewdirs: torch.Tensor, camera, scaling: float = 0.0,
-                     render_bkgd: Optional[torch.Tensor] = None, packed: bool = False):
+                     render_bkgd: Optional[torch.Tensor] = None, packed: bool = False, early_stop_eps=None,
+                     rank_windows=None):
         """``render`` for a camera frame WITHOUT any host wait: (rgb, alpha, depth, frame) -- with ``packed``
         (rgb | alpha | depth in ONE [R,5] array, None, None, frame).  The frame's sample count
         stays on the device -- the tile pack leaves it next to the tile bases and the field / deformation kernels read
         it there (``n_device``) -- so the whole frame is a fixed sequence of ~10 launches into worst-case buffers and
         the host is free to enqueue the next frame (or band) at once; ``frame`` answers
-        ``mesh_intersect.rayintersector.frame_samples()`` later, if anyone asks.  Same pixels as ``render``."""
+        ``mesh_intersect.rayintersector.frame_samples()`` later, if anyone asks.  Same pixels as ``render``.
+        ``early_stop_eps`` / ``rank_windows``: as on ``render`` (``frame.shaded_count``, ``frame.evaluated_count``)."""
+        if early_stop_eps is not None:
+            return self._render_front(origins, viewdirs, camera, scaling, render_bkgd, packed, early_stop_eps, rank_windows)
+        if rank_windows is not None:
+            raise ValueError("rank_windows is the schedule of the early_stop_eps route: give both")
         ri = self.mesh_intersect.rayintersector
         fused = getattr(self.radiance_field, "discretize", False) is False
         if not fused:
@@ -174,6 +194,58 @@ class FrameRenderer:
         ri.fused_frame_done(frame, token)
         frame._keep = frame._keep + keep      # referenced until their readers ran
         return (out5, None, None, frame) if packed else (rgb, alpha, depth, frame)
+
+    def _render_front(self, origins, viewdirs, camera, scaling, render_bkgd, packed, early_stop_eps, rank_windows,
+                      _switched=False):
+        """A field-evaluated camera frame front to back in rank windows with early ray termination, without a host wait
+        (DESIGN.md section 3.5c): (rgb, alpha, depth, frame) -- ``packed``: ([R,5], None, None, frame) -- with
+        ``frame.shaded_count`` / ``frame.evaluated_count`` int32 [H*W] on the device.  One bound call
+        (``qf_frame_render_front``) when the frame is the library's fixed sequence and the field is fp32 or fp16, the
+        separately bound launches (``utils.render_field_front``) otherwise; same pixels.  Anything the route does not
+        cover raises: the keyword is never ignored."""
+        stop_tau = utils.early_stop_tau(early_stop_eps)
+        if camera is None:
+            raise NotImplementedError("early_stop_eps needs a camera frame: the ray-major route evaluates every sample")
+        if self.field_net is not None and scaling != 0:
+            raise NotImplementedError("early_stop_eps: the deformed (\"before\") frame has no front-to-back route")
+        rf = self.radiance_field
+        if type(rf) not in (NGPRadianceField, NGPRadianceFieldSGNew) or getattr(rf, "discretize", False) is not False:
+            raise NotImplementedError("early_stop_eps: the field must be an NGPRadianceField or an NGPRadianceFieldSGNew "
+                                      "without discretize (the fused kernels evaluate the windows)")
+        ri = self.mesh_intersect.rayintersector
+        k = self.mesh_intersect.num_intersections
+        windows = utils.front_rank_windows(rank_windows, k)
+        if ((camera.width + 7) // 8) * ((camera.height + 7) // 8) > _C.QF_FRONT_MAX_TILES:
+            raise NotImplementedError("early_stop_eps: frames of more than 4096 x 4096 pixels have no front-to-back route")
+        if not _switched and torch._C._cuda_getDevice() != ri.device.index:
+            with torch.cuda.device(ri.device):
+                return self._render_front(origins, viewdirs, camera, scaling, render_bkgd, packed, early_stop_eps,
+                                          rank_windows, _switched=True)
+        prepared = None
+        if rf.compute_dtype in ("fp32", "fp16") and ri.fused_frame_ready(camera, k):
+            prepared = self._one_call_job(origins, viewdirs, camera, k, render_bkgd, packed)
+        if prepared is not None:
+            job, frame, token, keep, (rgb, alpha, depth, out5) = prepared
+            dev, n = ri.device, frame.width * frame.height
+            scratch, held = utils.front_scratch(n, frame.tile_base.shape[0], frame.total, dev)
+            shaded = torch.empty((n,), dtype=torch.int32, device=dev)
+            evaluated = torch.empty((n,), dtype=torch.int32, device=dev)
+            ri.last_route = "frame+cull" if job.cull_chunks & 1 else "frame"
+            _C.check(_C.lib().qf_frame_render_front(
+                ri._handle, ctypes.byref(job), stop_tau, (ctypes.c_int32 * len(windows))(*windows), len(windows),
+                ctypes.byref(scratch), _C.ptr(shaded), _C.ptr(evaluated), _C.stream()), "qf_frame_render_front")
+            ri.fused_frame_done(frame, token)
+            frame._keep = frame._keep + keep + held      # referenced until their readers ran
+            if packed:
+                rgb, alpha, depth = out5, None, None
+        else:
+            frame = ri.sample_frame_device(origins, viewdirs, k, camera)
+            _, xyz_c, dirs_c = ri.last_layout
+            rgb, alpha, depth, shaded, evaluated = utils.render_field_front(
+                rf, xyz_c, dirs_c, frame, self.render_step_size, stop_tau, windows, render_bkgd=render_bkgd,
+                bg_color=self.bg_color, packed=packed)
+        frame.shaded_count, frame.evaluated_count = shaded, evaluated
+        return rgb, alpha, depth, frame
 
     def _one_call_job(self, origins, viewdirs, camera, k, render_bkgd, packed, want_tri=False, image=True):
         """The complete ``qf_frame_job`` of a camera frame on the intersector's (current) device: the sampling half

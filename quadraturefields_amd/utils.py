@@ -509,13 +509,98 @@ def shade_baked_points(mesh_intersect, uv, compressor, points, index_tri, dirs, 
 
 
 def early_stop_tau(early_stop_eps) -> float:
-    """The optical depth behind which a baked frame's pixel stops shading, from the transmittance threshold
-    ``early_stop_eps`` in [0, 1): ``float32(-log(eps))``, computed once on the host; ``+inf`` (never stop) for 0.
+    """The optical depth behind which a front-to-back frame's pixel stops (a baked frame stops shading, a field frame
+    stops being evaluated), from the transmittance threshold ``early_stop_eps`` in [0, 1): ``float32(-log(eps))``, computed once on the host; ``+inf`` (never stop) for 0.
     Anything else, NaN included, raises ValueError."""
     eps = float(early_stop_eps)
     if not (0.0 <= eps < 1.0):
         raise ValueError(f"early_stop_eps must lie in [0, 1), got {early_stop_eps!r}")
     return float("inf") if eps == 0.0 else float(np.float32(-math.log(eps)))
+
+
+#: The default rank-window schedule of the front-to-back field frame before its ends >= K are collapsed into one final K
+#: (``front_rank_windows``): the fastest of the four candidates of ``tools/field_front_bench.py`` on its opaque scene
+#: (DESIGN.md section 3.5c has the numbers).
+FRONT_RANK_WINDOWS = (1, 3, 7, 15)
+
+
+def front_rank_windows(rank_windows, max_hits: int) -> tuple:
+    """The rank-window schedule of a front-to-back field frame as the library takes it: strictly increasing ints,
+    1 <= len <= 8, first >= 1, last >= ``max_hits``.  ``None``: the default, ``FRONT_RANK_WINDOWS`` followed by K with every
+    end >= K collapsed into the final K ((1, 3, 7, 15, 25) at K = 25, (1, 3, 5) at K = 5, (1,) at K = 1).  Anything else raises
+    ValueError."""
+    k = int(max_hits)
+    if rank_windows is None:
+        return tuple(b for b in FRONT_RANK_WINDOWS if b < k) + (k,)
+    w = tuple(int(b) for b in rank_windows)
+    if tuple(rank_windows) != w or not 1 <= len(w) <= _C.QF_FRONT_MAX_WINDOWS or w[0] < 1 or w[-1] < k \
+            or any(b <= a for a, b in zip(w, w[1:])):
+        raise ValueError(f"rank_windows must be 1..{_C.QF_FRONT_MAX_WINDOWS} strictly increasing integers, the first >= 1 and "
+                         f"the last >= max_hits = {k}, got {rank_windows!r}")
+    return w
+
+
+def front_scratch(n_rays: int, n_tiles: int, capacity: int, device):
+    """The ``qf_front_scratch`` of a front-to-back field frame: (struct, tensors it points at -- keep them referenced until
+    the frame's launches ran)."""
+    state = torch.empty((n_rays, 8), dtype=torch.float32, device=device)
+    win_count = torch.empty((n_tiles + (n_tiles + 15) // 16,), dtype=torch.int32, device=device)   # per tile | per 16 tiles
+    win_total = torch.empty((1,), dtype=torch.int64, device=device)
+    win_order = torch.empty((capacity,), dtype=torch.int32, device=device)
+    s = _C.FrontScratch()
+    s.state, s.win_count, s.win_total = state.data_ptr(), win_count.data_ptr(), win_total.data_ptr()
+    s.win_order = win_order.data_ptr()
+    return s, (state, win_count, win_total, win_order)
+
+
+@torch.no_grad()
+def render_field_front(radiance_field, xyz_c, dirs_c, frame, render_step_size: float, stop_tau: float, rank_windows,
+                       render_bkgd=None, bg_color="white", packed: bool = False):
+    """The field + ``composite_frame`` of a frame in the intersector's tile order, front to back in rank windows with
+    early ray termination, as separately bound launches: per window ``qf_front_select``
+    (composite the previous window, select the pixels that still see something, list their samples) and the field's
+    fused kernel over that list (``forward_into``: ``order`` = the list, ``n_device`` = its length), then
+    ``qf_front_finish``.  No host wait.  ``stop_tau`` from ``early_stop_tau`` (``inf`` never stops and gives the field +
+    ``composite_frame`` pixels bit for bit), ``rank_windows`` from ``front_rank_windows``.  Returns (rgb [N,3],
+    alpha [N,1], depth [N,1], shaded_count [N] int32, evaluated_count [N] int32) -- with ``packed`` ([N,5], None, None,
+    shaded_count, evaluated_count).  What ``qf_frame_render_front`` composes into one call."""
+    if getattr(frame, "band_rows", 0):
+        raise ValueError("render_field_front: an unbanded frame is required")
+    windows = front_rank_windows(rank_windows, frame.max_hits)
+    xyz_c, dirs_c = _C.f32c(xyz_c), _C.f32c(dirs_c)
+    dev = xyz_c.device
+    n = frame.depth_c.shape[0]
+    if xyz_c.shape[0] != n or dirs_c.shape[0] != n:
+        raise ValueError(f"render_field_front: {n} slots in the frame, {xyz_c.shape[0]} positions, {dirs_c.shape[0]} directions")
+    n_rays = frame.width * frame.height
+    mode = _BG.get(bg_color, _C.BG_CUSTOM)
+    bk = _C.f32c(render_bkgd.detach().reshape(3).to(dev)) if (mode == _C.BG_CUSTOM and render_bkgd is not None) else None
+    rgb = alpha = depth = out5 = None
+    if packed:
+        out5 = torch.empty((n_rays, 5), dtype=torch.float32, device=dev)
+    else:
+        rgb = torch.empty((n_rays, 3), dtype=torch.float32, device=dev)
+        alpha = torch.empty((n_rays, 1), dtype=torch.float32, device=dev)
+        depth = torch.empty((n_rays, 1), dtype=torch.float32, device=dev)
+    shaded = torch.empty((n_rays,), dtype=torch.int32, device=dev)
+    evaluated = torch.empty((n_rays,), dtype=torch.int32, device=dev)
+    rgbs = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    sigmas = torch.empty((n,), dtype=torch.float32, device=dev)
+    _, (state, win_count, win_total, win_order) = front_scratch(n_rays, frame.tile_base.shape[0], n, dev)
+    lib = _C.lib()
+    common = (_C.ptr(rgbs), _C.ptr(sigmas), _C.ptr(frame.depth_c), float(render_step_size), _C.ptr(frame.hit_count),
+              frame.max_hits, _C.ptr(frame.tile_base), frame.width, frame.height, float(stop_tau))
+    lo = mid = 0
+    for hi in windows:
+        _C.check(lib.qf_front_select(*common, lo, mid, hi, _C.ptr(state), _C.ptr(win_count), _C.ptr(win_total),
+                                     _C.ptr(win_order), n, _C.stream()), "qf_front_select")
+        radiance_field.forward_into(xyz_c, dirs_c, rgbs, sigmas, order=win_order, n_device=win_total)
+        lo, mid = mid, hi
+    _C.check(lib.qf_front_finish(*common, lo, mid, _C.ptr(state), mode, _C.ptr(bk), _C.ptr(rgb), _C.ptr(alpha), _C.ptr(depth),
+                                 _C.ptr(out5), _C.ptr(shaded), _C.ptr(evaluated), _C.stream()), "qf_front_finish")
+    if packed:
+        return out5, None, None, shaded, evaluated
+    return rgb, alpha, depth, shaded, evaluated
 
 
 def baked_shading(mesh_intersect, uv, compressor):
