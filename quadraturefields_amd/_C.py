@@ -314,6 +314,43 @@ def stream():
     return c_void_p(raw_stream())
 
 
+class StreamCached:
+    """A value the package builds on the device behind the caller's back (a 16-bit parameter copy, a record table)
+    together with the (device, stream) it was built on and an event recorded there.  The caller can order their own
+    tensors across streams but cannot know these exist, so ``get()`` does it: on the building stream, and on any stream
+    that has asked before, it costs the current-device and raw-stream queries and a set look-up (no launch, no host
+    wait); the FIRST time another stream asks, that stream waits for the event (``hipStreamWaitEvent``, device side: all
+    of its later work is ordered behind the build) and the tensors are ``record_stream``-ed, so that dropping the cache
+    entry while that stream still reads them does not hand their memory back to the allocator early (the allocator
+    looks at the stream's progress when the block is freed, so once per stream is enough).  The raw handle of the legacy
+    default stream is the same on every device: the device ordinal is part of the identity.  Construct it right after
+    enqueuing the build."""
+    __slots__ = ("key", "value", "tensors", "event", "ordered")
+
+    def __init__(self, key, value, tensors):
+        self.key, self.value = key, value
+        self.tensors = tuple(t for t in tensors if t.is_cuda)
+        self.event, self.ordered = None, set()
+        if self.tensors:
+            self.ordered.add((torch._C._cuda_getDevice(), raw_stream()))
+            self.event = torch.cuda.Event()
+            self.event.record()
+
+    def __getitem__(self, i):              # reads as the (key, value) pair the caches used to keep
+        return (self.key, self.value)[i]
+
+    def get(self):
+        if self.event is not None:
+            here = (torch._C._cuda_getDevice(), raw_stream())
+            if here not in self.ordered:
+                cur = torch.cuda.current_stream()
+                cur.wait_event(self.event)
+                for t in self.tensors:
+                    t.record_stream(cur)
+                self.ordered.add(here)
+        return self.value
+
+
 def resolve_device(device) -> torch.device:
     """``torch.device(device)`` WITH an index: "cuda" means the current device at construction time.  The package
     compares ``device.index`` with the raw current-device ordinal (``mesh_utils._on_device``, the renderers' fast

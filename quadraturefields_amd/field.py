@@ -176,11 +176,12 @@ class Field(nn.Module):
         p = self.xyz_encoder.params
         key = (p.data_ptr(), p._version)
         cache = getattr(self, "_half_cache", None)
-        if cache is None or cache[0] != key:
+        if cache is None or cache.key != key:
             self._half_cache = cache = None    # the old copy goes before the new one is allocated
-            cache = (key, p.detach().to(torch.float16).contiguous())
+            half = p.detach().to(torch.float16).contiguous()
+            cache = _C.StreamCached(key, half, [half])     # ordered for a consumer on another stream
             self._half_cache = cache
-        return cache[1]
+        return cache.get()
 
     def density(self, x, order=None, n_device=None):
         """[N,3] in [-scale, scale] -> [N,1].  field.py:186-203, one fused launch.  ``order`` (extension): int32

@@ -191,17 +191,19 @@ class _FusedFieldBase(nn.Module):
         params = [self.mlp_base.params] + ([head_ngp] if head_ngp is not None else []) + list(head_sg or [])
         key = (dtype,) + tuple((t.data_ptr(), t._version) for t in params)
         cache = getattr(self, "_half_cache", None)
-        if cache is None or cache[0] != key:
-            self._half_cache = cache = None    # the old set goes before the new one is allocated
+        if cache is None or cache.key != key:
+            # the old set goes before the new one is allocated (a stream other than the building one that still reads it
+            # has it record_stream-ed: _C.StreamCached)
+            self._half_cache = cache = None
             cv = lambda t: t.detach().to(dtype).contiguous()
             c = {"base": cv(self.mlp_base.network_params()), "table": cv(self.mlp_base.grid_params())}
             if head_ngp is not None:
                 c["head"] = cv(head_ngp)
             if head_sg is not None:
                 c["sg"] = [cv(head_sg[0]), cv(head_sg[1]), cv(head_sg[2]), cv(head_sg[4])]
-            cache = (key, c)
+            cache = _C.StreamCached(key, c, [c["base"], c["table"]] + ([c["head"]] if "head" in c else []) + c.get("sg", []))
             self._half_cache = cache
-        return cache[1]
+        return cache.get()
 
     def _half_sg_head(self, c, head_sg) -> _C.SGHead:
         """qf_sg_head_bf16 / _f16 of the copies: w1, b1, w2 16-bit | b2 fp32 | wout 16-bit | bout fp32."""

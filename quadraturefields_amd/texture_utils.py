@@ -176,15 +176,15 @@ class FeatureCompression:
                  [self.lambdas[i] for i in range(self.num_lobes)]
         key = tuple((p.data_ptr(), p._version) for p in planes)
         cache = getattr(self, "_records", None)
-        if cache is None or cache[0] != key:
+        if cache is None or cache.key != key:
             t = self.texture_set()
             size = int(self.alpha.shape[0])
             rec = torch.empty((size * size, _C.QF_TEXEL_RECORD_BYTES), dtype=torch.uint8, device=self.alpha.device)
             _C.check(_C.lib().qf_texture_pack(ctypes.byref(t), _C.ptr(rec), _C.stream()), "qf_texture_pack")
             planes = [self.alpha, self.diffuse] + [self.sg_colors[i] for i in range(self.num_lobes)] + \
                      [self.lambdas[i] for i in range(self.num_lobes)]      # texture_set() may have made them contiguous
-            cache = self._records = (tuple((p.data_ptr(), p._version) for p in planes), rec)
-        return cache[1]
+            cache = self._records = _C.StreamCached(tuple((p.data_ptr(), p._version) for p in planes), rec, [rec])
+        return cache.get()                 # ordered for a consumer on another stream than the one that packed them
 
     def shade(self, indices, dirs):
         """Fused fetch + dequantise + spherical-Gaussian shading: (rgb [S,3], sigma [S]) from the interleaved texel

@@ -470,8 +470,9 @@ def _triangle_records(mesh_intersect, uv):
         records = torch.empty((faces.shape[0], _C.QF_TEXEL_TRIANGLE_RECORD_BYTES), dtype=torch.uint8, device=uv.device)
         _C.check(_C.lib().qf_texel_records_pack(_C.ptr(v64), _C.ptr(faces), _C.ptr(uv), faces.shape[0], _C.ptr(records),
                                                 _C.stream()), "qf_texel_records_pack")
-        cache[3], cache[4] = key, (records, uv)             # the uv tensor stays referenced: its address is the key
-    return cache[4][0]
+        # the uv tensor stays referenced: its address is the key
+        cache[3], cache[4] = key, _C.StreamCached(key, (records, uv), [records])
+    return cache[4].get()[0]                 # ordered for a consumer on another stream than the one that packed them
 
 
 def texel_indices(mesh_intersect, uv, points, index_tri, texture_size: int) -> torch.Tensor:
