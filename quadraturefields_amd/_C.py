@@ -81,6 +81,12 @@ class BakedShading(Structure):
                 ("sigmoid_codec", c_int32), ("lambda_thres", c_float)]
 
 
+class VertexBakedShading(Structure):
+    """qf_vertex_baked_shading (include/qf_vertex_baked.h): the vertex table and records of a vertex-baked frame."""
+    _fields_ = [("table", c_void_p), ("records", c_void_p), ("n_vertices", c_int64), ("stride", c_int32),
+                ("n_lobes", c_int32)]
+
+
 class FrontScratch(Structure):
     """qf_front_scratch (include/qf_hip.h): what qf_frame_render_front keeps between its launches."""
     _fields_ = [("state", c_void_p), ("win_count", c_void_p), ("win_total", c_void_p), ("win_order", c_void_p)]
@@ -227,6 +233,21 @@ _SIGNATURES = {
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 ABI_VERSION = 6              # QF_ABI_VERSION of include/qf_hip.h
+# include/qf_vertex_baked.h: an additive header of the same library (same ABI version), bound the same way
+QF_VERTEX_TRIANGLE_RECORD_BYTES = 128
+_VERTEX_BAKED_SIGNATURES = {
+    "qf_vertex_records_pack": (c_int, [_P, c_int64, _P, c_int64, _P, _P]),
+    "qf_vertex_shade_points": (c_int, [_P, c_int32, c_int32, _P, _P, _P, _P, _P, c_int64, _P, _P, _P, _P, _P]),
+    "qf_vertex_composite_tiles": (c_int, [_P, c_int32, c_int32, _P, _P, _P, _P, _P, _P, c_int32, _P, c_int32, c_int32, c_float,
+                                          c_int32, _P, c_float, _P, _P, _P, _P, _P, _P]),
+    "qf_frame_render_vertex_baked": (c_int, [_P, POINTER(FrameJob), POINTER(VertexBakedShading), c_float, _P, _P]),
+}
+
+
+def vertex_row_stride(n_lobes: int) -> int:
+    """Floats per row of a vertex table: the width 3 + 7L + 1 rounded up to a 64-byte line (16 / 32 / 48 / 64 for
+    1 / 2 / 6 / 8 lobes)."""
+    return 16 * ((3 + 7 * int(n_lobes) + 1 + 15) // 16)
 
 _lib = None
 
@@ -240,7 +261,7 @@ def lib() -> ctypes.CDLL:
                 f"{LIB_PATH} is missing: build it with `python -m quadraturefields_amd.build` "
                 "(hipcc --offload-arch=gfx950).  quadraturefields_amd has no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in _SIGNATURES.items():
+        for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_VERTEX_BAKED_SIGNATURES.items()):
             fn = getattr(handle, name)   # AttributeError if the symbol is not exported
             fn.restype = restype
             fn.argtypes = argtypes

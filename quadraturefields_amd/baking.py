@@ -8,6 +8,8 @@
   host wait (``qf_bake_compact_texels`` / ``qf_bake_encode_texels``).
 * ``texel_positions``: the texel-position map ``V`` itself from a UV-mapped mesh -- the fill of the reference's UV stage
   (``examples/parameterization_utils.py:97-153``), one HIP call (``qf_texel_positions``).
+* ``bake_vertex_features``: the vertex-baked asset of ``render_image_finetune_baking_with_occgrid`` -- the SG field's
+  features once per mesh vertex.
 * ``triangle_max_weights`` / ``prune_faces``: ``examples/prune_mesh_after_finetuning.py:323-373`` -- per-triangle
   maximum compositing weight over the training views, faces below 1e-3 dropped.
 """
@@ -173,6 +175,25 @@ def bake_texture_set(radiance_field_sg, radiance_field, V, compressor, rows_per_
                      "qf_bake_encode_texels")
     compressor._records = None            # the planes changed behind torch's version counters: rebuild on next use
     return mask, counts.sum()
+
+
+@torch.no_grad()
+def bake_vertex_features(radiance_field, mesh_intersect, batch_size: int = 1000000) -> torch.Tensor:
+    """The vertex-baked asset of ``render_image_finetune_baking_with_occgrid`` (utils.py:819-836): the SG field's feature
+    vector ``radiance_field.features`` -- [diffuse3 | (axis3, lambda, colour3) * L | sigma] -- at every vertex of the mesh,
+    float32 [V, 3 + 7L + 1] on the device.  The reference evaluates it at the three corners of every sample's triangle,
+    every frame; the field depends on the position alone, so once per vertex gives the same values
+    (``utils.vertex_baked_shading`` pads the rows for the kernels).  Chunks of ``batch_size`` vertices as the reference's
+    loop (:831-833); the values do not depend on it."""
+    from .radiance_fields.ngp import NGPRadianceFieldSGNew
+    if not isinstance(radiance_field, NGPRadianceFieldSGNew):
+        raise NotImplementedError("bake_vertex_features takes an NGPRadianceFieldSGNew: the table holds its SG features")
+    vertices = _C.f32c(mesh_intersect.vertices)
+    n = vertices.shape[0]
+    out = torch.empty((n, 3 + 7 * radiance_field.num_g_lobes + 1), dtype=torch.float32, device=vertices.device)
+    for b in range(0, n, int(batch_size)):
+        out[b:b + batch_size] = radiance_field.features(vertices[b:b + batch_size])
+    return out
 
 
 def triangle_max_weights(weights: torch.Tensor, index_tri: torch.Tensor, out: torch.Tensor) -> torch.Tensor:

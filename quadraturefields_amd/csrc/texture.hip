@@ -14,13 +14,7 @@ __global__ void texel_records_kernel(const double *vertices, const int64_t *face
     for (int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; f < n_faces; f += (int64_t)gridDim.x * blockDim.x) {
         const int64_t ia = faces[f * 3], ib = faces[f * 3 + 1], ic = faces[f * 3 + 2];
         TexelRecord r;
-        r.ax = vertices[ia * 3]; r.ay = vertices[ia * 3 + 1]; r.az = vertices[ia * 3 + 2];
-        r.e0x = vertices[ib * 3] - r.ax; r.e0y = vertices[ib * 3 + 1] - r.ay; r.e0z = vertices[ib * 3 + 2] - r.az;
-        r.e1x = vertices[ic * 3] - r.ax; r.e1y = vertices[ic * 3 + 1] - r.ay; r.e1z = vertices[ic * 3 + 2] - r.az;
-        r.d00 = (r.e0x * r.e0x + r.e0y * r.e0y) + r.e0z * r.e0z;
-        r.d01 = (r.e0x * r.e1x + r.e0y * r.e1y) + r.e0z * r.e1z;
-        r.d11 = (r.e1x * r.e1x + r.e1y * r.e1y) + r.e1z * r.e1z;
-        r.inv = 1.0 / (r.d00 * r.d11 - r.d01 * r.d01);
+        triangle_record_geometry(vertices, ia, ib, ic, r);
         r.uv[0] = uv[ia * 2]; r.uv[1] = uv[ia * 2 + 1];
         r.uv[2] = uv[ib * 2]; r.uv[3] = uv[ib * 2 + 1];
         r.uv[4] = uv[ic * 2]; r.uv[5] = uv[ic * 2 + 1];

@@ -19,8 +19,27 @@ struct TexelRecord {
 };
 static_assert(sizeof(TexelRecord) == 128, "one 128-byte line per triangle");
 
-__device__ __forceinline__ void texel_from_record(const TexelRecord &r, float px, float py, float pz, int texture_size,
-                                                  int64_t out[2])
+// The 13 doubles every per-triangle record starts with (TexelRecord here, VertexTriRecord in vertex_baked_device.h): corner
+// a, edges e0 / e1, their three dot products and the reciprocal determinant, from the float64 vertices ia, ib, ic.  One
+// definition, hence the same bits in both record kinds.
+template <class R>
+__device__ __forceinline__ void triangle_record_geometry(const double *__restrict__ vertices, int64_t ia, int64_t ib,
+                                                         int64_t ic, R &r)
+{
+#pragma clang fp contract(off)
+    r.ax = vertices[ia * 3]; r.ay = vertices[ia * 3 + 1]; r.az = vertices[ia * 3 + 2];
+    r.e0x = vertices[ib * 3] - r.ax; r.e0y = vertices[ib * 3 + 1] - r.ay; r.e0z = vertices[ib * 3 + 2] - r.az;
+    r.e1x = vertices[ic * 3] - r.ax; r.e1y = vertices[ic * 3 + 1] - r.ay; r.e1z = vertices[ic * 3 + 2] - r.az;
+    r.d00 = (r.e0x * r.e0x + r.e0y * r.e0y) + r.e0z * r.e0z;
+    r.d01 = (r.e0x * r.e1x + r.e0y * r.e1y) + r.e0z * r.e1z;
+    r.d11 = (r.e1x * r.e1x + r.e1y * r.e1y) + r.e1z * r.e1z;
+    r.inv = 1.0 / (r.d00 * r.d11 - r.d01 * r.d01);
+}
+
+// The float64 Cramer barycentrics of a point in its triangle from the 13 doubles (trimesh's points_to_barycentric,
+// method 'cramer'): b[0..2] for corners a, b, c.
+template <class R>
+__device__ __forceinline__ void barycentrics_from_record(const R &r, float px, float py, float pz, double b[3])
 {
 #pragma clang fp contract(off)
     const double wx = (double)px - r.ax, wy = (double)py - r.ay, wz = (double)pz - r.az;
@@ -28,7 +47,18 @@ __device__ __forceinline__ void texel_from_record(const TexelRecord &r, float px
     const double d12 = (r.e1x * wx + r.e1y * wy) + r.e1z * wz;
     const double b2d = (r.d00 * d12 - r.d01 * d02) * r.inv;
     const double b1d = (r.d11 * d02 - r.d01 * d12) * r.inv;
-    const double b0d = 1.0 - b1d - b2d;
+    b[0] = 1.0 - b1d - b2d;
+    b[1] = b1d;
+    b[2] = b2d;
+}
+
+__device__ __forceinline__ void texel_from_record(const TexelRecord &r, float px, float py, float pz, int texture_size,
+                                                  int64_t out[2])
+{
+#pragma clang fp contract(off)
+    double bd[3];
+    barycentrics_from_record(r, px, py, pz, bd);
+    const double b0d = bd[0], b1d = bd[1], b2d = bd[2];
     float b0 = fminf(fmaxf((float)b0d, 0.0f), 1.0f);
     float b1 = fminf(fmaxf((float)b1d, 0.0f), 1.0f);
     float b2 = fminf(fmaxf((float)b2d, 0.0f), 1.0f);

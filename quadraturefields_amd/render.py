@@ -420,6 +420,96 @@ class FrameRenderer:
         return rgb, alpha, depth, n_samples
 
 
+    def _render_vertex_baked_front_to_back(self, origins, viewdirs, vertex_features, camera, stop_tau: float):
+        """``_render_baked_front_to_back`` for the vertex-baked asset (``qf_vertex_composite_tiles``, DESIGN.md section
+        3.5d): (rgb, alpha, depth, frame) without a host wait, ``frame.shaded_count`` = the samples of each pixel that
+        contributed.  One bound call (``qf_frame_render_vertex_baked``) when the frame is the library's fixed sequence,
+        the separately bound launches otherwise; same pixels."""
+        ri = self.mesh_intersect.rayintersector
+        k = self.mesh_intersect.num_intersections
+        prepared = None
+        if ri.fused_frame_ready(camera, k) and torch._C._cuda_getDevice() == ri.device.index:
+            prepared = ri.fused_frame_job(origins, viewdirs, k, camera, want_tri=True)
+        if prepared is not None:
+            job, frame, token = prepared
+            dev, n = ri.device, frame.width * frame.height
+            shading, keep = utils.vertex_baked_shading_struct(self.mesh_intersect, vertex_features)
+            rgb = torch.empty((n, 3), dtype=torch.float32, device=dev)
+            alpha = torch.empty((n, 1), dtype=torch.float32, device=dev)
+            depth = torch.empty((n, 1), dtype=torch.float32, device=dev)
+            shaded = torch.empty((n,), dtype=torch.int32, device=dev)
+            job.out_rgb, job.out_alpha, job.out_depth = rgb.data_ptr(), alpha.data_ptr(), depth.data_ptr()
+            job.delta_const, job.bg_mode = float(self.render_step_size), utils._BG.get(self.bg_color, _C.BG_CUSTOM)
+            ri.last_route = "frame+cull" if job.cull_chunks & 1 else "frame"
+            _C.check(_C.lib().qf_frame_render_vertex_baked(ri._handle, ctypes.byref(job), ctypes.byref(shading), stop_tau,
+                                                           _C.ptr(shaded), _C.stream()), "qf_frame_render_vertex_baked")
+            ri.fused_frame_done(frame, token)
+            frame._keep = frame._keep + keep      # referenced until their readers ran
+        else:
+            frame = ri.sample_frame_device(origins, viewdirs, k, camera, want_tri=True)
+            _, xyz_c, dirs_c = ri.last_layout
+            rgb, alpha, depth, shaded = utils.shade_composite_vertex_baked_frame(
+                self.mesh_intersect, vertex_features, xyz_c, dirs_c, frame, self.render_step_size, stop_tau,
+                bg_color=self.bg_color)
+        frame.shaded_count = shaded
+        return rgb, alpha, depth, frame
+
+    @torch.no_grad()
+    def render_vertex_baked_async(self, origins, viewdirs, vertex_features, camera, early_stop_eps=None):
+        """``render_vertex_baked`` for a camera frame without a host wait: (rgb, alpha, depth, frame), always through the
+        front-to-back launch (``early_stop_eps`` None or 0 never stops: the default route's pixels bit for bit)."""
+        if camera is None:
+            raise NotImplementedError("render_vertex_baked_async needs a camera frame")
+        stop_tau = utils.early_stop_tau(0.0 if early_stop_eps is None else early_stop_eps)
+        return self._render_vertex_baked_front_to_back(origins, viewdirs, vertex_features, camera, stop_tau)
+
+    @torch.no_grad()
+    def render_vertex_baked(self, origins, viewdirs, vertex_features, image_width: int = 0, camera=None, early_stop_eps=None):
+        """Vertex-baked variant (``utils.render_image_finetune_baking_with_occgrid``): the SG features live at the mesh
+        vertices (``vertex_features`` [V, 3 + 7L + 1], ``baking.bake_vertex_features``) and every quadrature point shades
+        the barycentric blend of its triangle's three rows.  With a ``camera`` the frame stays in the intersector's tile
+        order: tile pack with triangle ids -> ``qf_vertex_shade_points`` -> tile compositor; same pixels as that function
+        on the ray-major samples, bit for bit.  ``early_stop_eps`` (camera frames only; None = the route above, a float
+        in [0, 1) otherwise): shading and compositing are ONE launch that walks each pixel front to back and stops
+        reading vertex rows once the transmittance in front of the next sample has fallen below it
+        (``qf_vertex_composite_tiles`` -- the one bound call ``qf_frame_render_vertex_baked`` when the frame is the
+        library's fixed sequence; 0 never stops and gives the route above bit for bit).  ``last_frame.shaded_count`` of
+        the intersector then holds the samples of each pixel that contributed.  Returns (rgb, alpha, depth, n_samples)."""
+        n_rays = origins.shape[0]
+        if early_stop_eps is not None:
+            stop_tau = utils.early_stop_tau(early_stop_eps)
+            if camera is None:
+                raise NotImplementedError("early_stop_eps needs a camera frame: the ray-major route shades every sample")
+        utils.vertex_baked_shading(self.mesh_intersect, vertex_features)      # a malformed table raises before any sampling
+        if early_stop_eps is not None:
+            ri = self.mesh_intersect.rayintersector
+            rgb, alpha, depth, frame = self._render_vertex_baked_front_to_back(origins, viewdirs, vertex_features, camera,
+                                                                               stop_tau)
+            return rgb, alpha, depth, ri.frame_samples(frame)
+        if camera is not None:
+            ri = self.mesh_intersect.rayintersector
+            data = ri.sample_device(origins, viewdirs, self.mesh_intersect.num_intersections, camera.width, camera,
+                                    lean=True, want_tri=True)
+            if data is not None and ri.last_frame is not None and ri.last_frame.tri_c is not None:
+                frame = ri.last_frame
+                _, xyz_c, dirs_c = ri.last_layout
+                rgbs, sigmas = utils.shade_vertex_baked_points(self.mesh_intersect, vertex_features, xyz_c, frame.tri_c, dirs_c)
+                rgb, alpha, depth, _ = utils.composite_frame(rgbs, sigmas, frame, self.render_step_size,
+                                                             bg_color=self.bg_color)
+                return rgb, alpha, depth, ri.frame_samples()
+            if data is None:
+                return self._background(n_rays, origins.device)
+        data = self.mesh_intersect.sampling_raytrace_device(viewdirs, origins, image_width=image_width, camera=camera,
+                                                            layout=False)     # no field evaluation: no processing order
+        if data is None:
+            return self._background(n_rays, origins.device)
+        rays = Rays(origins=origins, viewdirs=viewdirs)
+        rgb, alpha, depth, n_samples, *_ = utils.render_image_finetune_baking_with_occgrid(
+            self.radiance_field, None, rays, data, render_step_size=self.render_step_size,
+            mesh_intersect=self.mesh_intersect, vertex_features=vertex_features, bg_color=self.bg_color)
+        return rgb, alpha, depth, n_samples
+
+
 def area_downsample(img: torch.Tensor, factor: int) -> torch.Tensor:
     """cv2.resize(..., INTER_AREA) by an integer factor (train_finetune.py:624-627) == box average."""
     if factor == 1:

@@ -657,6 +657,156 @@ def shade_composite_baked_frame(mesh_intersect, uv, compressor, xyz_c, dirs_c, f
     return rgb, alpha, depth, shaded
 
 
+def _vertex_lobes(width: int) -> int:
+    lobes, rest = divmod(int(width) - 4, 7)
+    if rest or not 1 <= lobes <= _C.QF_MAX_LOBES:
+        raise ValueError(f"vertex features must have 3 + 7 L + 1 columns with 1 <= L <= {_C.QF_MAX_LOBES}, got {width}")
+    return lobes
+
+
+def vertex_baked_shading(mesh_intersect, vertex_features):
+    """What the vertex-baked kernels read, on the device: (table, records).  ``table``: float32
+    [V, stride], ``vertex_features`` ([V, 3 + 7L + 1], ``baking.bake_vertex_features``) with every row zero-padded to
+    ``_C.vertex_row_stride(L)`` floats (64-byte lines).  ``records``: the 128-byte vertex-triangle records of
+    ``qf_vertex_records_pack`` from the mesh's float64 vertices.  Both are built on first use and cached the way
+    ``_triangle_records`` caches its table: the records per vertex array of the mesh, the padded table per (address,
+    version, shape) of the feature tensor, each ordered for a consumer on another stream than the one that built it."""
+    cache = getattr(mesh_intersect, "_vertex_baked_cache", None)
+    if cache is None or cache[0] is not mesh_intersect.mesh.vertices:
+        dev = mesh_intersect.device
+        v64 = torch.from_numpy(np.ascontiguousarray(mesh_intersect.mesh.vertices, dtype=np.float64)).to(dev)
+        faces = torch.from_numpy(np.ascontiguousarray(mesh_intersect.mesh.faces, dtype=np.int64)).to(dev)
+        records = torch.empty((faces.shape[0], _C.QF_VERTEX_TRIANGLE_RECORD_BYTES), dtype=torch.uint8, device=dev)
+        _C.check(_C.lib().qf_vertex_records_pack(_C.ptr(v64), v64.shape[0], _C.ptr(faces), faces.shape[0], _C.ptr(records),
+                                                 _C.stream()), "qf_vertex_records_pack")
+        # v64 and faces stay referenced: the pack may still be reading them on its stream
+        cache = mesh_intersect._vertex_baked_cache = [mesh_intersect.mesh.vertices,
+                                                      _C.StreamCached(None, (records, v64, faces), [records]), None, None]
+    feats = torch.as_tensor(vertex_features)
+    if feats.dim() != 2 or feats.shape[0] != mesh_intersect.mesh.vertices.shape[0]:
+        raise ValueError(f"vertex_features must be [V, 3 + 7L + 1] with V = {mesh_intersect.mesh.vertices.shape[0]} rows, "
+                         f"got {tuple(feats.shape)}")
+    lobes = _vertex_lobes(feats.shape[1])
+    key = (feats.data_ptr(), feats._version, tuple(feats.shape), feats.dtype, feats.device)
+    if cache[2] != key:
+        table = torch.zeros((feats.shape[0], _C.vertex_row_stride(lobes)), dtype=torch.float32, device=mesh_intersect.device)
+        table[:, :feats.shape[1]] = feats.detach().to(mesh_intersect.device)
+        # the feature tensor stays referenced: its address is the key
+        cache[2], cache[3] = key, _C.StreamCached(key, (table, feats), [table])
+    return cache[3].get()[0], cache[1].get()[0]
+
+
+def vertex_baked_shading_struct(mesh_intersect, vertex_features):
+    """The ``qf_vertex_baked_shading`` of a (mesh, feature tensor): (struct, tensors it points at -- keep them referenced
+    until the launch that reads them ran)."""
+    table, records = vertex_baked_shading(mesh_intersect, vertex_features)
+    s = _C.VertexBakedShading()
+    s.table, s.records = table.data_ptr(), records.data_ptr()
+    s.n_vertices, s.stride, s.n_lobes = int(table.shape[0]), int(table.shape[1]), _vertex_lobes(vertex_features.shape[1])
+    return s, (table, records)
+
+
+@torch.no_grad()
+def shade_vertex_baked_points(mesh_intersect, vertex_features, points, index_tri, dirs, n_device=None,
+                              want_features: bool = False):
+    """(rgb [n,3], sigma [n]) of samples given by position and triangle from the vertex-baked features: the unclamped
+    fp32 barycentrics of the sample in its triangle, the blend of the triangle's three vertex rows, SG shading of the
+    blend -- utils.py:822-840 in one launch (``qf_vertex_shade_points``).  ``want_features``: the blend itself comes
+    back as a third value, [n, 3 + 7L + 1].  ``n_device``: see ``shade_baked_points``."""
+    table, records = vertex_baked_shading(mesh_intersect, vertex_features)
+    lobes = _vertex_lobes(vertex_features.shape[1])
+    points, dirs = _C.f32c(points), _C.f32c(dirs)
+    # int32 ids (what the tile pack writes) go to the kernel as they are; anything else as the reference's int64
+    tri32 = index_tri.contiguous() if index_tri.dtype == torch.int32 else None
+    tri64 = None if tri32 is not None else _C.i64c(index_tri)
+    n = points.shape[0]
+    rgb = torch.empty((n, 3), dtype=torch.float32, device=points.device)
+    sigma = torch.empty((n,), dtype=torch.float32, device=points.device)
+    feats = torch.empty((n, vertex_features.shape[1]), dtype=torch.float32, device=points.device) if want_features else None
+    _C.check(_C.lib().qf_vertex_shade_points(
+        _C.ptr(table), int(table.shape[1]), lobes, _C.ptr(records), _C.ptr(points), _C.ptr(tri64), _C.ptr(tri32), _C.ptr(dirs),
+        n, _C.ptr(n_device, torch.int64), _C.ptr(feats), _C.ptr(rgb), _C.ptr(sigma), _C.stream()), "qf_vertex_shade_points")
+    if want_features:
+        return rgb, sigma, feats
+    return rgb, sigma
+
+
+@torch.no_grad()
+def shade_composite_vertex_baked_frame(mesh_intersect, vertex_features, xyz_c, dirs_c, frame, render_step_size: float,
+                                       stop_tau: float, render_bkgd=None, bg_color="white", packed: bool = False):
+    """``shade_vertex_baked_points`` + ``composite_frame`` of a frame in the intersector's tile order as ONE launch that
+    walks every pixel front to back (``qf_vertex_composite_tiles``) and stops reading vertex rows once the optical depth
+    in front of a pixel's next sample exceeds ``stop_tau`` (``early_stop_tau``; ``inf`` never stops and gives the two
+    calls' pixels bit for bit).  Arguments and returns as ``shade_composite_baked_frame``."""
+    if getattr(frame, "band_rows", 0) or frame.tri_c is None:
+        raise ValueError("shade_composite_vertex_baked_frame: an unbanded frame with triangle ids (want_tri) is required")
+    shading, keep = vertex_baked_shading_struct(mesh_intersect, vertex_features)
+    xyz_c, dirs_c = _C.f32c(xyz_c), _C.f32c(dirs_c)
+    dev = xyz_c.device
+    n = frame.depth_c.shape[0]
+    if xyz_c.shape[0] != n or dirs_c.shape[0] != n or frame.tri_c.shape[0] != n:
+        raise ValueError(f"shade_composite_vertex_baked_frame: {n} slots in the frame, {xyz_c.shape[0]} positions, "
+                         f"{dirs_c.shape[0]} directions, {frame.tri_c.shape[0]} triangle ids")
+    n_rays = frame.width * frame.height
+    mode = _BG.get(bg_color, _C.BG_CUSTOM)
+    bk = _C.f32c(render_bkgd.detach().reshape(3).to(dev)) if (mode == _C.BG_CUSTOM and render_bkgd is not None) else None
+    rgb = alpha = depth = out5 = None
+    if packed:
+        out5 = torch.empty((n_rays, 5), dtype=torch.float32, device=dev)
+    else:
+        rgb = torch.empty((n_rays, 3), dtype=torch.float32, device=dev)
+        alpha = torch.empty((n_rays, 1), dtype=torch.float32, device=dev)
+        depth = torch.empty((n_rays, 1), dtype=torch.float32, device=dev)
+    shaded = torch.empty((n_rays,), dtype=torch.int32, device=dev)
+    _C.check(_C.lib().qf_vertex_composite_tiles(
+        shading.table, shading.stride, shading.n_lobes, shading.records, _C.ptr(xyz_c), _C.ptr(dirs_c), _C.ptr(frame.depth_c),
+        _C.ptr(frame.tri_c, torch.int32), _C.ptr(frame.hit_count), frame.max_hits, _C.ptr(frame.tile_base), frame.width,
+        frame.height, float(render_step_size), mode, _C.ptr(bk), float(stop_tau), _C.ptr(rgb), _C.ptr(alpha), _C.ptr(depth),
+        _C.ptr(out5), _C.ptr(shaded), _C.stream()), "qf_vertex_composite_tiles")
+    if packed:
+        return out5, None, None, shaded
+    return rgb, alpha, depth, shaded
+
+
+@torch.no_grad()
+def render_image_finetune_baking_with_occgrid(
+    radiance_field: torch.nn.Module, estimator, rays: Rays, data, near_plane: float = 0.0, far_plane: float = 1e10,
+    render_step_size: float = 1e-3, render_bkgd: Optional[torch.Tensor] = None, cone_angle: float = 0.0,
+    alpha_thre: float = 0.0, test_chunk_size: int = 8192, timestamps: Optional[torch.Tensor] = None, mesh_intersect=None,
+    mesh_finetune=None, scaling=1 / 128, vertex_features=None, bg_color="white",
+):
+    """Render from SG features kept at the mesh vertices -- utils.py:733-861.  Returns the reference's 8-tuple (colors,
+    opacities, depths, n_samples, weights, positions, rays, 0); ``positions`` is, as there, the three corner positions of
+    every sample's triangle, [3n, 3].  The reference evaluates ``radiance_field.features`` at those 3n corners on every
+    call; here the field is evaluated once per VERTEX (``baking.bake_vertex_features``: the same values, the field being a
+    function of the position) and the samples gather: ``vertex_features`` (extension) takes that table from the caller,
+    ``None`` bakes it once per call.  ``bg_color`` (extension): the reference composites on white.
+    The view direction of a sample is the loader's ``dirs`` (``d / (|d| + 1e-7)``, what every other renderer here and the
+    tile pack use) where the reference indexes ``rays.viewdirs`` (:840): one ulp apart, and the camera frame of
+    ``FrameRenderer.render_vertex_baked`` then equals this function bit for bit."""
+    if timestamps is not None:
+        raise NotImplementedError("dynamic (D-NeRF) fields are out of scope")
+    rays, rays_shape, num_rays = _flatten_rays(rays)
+    device = mesh_intersect.device
+    if vertex_features is None:
+        from .baking import bake_vertex_features
+        vertex_features = bake_vertex_features(radiance_field, mesh_intersect)
+    xyzs, dirs, index_ray, ts, index_tri, origins = _to_device(data, device)
+    if isinstance(data, (SampleSet, SampleWindow)):
+        # the device loader's own pack: sorted by (ray, depth) and not displaced since (no deformation here), so the
+        # re-sort of sampling_indexing is the identity and the constant step needs no boundaries
+        points, depth, deltas, boundary = xyzs, ts, float(mesh_intersect.render_step_size), None
+    else:
+        points, deltas, boundary, dirs, index_ray, depth, index_tri, _ = mesh_intersect.sampling_indexing(
+            xyzs, origins, dirs, index_ray, ts, index_tri)
+    rgbs, sigmas = shade_vertex_baked_points(mesh_intersect, vertex_features, points, index_tri, dirs)
+    rgb, opacity, _, depth_img, weights = derive_properties(
+        rgbs, sigmas, depth, deltas, boundary, index_ray, bg_color=bg_color, render_bkgd=None, N=num_rays)
+    corners = mesh_intersect.vertices[_faces_on_device(mesh_intersect)[index_tri]].reshape(-1, 3)
+    return (rgb.view((*rays_shape[:-1], -1)), opacity.view((*rays_shape[:-1], -1)),
+            depth_img.view((*rays_shape[:-1], -1)), xyzs.shape[0], weights, corners, rays, 0)
+
+
 def render_image_with_occgrid(
     radiance_field: torch.nn.Module, estimator, rays: Rays, near_plane: float = 0.0, far_plane: float = 1e10,
     render_step_size: float = 1e-3, render_bkgd: Optional[torch.Tensor] = None, cone_angle: float = 0.0,
