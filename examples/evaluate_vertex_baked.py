@@ -4,6 +4,7 @@
     python examples/evaluate_vertex_baked.py --synthetic --root ROOT --num_lobes 6 --log2_hashmap_size 19
                                              --ckpt_path ROOT/fit_sg.pth [--early_stop_eps E] [--mesh_path MESH]
                                              [--size 200] [--views 4] [--up_sample 1] [--shells 2] [--subdivisions 3]
+                                             [--features PATH]
 
 The mesh is ``--mesh_path`` or, without it, the shell mesh ``examples/fit_sg_synthetic.py`` fits on (``--shells``,
 ``--subdivisions``); the field is ``--ckpt_path``'s ``radiance_field`` (what ``fit_sg_synthetic.py --out`` wrote) or, if
@@ -12,7 +13,9 @@ table goes to ``ROOT/vertex_features.npy``; every orbit view is rendered by ``Fr
 scored by ``metrics.FrameScorer`` against the SG field's own render of the view on the same mesh at ``up_sample`` 1, as
 ``examples/evaluate_baked_textures.py --synthetic`` scores a texture set -- the score is what interpolating the features
 inside a triangle costs.  Prints PSNR / SSIM (and one JSON line); with ``--early_stop_eps`` the frame is rendered front to
-back with early ray termination and the share of the samples that were shaded is printed too.
+back with early ray termination and the share of the samples that were shaded is printed too.  ``--features PATH`` loads
+a [V, 3 + 7L + 1] table (``vertex_features.npy``, or what ``examples/finetune_vertex_baked.py`` wrote) instead of baking
+one; nothing is written then.
 """
 import argparse
 import json
@@ -43,6 +46,7 @@ def parse(argv):
     ap.add_argument("--views", type=int, default=4, help="orbit cameras")
     ap.add_argument("--shells", type=int, default=2)
     ap.add_argument("--subdivisions", type=int, default=3)
+    ap.add_argument("--features", type=str, default="", help="load this vertex table (.npy) instead of baking one")
     return ap.parse_args(argv)
 
 
@@ -75,10 +79,14 @@ def main(argv=None):
     sg = sg.to(device).eval()
     os.makedirs(args.root, exist_ok=True)
     with torch.no_grad():
-        features = baking.bake_vertex_features(sg, mesh_intersect)
-        path = os.path.join(args.root, "vertex_features.npy")
-        np.save(path, features.cpu().numpy())
-        print(f"baked {features.shape[0]} vertices x {features.shape[1]} columns ({features.numel() * 4 / 1e6:.2f} MB) -> {path}")
+        if args.features:
+            features = torch.from_numpy(np.load(args.features).astype(np.float32)).to(device)
+            print(f"loaded {features.shape[0]} vertices x {features.shape[1]} columns from {args.features}")
+        else:
+            features = baking.bake_vertex_features(sg, mesh_intersect)
+            path = os.path.join(args.root, "vertex_features.npy")
+            np.save(path, features.cpu().numpy())
+            print(f"baked {features.shape[0]} vertices x {features.shape[1]} columns ({features.numel() * 4 / 1e6:.2f} MB) -> {path}")
         renderer = FrameRenderer(mesh_intersect, sg, render_step_size=5e-3)
         size = args.size
         focal = synthetic.lego_focal(size)

@@ -242,6 +242,10 @@ _VERTEX_BAKED_SIGNATURES = {
                                           c_int32, _P, c_float, _P, _P, _P, _P, _P, _P]),
     "qf_frame_render_vertex_baked": (c_int, [_P, POINTER(FrameJob), POINTER(VertexBakedShading), c_float, _P, _P]),
 }
+# include/qf_vertex_train.h: the backward of qf_vertex_shade_points, additive in the same way
+_VERTEX_TRAIN_SIGNATURES = {
+    "qf_vertex_shade_points_backward": (c_int, [_P, c_int32, c_int32, _P, c_int64, _P, _P, _P, _P, c_int64, _P, _P, _P, _P, _P]),
+}
 
 
 def vertex_row_stride(n_lobes: int) -> int:
@@ -261,7 +265,8 @@ def lib() -> ctypes.CDLL:
                 f"{LIB_PATH} is missing: build it with `python -m quadraturefields_amd.build` "
                 "(hipcc --offload-arch=gfx950).  quadraturefields_amd has no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_VERTEX_BAKED_SIGNATURES.items()):
+        for name, (restype, argtypes) in (list(_SIGNATURES.items()) + list(_VERTEX_BAKED_SIGNATURES.items())
+                                          + list(_VERTEX_TRAIN_SIGNATURES.items())):
             fn = getattr(handle, name)   # AttributeError if the symbol is not exported
             fn.restype = restype
             fn.argtypes = argtypes

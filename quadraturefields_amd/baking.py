@@ -10,6 +10,8 @@
   (``examples/parameterization_utils.py:97-153``), one HIP call (``qf_texel_positions``).
 * ``bake_vertex_features``: the vertex-baked asset of ``render_image_finetune_baking_with_occgrid`` -- the SG field's
   features once per mesh vertex.
+* ``VertexBakedFeatures`` / ``finetune_vertex_features``: that table as a trainable module, and the loop that fits it to
+  images through the differentiable vertex shading.
 * ``triangle_max_weights`` / ``prune_faces``: ``examples/prune_mesh_after_finetuning.py:323-373`` -- per-triangle
   maximum compositing weight over the training views, faces below 1e-3 dropped.
 """
@@ -194,6 +196,107 @@ def bake_vertex_features(radiance_field, mesh_intersect, batch_size: int = 10000
     for b in range(0, n, int(batch_size)):
         out[b:b + batch_size] = radiance_field.features(vertices[b:b + batch_size])
     return out
+
+
+class VertexBakedFeatures(torch.nn.Module):
+    """The vertex-baked asset as something that trains: ONE parameter ``table``, float32
+    [V, ``_C.vertex_row_stride(L)``] -- the rows of ``bake_vertex_features`` zero-padded to 64-byte lines, which is the
+    layout the kernels read, so they read the parameter in place and no padded copy is rebuilt after an optimiser step.
+    Every function that takes ``vertex_features`` takes this module too and then uses its table directly; the pixels
+    equal those of ``features()`` passed as a plain tensor.  The type decides, not the shape: 32 columns is both the
+    stride of 2 lobes and the width of 4.
+
+    ``features``: a [V, 3 + 7L + 1] tensor (any device; the table lives on ``device``, default the tensor's).
+    ``train_density``: whether the differentiable route hands the density column a gradient (``finetune_vertex_features``
+    sets it per run; stage 5's rule is colours over fixed densities)."""
+
+    def __init__(self, features, device=None, train_density: bool = True):
+        super().__init__()
+        feats = torch.as_tensor(features)
+        if feats.dim() != 2 or feats.shape[0] < 1:
+            raise ValueError(f"vertex features must be [V, 3 + 7L + 1] with V >= 1, got {tuple(feats.shape)}")
+        lobes, rest = divmod(int(feats.shape[1]) - 4, 7)
+        if rest or not 1 <= lobes <= _C.QF_MAX_LOBES:
+            raise ValueError(f"vertex features must have 3 + 7 L + 1 columns with 1 <= L <= {_C.QF_MAX_LOBES}, "
+                             f"got {feats.shape[1]}")
+        self.n_lobes = lobes
+        self.train_density = bool(train_density)
+        table = torch.zeros((feats.shape[0], _C.vertex_row_stride(lobes)), dtype=torch.float32,
+                            device=feats.device if device is None else device)
+        table[:, :feats.shape[1]] = feats.detach().to(table.device, torch.float32)
+        if table.data_ptr() % 64:
+            raise RuntimeError("the allocator returned a vertex table that is not 64-byte aligned")
+        self.table = torch.nn.Parameter(table)
+
+    @classmethod
+    def from_field(cls, radiance_field, mesh_intersect, batch_size: int = 1000000):
+        """The table of ``bake_vertex_features(radiance_field, mesh_intersect)``."""
+        return cls(bake_vertex_features(radiance_field, mesh_intersect, batch_size))
+
+    @property
+    def width(self) -> int:
+        return 3 + 7 * self.n_lobes + 1
+
+    def features(self) -> torch.Tensor:
+        """The detached [V, 3 + 7L + 1] view of the table: what ``vertex_features.npy`` holds."""
+        return self.table.detach()[:, :self.width]
+
+    def check_rows(self, n_vertices: int) -> None:
+        if self.table.shape[0] != n_vertices:
+            raise ValueError(f"vertex_features must have V = {n_vertices} rows, got {tuple(self.table.shape)}")
+
+
+def finetune_vertex_features(module, mesh_intersect, next_batch, steps: int, lr: float = 1e-2, train_density: bool = False,
+                             bg_color="white", render_step_size=None):
+    """Fit a ``VertexBakedFeatures`` to images: ``steps`` times ``next_batch() -> (Rays,
+    pixels [n, 3])`` (random training rays, as train_fit_sg.py's loop draws them) -> ray-major intersection
+    (``sampling_raytrace_device(..., layout=False)``) -> ``utils.render_image_finetune_baking_with_occgrid`` on the module
+    under autograd -> ``smooth_l1_loss`` -> ``optim.Adam`` (eps 1e-15), whose update of a zero gradient from zero moments
+    is zero: the pad columns stay exactly zero.  ``train_density`` False (stage 5's rule: colours train over fixed
+    densities) leaves the density column bit for bit; True trains it too and clamps it at >= 0 after every step, which
+    keeps the compositor inside its documented domain.  A batch none of whose rays hits the mesh is skipped (its loss is
+    recorded from the background alone).  Returns the loss history, a list of floats read back once at the end."""
+    from . import utils
+    from .optim import Adam
+    if not isinstance(module, VertexBakedFeatures):
+        raise TypeError("finetune_vertex_features takes a VertexBakedFeatures")
+    # the renderer composites with the mesh's step (the loader's pack carries no deltas): a value given here replaces it
+    # for the run
+    was_step = mesh_intersect.render_step_size
+    step_size = float(was_step if render_step_size is None else render_step_size)
+    mesh_intersect.render_step_size = step_size
+    optimizer = Adam([module.table], lr=lr, eps=1e-15)
+    was_density, was_grad = module.train_density, module.table.requires_grad
+    module.train_density = bool(train_density)
+    module.table.requires_grad_(True)
+    sigma_col = module.width - 1
+    losses = []
+    try:
+        for _ in range(int(steps)):
+            rays, pixels = next_batch()
+            origins, viewdirs = rays.origins.reshape(-1, 3), rays.viewdirs.reshape(-1, 3)
+            pixels = pixels.reshape(-1, 3).to(module.table.device, torch.float32)
+            data = mesh_intersect.sampling_raytrace_device(viewdirs, origins, layout=False)
+            if data is None:
+                bg = torch.zeros_like(pixels) if bg_color == "black" else torch.ones_like(pixels)
+                losses.append(torch.nn.functional.smooth_l1_loss(bg, pixels).detach())
+                continue
+            rgb = utils.render_image_finetune_baking_with_occgrid(
+                None, None, type(rays)(origins=origins, viewdirs=viewdirs), data, render_step_size=step_size,
+                mesh_intersect=mesh_intersect, vertex_features=module, bg_color=bg_color)[0]
+            loss = torch.nn.functional.smooth_l1_loss(rgb, pixels)
+            optimizer.zero_grad(set_to_none=True)
+            loss.backward()
+            optimizer.step()
+            if train_density:
+                with torch.no_grad():
+                    module.table[:, sigma_col].clamp_(min=0.0)
+            losses.append(loss.detach())
+    finally:
+        module.train_density = was_density
+        module.table.requires_grad_(was_grad)
+        mesh_intersect.render_step_size = was_step
+    return [float(v) for v in torch.stack(losses).cpu()] if losses else []
 
 
 def triangle_max_weights(weights: torch.Tensor, index_tri: torch.Tensor, out: torch.Tensor) -> torch.Tensor:

@@ -457,7 +457,8 @@ class FrameRenderer:
     @torch.no_grad()
     def render_vertex_baked_async(self, origins, viewdirs, vertex_features, camera, early_stop_eps=None):
         """``render_vertex_baked`` for a camera frame without a host wait: (rgb, alpha, depth, frame), always through the
-        front-to-back launch (``early_stop_eps`` None or 0 never stops: the default route's pixels bit for bit)."""
+        front-to-back launch (``early_stop_eps`` None or 0 never stops: the default route's pixels bit for bit).
+        ``vertex_features``: a tensor or a ``baking.VertexBakedFeatures``, as ``render_vertex_baked``."""
         if camera is None:
             raise NotImplementedError("render_vertex_baked_async needs a camera frame")
         stop_tau = utils.early_stop_tau(0.0 if early_stop_eps is None else early_stop_eps)
@@ -466,7 +467,8 @@ class FrameRenderer:
     @torch.no_grad()
     def render_vertex_baked(self, origins, viewdirs, vertex_features, image_width: int = 0, camera=None, early_stop_eps=None):
         """Vertex-baked variant (``utils.render_image_finetune_baking_with_occgrid``): the SG features live at the mesh
-        vertices (``vertex_features`` [V, 3 + 7L + 1], ``baking.bake_vertex_features``) and every quadrature point shades
+        vertices (``vertex_features`` [V, 3 + 7L + 1], ``baking.bake_vertex_features``, or a ``baking.VertexBakedFeatures``,
+        e.g. one that ``baking.finetune_vertex_features`` fitted: its table is read in place) and every quadrature point shades
         the barycentric blend of its triangle's three rows.  With a ``camera`` the frame stays in the intersector's tile
         order: tile pack with triangle ids -> ``qf_vertex_shade_points`` -> tile compositor; same pixels as that function
         on the ray-major samples, bit for bit.  ``early_stop_eps`` (camera frames only; None = the route above, a float

@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import _C
+from .baking import VertexBakedFeatures
 from .datasets.utils import Rays, namedtuple_map
 from .field import Field as _Field
 from .mesh_utils import SampleSet, SampleWindow
@@ -664,13 +665,14 @@ def _vertex_lobes(width: int) -> int:
     return lobes
 
 
-def vertex_baked_shading(mesh_intersect, vertex_features):
-    """What the vertex-baked kernels read (DESIGN.md section 3.5d), on the device: (table, records).  ``table``: float32
-    [V, stride], ``vertex_features`` ([V, 3 + 7L + 1], ``baking.bake_vertex_features``) with every row zero-padded to
-    ``_C.vertex_row_stride(L)`` floats (64-byte lines).  ``records``: the 128-byte vertex-triangle records of
-    ``qf_vertex_records_pack`` from the mesh's float64 vertices.  Both are built on first use and cached the way
-    ``_triangle_records`` caches its table: the records per vertex array of the mesh, the padded table per (address,
-    version, shape) of the feature tensor, each ordered for a consumer on another stream than the one that built it."""
+def _vertex_features_lobes(vertex_features) -> int:
+    if isinstance(vertex_features, VertexBakedFeatures):
+        return vertex_features.n_lobes
+    return _vertex_lobes(vertex_features.shape[1])
+
+
+def _vertex_records(mesh_intersect):
+    """The mesh's cache of the vertex-baked route, built on first use: [vertex array, records, table key, table]."""
     cache = getattr(mesh_intersect, "_vertex_baked_cache", None)
     if cache is None or cache[0] is not mesh_intersect.mesh.vertices:
         dev = mesh_intersect.device
@@ -682,6 +684,26 @@ def vertex_baked_shading(mesh_intersect, vertex_features):
         # v64 and faces stay referenced: the pack may still be reading them on its stream
         cache = mesh_intersect._vertex_baked_cache = [mesh_intersect.mesh.vertices,
                                                       _C.StreamCached(None, (records, v64, faces), [records]), None, None]
+    return cache
+
+
+def vertex_baked_shading(mesh_intersect, vertex_features):
+    """What the vertex-baked kernels read (DESIGN.md section 3.5d), on the device: (table, records).  ``table``: float32
+    [V, stride], ``vertex_features`` ([V, 3 + 7L + 1], ``baking.bake_vertex_features``) with every row zero-padded to
+    ``_C.vertex_row_stride(L)`` floats (64-byte lines).  ``records``: the 128-byte vertex-triangle records of
+    ``qf_vertex_records_pack`` from the mesh's float64 vertices.  Both are built on first use and cached the way
+    ``_triangle_records`` caches its table: the records per vertex array of the mesh, the padded table per (address,
+    version, shape) of the feature tensor, each ordered for a consumer on another stream than the one that built it.
+    A ``baking.VertexBakedFeatures`` is taken as it is: ``table`` is its parameter's own memory (detached), nothing is
+    copied or cached, and ordering it across streams is the caller's, as for any tensor they own."""
+    cache = _vertex_records(mesh_intersect)
+    if isinstance(vertex_features, VertexBakedFeatures):
+        vertex_features.check_rows(mesh_intersect.mesh.vertices.shape[0])
+        table = vertex_features.table.detach()
+        if table.device != _C.resolve_device(mesh_intersect.device) or not table.is_contiguous() or table.data_ptr() % 64:
+            raise ValueError(f"the VertexBakedFeatures table must be contiguous, 64-byte aligned and on "
+                             f"{mesh_intersect.device}, it is on {table.device}")
+        return table, cache[1].get()[0]
     feats = torch.as_tensor(vertex_features)
     if feats.dim() != 2 or feats.shape[0] != mesh_intersect.mesh.vertices.shape[0]:
         raise ValueError(f"vertex_features must be [V, 3 + 7L + 1] with V = {mesh_intersect.mesh.vertices.shape[0]} rows, "
@@ -697,35 +719,91 @@ def vertex_baked_shading(mesh_intersect, vertex_features):
 
 
 def vertex_baked_shading_struct(mesh_intersect, vertex_features):
-    """The ``qf_vertex_baked_shading`` of a (mesh, feature tensor): (struct, tensors it points at -- keep them referenced
-    until the launch that reads them ran)."""
+    """The ``qf_vertex_baked_shading`` of a (mesh, feature tensor or ``VertexBakedFeatures``): (struct, tensors it points
+    at -- keep them referenced until the launch that reads them ran)."""
     table, records = vertex_baked_shading(mesh_intersect, vertex_features)
     s = _C.VertexBakedShading()
     s.table, s.records = table.data_ptr(), records.data_ptr()
-    s.n_vertices, s.stride, s.n_lobes = int(table.shape[0]), int(table.shape[1]), _vertex_lobes(vertex_features.shape[1])
+    s.n_vertices, s.stride, s.n_lobes = int(table.shape[0]), int(table.shape[1]), _vertex_features_lobes(vertex_features)
     return s, (table, records)
 
 
-@torch.no_grad()
+class _VertexShadeFn(torch.autograd.Function):
+    """Differentiable vertex shading: forward = ``qf_vertex_shade_points`` on the padded table,
+    backward = ``qf_vertex_shade_points_backward`` into a zero-filled [V, stride] gradient.  Only inputs are saved: the
+    backward recomputes the blend.  ``train_density`` False: the density is frozen -- sigma carries no graph and the
+    kernel gets no ``d_sigma``.  The ids come as exactly one of ``tri64`` / ``tri32``."""
+
+    @staticmethod
+    def forward(ctx, table, records, points, tri64, tri32, dirs, lobes, n_device, train_density):
+        n = points.shape[0]
+        rgb = torch.empty((n, 3), dtype=torch.float32, device=points.device)
+        sigma = torch.empty((n,), dtype=torch.float32, device=points.device)
+        _C.check(_C.lib().qf_vertex_shade_points(
+            _C.ptr(table), int(table.shape[1]), lobes, _C.ptr(records), _C.ptr(points), _C.ptr(tri64), _C.ptr(tri32),
+            _C.ptr(dirs), n, _C.ptr(n_device, torch.int64), None, _C.ptr(rgb), _C.ptr(sigma), _C.stream()),
+            "qf_vertex_shade_points")
+        ctx.save_for_backward(table, records, points, tri64, tri32, dirs, n_device)
+        ctx.lobes, ctx.train_density = lobes, train_density
+        if not train_density:
+            ctx.mark_non_differentiable(sigma)
+        return rgb, sigma
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_sigma):
+        table, records, points, tri64, tri32, dirs, n_device = ctx.saved_tensors
+        grad = torch.zeros_like(table)
+        g_rgb = _C.f32c(g_rgb)
+        g_sigma = _C.f32c(g_sigma) if ctx.train_density else None
+        _C.check(_C.lib().qf_vertex_shade_points_backward(
+            _C.ptr(table), int(table.shape[1]), ctx.lobes, _C.ptr(records), int(table.shape[0]), _C.ptr(points),
+            _C.ptr(tri64), _C.ptr(tri32), _C.ptr(dirs), points.shape[0], _C.ptr(n_device, torch.int64), _C.ptr(g_rgb),
+            _C.ptr(g_sigma), _C.ptr(grad), _C.stream()), "qf_vertex_shade_points_backward")
+        return grad, None, None, None, None, None, None, None, None
+
+
+def _vertex_table_trains(vertex_features) -> bool:
+    """The differentiable route is taken exactly when a ``VertexBakedFeatures`` whose table requires a gradient is passed
+    while autograd is recording."""
+    return (isinstance(vertex_features, VertexBakedFeatures) and torch.is_grad_enabled()
+            and vertex_features.table.requires_grad)
+
+
 def shade_vertex_baked_points(mesh_intersect, vertex_features, points, index_tri, dirs, n_device=None,
                               want_features: bool = False):
     """(rgb [n,3], sigma [n]) of samples given by position and triangle from the vertex-baked features: the unclamped
     fp32 barycentrics of the sample in its triangle, the blend of the triangle's three vertex rows, SG shading of the
     blend -- utils.py:822-840 in one launch (``qf_vertex_shade_points``).  ``want_features``: the blend itself comes
-    back as a third value, [n, 3 + 7L + 1].  ``n_device``: see ``shade_baked_points``."""
-    table, records = vertex_baked_shading(mesh_intersect, vertex_features)
-    lobes = _vertex_lobes(vertex_features.shape[1])
-    points, dirs = _C.f32c(points), _C.f32c(dirs)
-    # int32 ids (what the tile pack writes) go to the kernel as they are; anything else as the reference's int64
-    tri32 = index_tri.contiguous() if index_tri.dtype == torch.int32 else None
-    tri64 = None if tri32 is not None else _C.i64c(index_tri)
-    n = points.shape[0]
-    rgb = torch.empty((n, 3), dtype=torch.float32, device=points.device)
-    sigma = torch.empty((n,), dtype=torch.float32, device=points.device)
-    feats = torch.empty((n, vertex_features.shape[1]), dtype=torch.float32, device=points.device) if want_features else None
-    _C.check(_C.lib().qf_vertex_shade_points(
-        _C.ptr(table), int(table.shape[1]), lobes, _C.ptr(records), _C.ptr(points), _C.ptr(tri64), _C.ptr(tri32), _C.ptr(dirs),
-        n, _C.ptr(n_device, torch.int64), _C.ptr(feats), _C.ptr(rgb), _C.ptr(sigma), _C.stream()), "qf_vertex_shade_points")
+    back as a third value, [n, 3 + 7L + 1].  ``n_device``: see ``shade_baked_points``.
+    ``vertex_features``: a [V, 3 + 7L + 1] tensor (inference only: detached, padded once, cached) or a
+    ``baking.VertexBakedFeatures``, whose table is read in place.  With such a module whose table requires a gradient,
+    while autograd is recording, rgb and sigma carry a graph to the table (``_VertexShadeFn``; ``want_features`` is then
+    not offered); every other call runs without one, as before."""
+    if _vertex_table_trains(vertex_features):
+        if want_features:
+            raise ValueError("want_features is an inference-only output")
+        with torch.no_grad():
+            _, records = vertex_baked_shading(mesh_intersect, vertex_features)
+            points, dirs = _C.f32c(points.detach()), _C.f32c(dirs.detach())
+            tri32 = index_tri.contiguous() if index_tri.dtype == torch.int32 else None
+            tri64 = None if tri32 is not None else _C.i64c(index_tri)
+        return _VertexShadeFn.apply(vertex_features.table, records, points, tri64, tri32, dirs, vertex_features.n_lobes,
+                                    n_device, vertex_features.train_density)
+    with torch.no_grad():
+        table, records = vertex_baked_shading(mesh_intersect, vertex_features)
+        lobes = _vertex_features_lobes(vertex_features)
+        points, dirs = _C.f32c(points), _C.f32c(dirs)
+        # int32 ids (what the tile pack writes) go to the kernel as they are; anything else as the reference's int64
+        tri32 = index_tri.contiguous() if index_tri.dtype == torch.int32 else None
+        tri64 = None if tri32 is not None else _C.i64c(index_tri)
+        n = points.shape[0]
+        rgb = torch.empty((n, 3), dtype=torch.float32, device=points.device)
+        sigma = torch.empty((n,), dtype=torch.float32, device=points.device)
+        feats = torch.empty((n, 3 + 7 * lobes + 1), dtype=torch.float32, device=points.device) if want_features else None
+        _C.check(_C.lib().qf_vertex_shade_points(
+            _C.ptr(table), int(table.shape[1]), lobes, _C.ptr(records), _C.ptr(points), _C.ptr(tri64), _C.ptr(tri32),
+            _C.ptr(dirs), n, _C.ptr(n_device, torch.int64), _C.ptr(feats), _C.ptr(rgb), _C.ptr(sigma), _C.stream()),
+            "qf_vertex_shade_points")
     if want_features:
         return rgb, sigma, feats
     return rgb, sigma
@@ -737,7 +815,8 @@ def shade_composite_vertex_baked_frame(mesh_intersect, vertex_features, xyz_c, d
     """``shade_vertex_baked_points`` + ``composite_frame`` of a frame in the intersector's tile order as ONE launch that
     walks every pixel front to back (``qf_vertex_composite_tiles``) and stops reading vertex rows once the optical depth
     in front of a pixel's next sample exceeds ``stop_tau`` (``early_stop_tau``; ``inf`` never stops and gives the two
-    calls' pixels bit for bit).  Arguments and returns as ``shade_composite_baked_frame``."""
+    calls' pixels bit for bit).  Arguments and returns as ``shade_composite_baked_frame``; ``vertex_features`` a tensor or a
+    ``baking.VertexBakedFeatures`` (inference either way: the tile-order frame has no backward)."""
     if getattr(frame, "band_rows", 0) or frame.tri_c is None:
         raise ValueError("shade_composite_vertex_baked_frame: an unbanded frame with triangle ids (want_tri) is required")
     shading, keep = vertex_baked_shading_struct(mesh_intersect, vertex_features)
@@ -768,7 +847,6 @@ def shade_composite_vertex_baked_frame(mesh_intersect, vertex_features, xyz_c, d
     return rgb, alpha, depth, shaded
 
 
-@torch.no_grad()
 def render_image_finetune_baking_with_occgrid(
     radiance_field: torch.nn.Module, estimator, rays: Rays, data, near_plane: float = 0.0, far_plane: float = 1e10,
     render_step_size: float = 1e-3, render_bkgd: Optional[torch.Tensor] = None, cone_angle: float = 0.0,
@@ -783,7 +861,16 @@ def render_image_finetune_baking_with_occgrid(
     ``None`` bakes it once per call.  ``bg_color`` (extension): the reference composites on white.
     The view direction of a sample is the loader's ``dirs`` (``d / (|d| + 1e-7)``, what every other renderer here and the
     tile pack use) where the reference indexes ``rays.viewdirs`` (:840): one ulp apart, and the camera frame of
-    ``FrameRenderer.render_vertex_baked`` then equals this function bit for bit."""
+    ``FrameRenderer.render_vertex_baked`` then equals this function bit for bit.
+    ``vertex_features`` may also be a ``baking.VertexBakedFeatures``, whose table is read in place.  With such a module
+    whose table requires a gradient, while autograd is recording, colors, opacities and depths carry a graph to the table
+    (``_VertexShadeFn`` followed by the differentiable ``derive_properties``); every other call
+    runs under ``torch.no_grad()`` and returns tensors without a graph, as before."""
+    with torch.set_grad_enabled(_vertex_table_trains(vertex_features)):
+        return _render_vertex_baked_ray_major(radiance_field, rays, data, timestamps, mesh_intersect, vertex_features, bg_color)
+
+
+def _render_vertex_baked_ray_major(radiance_field, rays, data, timestamps, mesh_intersect, vertex_features, bg_color):
     if timestamps is not None:
         raise NotImplementedError("dynamic (D-NeRF) fields are out of scope")
     rays, rays_shape, num_rays = _flatten_rays(rays)
