@@ -33,6 +33,86 @@ def test_generate_rays_vs_reference_fixture(device):
     assert torch.allclose(d.norm(dim=-1), torch.ones(640000, device=device), atol=1e-6)
 
 
+@pytest.mark.parametrize("opengl", [True, False])
+def test_generate_rays_with_general_intrinsics(device, opengl):
+    """qf_generate_rays for a camera with fx != fy, an off-centre principal point and roll (tests/asymmetric_inputs.py),
+    both axis conventions, against the host arithmetic of the loader with K's four entries -- under the bar of
+    test_generate_rays_vs_reference_fixture: origins exact, directions within 1.2e-7."""
+    import ctypes
+    from quadraturefields_amd import _C
+    from tests import asymmetric_inputs as asym
+    w, h = 93, 61
+    cam, c2w, k = asym.general_camera(w, h)
+    o = torch.full((w * h, 3), float("nan"), device=device)
+    d = torch.full((w * h, 3), float("nan"), device=device)
+    _C.check(_C.lib().qf_generate_rays(ctypes.byref(cam), 1 if opengl else 0, _C.ptr(o), _C.ptr(d), _C.stream()),
+             "qf_generate_rays")
+    o_t, d_t = asym.rays_from_k(c2w, *k, w, h, opengl=opengl)
+    assert torch.equal(o.cpu(), o_t)
+    err = float((d.cpu() - d_t).abs().max())
+    print(f"opengl={opengl}: max |d - host| = {err:.3e}")
+    assert torch.allclose(d.cpu(), d_t, rtol=0, atol=1.2e-7)
+    assert torch.allclose(d.norm(dim=-1), torch.ones(w * h, device=device), atol=1e-6)
+    # the two conventions look in opposite directions along the camera's z axis
+    back = c2w[:, 2].to(device)
+    assert bool(((d @ back < 0) == opengl).all())
+
+
+def test_frame_through_the_general_camera_equals_the_camera_less_route(device):
+    """FrameRenderer.render(o, d, camera=general_camera): the camera-coherent route answers (no mismatch frame, the plain
+    pass as the last route of ``hits``) and the frame -- pixels, opacity, depth, sample count -- and the hit lists equal
+    those of the camera-less BVH route bit for bit.  Handed the same rays with fx and fy exchanged in the struct, the
+    frame is still that frame, but through the BVH: the mismatch is counted."""
+    import warnings
+    from quadraturefields_amd import synthetic
+    from quadraturefields_amd.mesh_utils import MeshIntersection
+    from quadraturefields_amd.radiance_fields.ngp import NGPRadianceField
+    from quadraturefields_amd.render import FrameRenderer
+    from tests import asymmetric_inputs as asym
+    mesh = synthetic.shell_mesh(n_shells=4, subdivisions=3)
+    mi = MeshIntersection(mesh, simplify_mesh=False, scale=1.0, num_intersections=25)
+    field = NGPRadianceField(aabb=asym.BOX, log2_hashmap_size=14)
+    field.load_state_dict(synthetic.seeded_ngp_state(14, field.mlp_base.grid.n_rows), strict=False)
+    field = field.to(device)
+    fr = FrameRenderer(mi, field)
+    ri = mi.rayintersector
+    w, h = 96, 64
+    cam, c2w, k = asym.general_camera(w, h)
+    o, d = asym.rays_from_k(c2w, *k, w, h, device=device)
+    want = fr.render(o, d, image_width=w)                 # BVH traversal
+    assert want[3] > 1000
+    got = fr.render(o, d, camera=cam)
+    assert ri.camera_mismatch_frames == 0
+    assert got[3] == want[3]
+    for a, b in zip(got[:3], want[:3]):
+        assert torch.equal(a, b)
+    ri._raster_backoff = 0
+    assert ri.fused_frame_ready(cam, 25)
+    one = fr.render_async(o, d, cam)                      # ... and the one-call frame
+    assert ri.frame_samples() == want[3]
+    ri._settle_fused_policy(0)
+    assert ri.camera_mismatch_frames == 0
+    for a, b in zip(one[:3], want[:3]):
+        assert torch.equal(a, b)
+    ri._raster_backoff = 0
+    lists = ri.hits(o, d, camera=cam)
+    assert ri.last_route == "plain" and ri.camera_mismatch_frames == 0
+    lists_bvh = ri.hits(o, d, image_width=w)
+    assert ri.last_route == "bvh"
+    for a, b in zip(lists[:3], lists_bvh[:3]):
+        assert torch.equal(a, b)
+    assert int(lists[2].sum()) > 1000
+    # the counterpart: a struct that does not describe the rays
+    wrong = asym.set_intrinsics(cam, k[1], k[0], k[2], k[3])
+    ri._raster_backoff = 0
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        lists_wrong = ri.hits(o, d, camera=wrong)
+    assert ri.camera_mismatch_frames == 1 and ri.last_route == "bvh"
+    for a, b in zip(lists_wrong[:3], lists_bvh[:3]):
+        assert torch.equal(a, b)
+
+
 def test_loader_item_renders_like_the_frame_renderer(device):
     from quadraturefields_amd import synthetic, utils
     from quadraturefields_amd.datasets.nerf_synthetic import SubjectLoader

@@ -63,6 +63,102 @@ def test_march_bit_exact_vs_oracle(device, res, step):
     assert est.sampling(torch.from_numpy(o).to(device), torch.from_numpy(d).to(device), render_step_size=step)[0].numel() == 0
 
 
+def _box_estimator(device, pattern=None):
+    from quadraturefields_amd.estimators import OccGridEstimator
+    from tests import asymmetric_inputs as asym
+    est = OccGridEstimator(roi_aabb=asym.BOX, resolution=list(asym.RES), levels=1).to(device)
+    assert est.binaries.shape == (1,) + asym.RES and est.occs.shape == (int(np.prod(asym.RES)),)
+    if pattern is not None:
+        est.binaries.copy_(torch.from_numpy(pattern)[None].to(device))
+    return est
+
+
+def _assert_march_equal(got, want, more_than=1000):
+    ridx, ts, te = got
+    assert ridx.dtype == torch.int64 and ridx.shape[0] == want[0].shape[0] > more_than, (ridx.shape[0], want[0].shape[0])
+    assert np.array_equal(ridx.cpu().numpy(), want[0])
+    assert np.array_equal(ts.cpu().numpy(), want[1]) and np.array_equal(te.cpu().numpy(), want[2])
+
+
+@pytest.mark.gpu
+def test_march_bit_exact_vs_oracle_on_the_asymmetric_box_and_grid(device):
+    """test_march_bit_exact_vs_oracle on a box with three different extents, off the origin, and a 32 x 16 x 48 grid
+    (tests/asymmetric_inputs.py): the per-axis normalisation and the cell linearisation cannot hide behind a symmetry.
+    Whole rays, a clipping pair of planes, and the per-ray ``t_min`` / ``t_max`` tensors."""
+    from tests import asymmetric_inputs as asym
+    b = asym.binaries()
+    est = _box_estimator(device, b)
+    o, d = asym.march_rays()
+    od, dd = torch.from_numpy(o).to(device), torch.from_numpy(d).to(device)
+    step = 0.02
+    lo, hi = np.array(asym.BOX_LO, np.float32), np.array(asym.BOX_HI, np.float32)
+    assert ((o[:20] > lo) & (o[:20] < hi)).all() and o[23, 0] == lo[0]
+    for near, far in ((0.0, 1e10), (3.0, 4.5)):
+        want = oocc.march(asym.BOX, b, o, d, near, far, step)
+        _assert_march_equal(est.sampling(od, dd, near_plane=near, far_plane=far, render_step_size=step), want)
+        if near == 0.0:
+            per_ray = np.bincount(want[0], minlength=o.shape[0])
+            # origins inside the box, the axis-aligned rays and the one that starts on a face are sampled; the misses not
+            assert (per_ray[:20] > 0).sum() >= 10 and (per_ray[20:24] > 0).all() and not per_ray[24:30].any()
+    rng = np.random.default_rng(5)
+    t_min = rng.uniform(0.0, 3.5, size=o.shape[0]).astype(np.float32)
+    t_max = rng.uniform(4.0, 6.0, size=o.shape[0]).astype(np.float32)
+    for near, far in ((0.0, 1e10), (2.0, 5.0)):               # the planes bind for some rays, the tensors for the others
+        want = oocc.march(asym.BOX, b, o, d, near, far, step, t_min=t_min, t_max=t_max)
+        assert want[0].shape[0] != oocc.march(asym.BOX, b, o, d, near, far, step)[0].shape[0]
+        got = est.sampling(od, dd, near_plane=near, far_plane=far, render_step_size=step,
+                           t_min=torch.from_numpy(t_min).to(device), t_max=torch.from_numpy(t_max).to(device))
+        _assert_march_equal(got, want)
+
+
+@pytest.mark.gpu
+def test_index_coordinate_round_trip_on_the_asymmetric_grid(device):
+    """``estimators.py`` inverts the kernel's cell linearisation in Python (``update_every_n_steps``: index -> cell ->
+    point; ``set_occupancy_from_density``: the meshgrid of centres -> flat).  A density that is 1 exactly where a known
+    pattern [32,16,48] is set at the cell of x -- computed on the host in fp64 -- must come back as that pattern, and
+    marching it must equal the oracle's march of the pattern."""
+    from tests import asymmetric_inputs as asym
+    pattern = asym.binaries(seed=3)
+    lo, hi = np.array(asym.BOX_LO, np.float64), np.array(asym.BOX_HI, np.float64)
+    res = np.array(asym.RES)
+    calls = []
+
+    def density(x):
+        p = x.detach().cpu().numpy().astype(np.float64)
+        c = np.floor((p - lo) / (hi - lo) * res).astype(np.int64)
+        assert ((c >= 0) & (c < res)).all()
+        calls.append(c)
+        return torch.from_numpy(pattern[c[:, 0], c[:, 1], c[:, 2]].astype(np.float32)).to(x.device)
+
+    want = torch.from_numpy(pattern)[None]
+    est = _box_estimator(device)
+    est.set_occupancy_from_density(density, threshold=0.5)
+    assert torch.equal(est.binaries.cpu(), want)
+    assert torch.equal(est.occs.cpu(), want.reshape(-1).float())
+    every = np.stack(np.meshgrid(*[np.arange(r) for r in asym.RES], indexing="ij"), axis=-1).reshape(-1, 3)
+    assert np.array_equal(np.concatenate(calls), every)       # cell i of the flat order was asked for at ITS centre
+    del calls[:]
+    est2 = _box_estimator(device)
+    est2.train()
+    torch.manual_seed(11)
+    torch.cuda.manual_seed(11)
+    est2.update_every_n_steps(step=0, occ_eval_fn=density, occ_thre=0.5)      # warm-up: every cell, a random point in it
+    asked = np.concatenate(calls)
+    assert asked.shape == every.shape
+    # the point of cell i is drawn inside cell i; its fp32 coordinates may round across a face when the random offset is
+    # within ~2e-6 of it (expected: 0.3 coordinates of the 73 728) -- never further than the neighbouring cell.  Stated
+    # cap: 8 cells.  The estimator's result below is compared exactly.
+    stray = (asked != every).any(axis=1)
+    print(f"{int(stray.sum())} of {every.shape[0]} points rounded into a neighbouring cell")
+    assert np.abs(asked - every).max() <= 1 and int(stray.sum()) <= 8
+    assert torch.equal(est2.binaries.cpu(), want)
+    o, d = asym.march_rays()
+    truth = oocc.march(asym.BOX, pattern, o, d, 0.0, 1e10, 0.02)
+    for e in (est, est2):
+        _assert_march_equal(e.sampling(torch.from_numpy(o).to(device), torch.from_numpy(d).to(device),
+                                       render_step_size=0.02), truth)
+
+
 @pytest.mark.gpu
 def test_sampling_filter_and_render_image_with_occgrid(device):
     from quadraturefields_amd import synthetic, utils

@@ -61,11 +61,29 @@ def _f0():
 
 
 @functools.lru_cache(maxsize=None)
-def _view(pose="orbit", focal_scale=1.0, w=W, h=H, band=None, zero_x=False):
+def _view(pose="orbit", focal_scale=1.0, w=W, h=H, band=None, zero_x=False, struct=None):
     """One camera's pixel grid (or rows ``band`` of it, with ``parallel.band_camera``): rays generated on the host -- the
-    brute force and the device see the same bits."""
+    brute force and the device see the same bits.  ``pose = "general"``: the camera of tests/asymmetric_inputs.py -- fy =
+    0.62 fx, the principal point off the image centre, 25 degrees of roll, looking past the origin; ``struct`` =
+    ``"swapped"`` / ``"centred"`` hands the pass the SAME rays with a struct whose fx and fy are exchanged / whose
+    principal point is the image centre (a camera that does not describe them)."""
     from quadraturefields_amd import parallel, synthetic
     from quadraturefields_amd.mesh_utils import make_camera
+    if pose == "general":
+        from tests import asymmetric_inputs as asym
+        assert not zero_x
+        cam, c2w, k = asym.general_camera(w, h, focal_scale=focal_scale, band=band)
+        o, d = asym.rays_from_k(c2w, *k, w, h)
+        y0, y1 = (0, h) if band is None else band
+        if struct is not None:
+            fx, fy, cx, cy = k
+            wrong = {"swapped": (fy, fx, cx, cy - y0), "centred": (fx, fy, w / 2.0, h / 2.0 - y0)}[struct]
+            cam = asym.set_intrinsics(cam, *wrong)
+        o, d = o[y0 * w:y1 * w].contiguous(), d[y0 * w:y1 * w].contiguous()
+        # (the key names the RAYS: the brute force's answer is shared by every struct that is handed the same ones)
+        return SimpleNamespace(key=(pose, focal_scale, w, h, band, zero_x), c2w=c2w.numpy().astype(np.float64), focal=k[0],
+                               w=w, h=y1 - y0, n=(y1 - y0) * w, cam=cam, o=o.numpy(), d=d.numpy(), _dev=None)
+    assert struct is None
     c2w = synthetic.orbit_cameras(1, seed=1)[0].clone()
     if pose == "inside":
         c2w[:, 3] *= 0.2                          # inside the shells: box corners behind the camera plane
@@ -318,6 +336,10 @@ PLAIN_CASES = [
     ((8, 3), "orbit", None, 5),
     ((8, 3), "orbit", None, 25),
     ((8, 3), "inside", None, 5),           # 10 .. 12 hits on every ray: every list overflows
+    ((4, 3), "general", None, 5),          # fx != fy, an off-centre principal point, roll (tests/asymmetric_inputs.py)
+    ((4, 3), "general", None, 25),
+    ((8, 3), "general", None, 5),
+    ((8, 3), "general", None, 25),
 ]
 
 
@@ -373,7 +395,9 @@ def test_sorted_lists_with_the_rule_on(device, lib, mesh, pose, k, cull):
 
 
 WIDE_CASES = [((8, 3), "orbit", 5, 7), ((8, 3), "orbit", 5, 24), ((8, 3), "orbit", 3, 7), ((4, 3), "orbit", 3, 7),
-              ((8, 3), "inside", 5, 24), ((3, 1), "orbit", 3, 24), ((1, 1), "orbit", 5, 7), ((8, 3), "orbit", 25, 25)]
+              ((8, 3), "inside", 5, 24), ((3, 1), "orbit", 3, 24), ((1, 1), "orbit", 5, 7), ((8, 3), "orbit", 25, 25),
+              ((4, 3), "general", 5, 7), ((8, 3), "general", 5, 7), ((8, 3), "general", 5, 24), ((4, 3), "general", 25, 25),
+              ((8, 3), "general", 25, 25)]
 
 
 @pytest.mark.parametrize("min_sep", [0.0, RULE])
@@ -404,7 +428,9 @@ def _bvh_lists(lib, ri, view, k):
 SLAB_CASES = [((8, 3), "orbit", 5, 7, 2, 0.0), ((8, 3), "orbit", 5, 7, 8, 0.0), ((8, 3), "orbit", 5, 24, 2, 0.0),
               ((8, 3), "orbit", 5, 24, 8, 0.0), ((8, 3), "orbit", 3, 24, 8, RULE), ((8, 3), "orbit", 5, 24, 2, RULE),
               ((8, 3), "inside", 5, 24, 8, 0.0), ((8, 3), "inside", 5, 24, 2, RULE), ((4, 3), "orbit", 3, 7, 8, 0.0),
-              ((3, 1), "orbit", 3, 24, 2, RULE), ((1, 0), "orbit", 3, 7, 2, 0.0)]
+              ((3, 1), "orbit", 3, 24, 2, RULE), ((1, 0), "orbit", 3, 7, 2, 0.0),
+              ((4, 3), "general", 5, 7, 2, 0.0), ((8, 3), "general", 5, 7, 8, 0.0), ((8, 3), "general", 5, 24, 8, 0.0),
+              ((4, 3), "general", 5, 24, 2, RULE), ((4, 3), "general", 25, 32, 2, 0.0), ((8, 3), "general", 25, 32, 8, 0.0)]
 
 
 @pytest.mark.parametrize("mesh,pose,k,wide,slabs,min_sep", SLAB_CASES)
@@ -448,7 +474,9 @@ def test_slab_pass_selects_the_k_nearest_and_repairs_to_the_bvh(device, lib, mes
 
 @pytest.mark.parametrize("mesh,pose,w,h,k", [((8, 3), "orbit", 96, 64, 3), ((8, 3), "orbit", 93, 61, 3), ((8, 3), "orbit", 93, 61, 5),
                                              ((4, 3), "orbit", 93, 61, 5), ((4, 3), "orbit", 96, 64, 25), ((3, 1), "inside", 93, 61, 3),
-                                             ((1, 0), "orbit", 90, 60, 5), ((4, 3), "behind", 93, 61, 5)])
+                                             ((1, 0), "orbit", 90, 60, 5), ((4, 3), "behind", 93, 61, 5),
+                                             ((4, 3), "general", 93, 61, 5), ((4, 3), "general", 96, 64, 25),
+                                             ((8, 3), "general", 96, 64, 5), ((8, 3), "general", 93, 61, 25)])
 def test_tile_bins_hold_exactly_the_hits(device, lib, mesh, pose, w, h, k):
     """93 x 61 and 90 x 60: ragged right and bottom tiles (5 resp. 2 of 8 columns, 5 resp. 4 of 8 rows inside the image)."""
     view = _view(pose, w=w, h=h)
@@ -561,6 +589,38 @@ def test_ray_flag_through_the_culling_launch(device, lib, mesh, route):
             assert (out.tri == SENT_TRI).all() and np.isnan(out.t).all(), (i, what)
 
 
+@pytest.mark.parametrize("struct", ["swapped", "centred"])
+@pytest.mark.parametrize("mesh,route,cull,k", [((4, 3), "plain", 0, 5), ((4, 3), "plain", 1, 25), ((8, 3), "wide", 1, 5),
+                                               ((8, 3), "slabs", 0, 5), ((4, 3), "tiles", 0, 25)])
+def test_general_camera_rays_with_another_cameras_struct_raise_the_flag(device, lib, mesh, route, cull, k, struct):
+    """The general camera's rays with a struct whose fx and fy are exchanged, or whose principal point is the image centre:
+    the struct does not describe the rays, so every pass must raise the flag and write nothing; the repair then answers
+    every ray through the BVH, and the lists are the brute force's.  With the RIGHT struct the same rays pass the check
+    (flag 0) in the case lists above: the check reads fx, fy, cx and cy where the struct keeps them."""
+    from quadraturefields_amd import _C
+    good, view = _view("general"), _view("general", struct=struct)
+    assert np.array_equal(view.o, good.o) and np.array_equal(view.d, good.d) and view.key == good.key
+    assert (view.cam.fx, view.cam.fy, view.cam.cx, view.cam.cy) != (good.cam.fx, good.cam.fy, good.cam.cx, good.cam.cy)
+    ri = _ri(mesh)
+    T = _truth(mesh, view)
+    assert (T.cnt > 0).mean() > 0.2
+    wide, slabs = 24, 2
+    assert _call(lib, ri, good, k, route, cull=cull, wide=wide, slabs=slabs).flag == 0
+    out = _call(lib, ri, view, k, route, cull=cull, wide=wide, slabs=slabs)
+    assert out.flag == 1
+    assert out.overflow == 0 and not out.count.any()
+    assert (out.tri == SENT_TRI).all() and np.isnan(out.t).all()
+    if route == "tiles":
+        assert not out.cursor.any() and not out.mask.any()
+        return                                    # (the bins' consumer is the frame's tile pack, not this repair)
+    dv = out.dev
+    _C.check(lib.qf_bvh_repair_overflow(ri._handle, _C.ptr(dv.o), _C.ptr(dv.d), view.n, k, view.w, _C.ptr(dv.tri), _C.ptr(dv.t),
+                                        _C.ptr(dv.cnt), None, None, _C.ptr(dv.flag), _C.stream()), "qf_bvh_repair_overflow")
+    tri, t, cnt = dv.tri.cpu().numpy(), dv.t.cpu().numpy(), dv.cnt.cpu().numpy()
+    assert np.array_equal(cnt, np.minimum(T.cnt, k))
+    assert np.array_equal(_sorted_rows(t, tri, cnt)[0], _nearest(T, k))
+
+
 # ------------------------------------------------------------------------------------------------ part 2: the culling
 def _chunk_geometry(lib, ri, mesh_key):
     """The chunks restated on the host in fp64: 64 consecutive triangles in leaf order (``qf_bvh_copy_tri_ids``) ->
@@ -634,7 +694,7 @@ def test_culling_is_conservative_and_tight(device, lib, mesh):
     geometry = _chunk_geometry(lib, ri, mesh)
     n_chunks = geometry[0].shape[0]
     sizes = []
-    for pose in ("orbit", "inside"):
+    for pose in ("orbit", "inside", "general"):
         for band in CULL_BANDS:
             view = _view(pose, 0.5, band=band)
             vis, must, may = _check_culled_call(lib, ri, mesh, view, geometry)

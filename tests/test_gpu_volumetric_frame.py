@@ -33,10 +33,10 @@ class AnalyticField(torch.nn.Module):
     """Density constant on the cells of a K^3 lattice over the aabb, colour an affine function of position: every
     operation is a basic IEEE one, so the CPU and the device evaluate it to the same bits at the same positions."""
 
-    def __init__(self, table):
+    def __init__(self, table, aabb=AABB):
         super().__init__()
         self.register_buffer("table", torch.as_tensor(table, dtype=torch.float32))
-        self.register_buffer("aabb", torch.tensor(AABB))
+        self.register_buffer("aabb", torch.tensor(aabb, dtype=torch.float32))
 
     def normalize(self, x):
         x01 = (x - self.aabb[:3]) / (self.aabb[3:] - self.aabb[:3])
@@ -213,6 +213,52 @@ def test_analytic_field_rounds_and_image(device, name, max_samples):
         if name == "inside16":
             assert rounds[0]["ray_indices"].shape[0] > 300                 # origins inside the box: samples start at t = 0
             assert float(rounds[0]["t_starts"].min()) == 0.0
+
+
+@functools.lru_cache(maxsize=None)
+def _box_reference(max_samples):
+    """The capped rounds on the asymmetric box and the 32 x 16 x 48 grid of tests/asymmetric_inputs.py, its 600 rays."""
+    from tests import asymmetric_inputs as asym
+    b = asym.binaries()
+    o, d = asym.march_rays()
+    table = _table(5)
+    field = AnalyticField(table, asym.BOX)
+
+    def field_fn(pos, dirs):
+        rgb, sigma = field(torch.from_numpy(pos), torch.from_numpy(dirs))
+        return rgb.numpy(), sigma.numpy()
+
+    ref = vref.render(max_samples, field_fn, asym.BOX, b, o, d, render_step_size=STEP, early_stop_eps=EPS,
+                      render_bkgd=[1.0, 1.0, 1.0])
+    return b, o, d, table, ref
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("max_samples", [7, 1024])
+def test_capped_rounds_on_the_asymmetric_box_and_grid(device, max_samples):
+    """``qf_grid_march_round_count`` / ``_write`` (through the renderer's trace) against ``march_round`` where the three
+    extents, the three resolutions and the box's centre all differ: every round's sample lists, alive sets and near
+    planes exactly, the image within the bar of the cases above."""
+    from quadraturefields_amd import utils
+    from quadraturefields_amd.estimators import OccGridEstimator
+    from tests import asymmetric_inputs as asym
+    b, o, d, table, (rounds, (rgb_o, op_o, dep_o, total_o, pos_o)) = _box_reference(max_samples)
+    _assert_margins(rounds)
+    assert len(rounds) > 3 and total_o > (1000 if max_samples == 1024 else 100)
+    assert len({r["n_samples"] for r in rounds}) > 1       # the quota grows as rays retire
+    est = OccGridEstimator(roi_aabb=asym.BOX, resolution=list(asym.RES), levels=1).to(device)
+    est.binaries.copy_(torch.from_numpy(b)[None].to(device))
+    trace = []
+    rgb, opac, depth, total, positions = utils.render_image_with_occgrid_test(
+        max_samples, AnalyticField(table, asym.BOX).to(device), est, _rays(o, d, None, device), render_step_size=STEP,
+        render_bkgd=torch.ones(3, device=device), early_stop_eps=EPS, trace=trace)
+    _compare_rounds(trace, rounds)
+    assert total == total_o
+    assert np.array_equal(positions.cpu().numpy(), pos_o)
+    err = [float(np.abs(a.reshape(len(o), -1).cpu().numpy().astype(np.float64) - w.reshape(len(o), -1)).max())
+           for a, w in ((rgb, rgb_o), (opac, op_o), (depth, dep_o))]
+    print(f"box max_samples={max_samples}: rounds={len(rounds)} samples={total} max err rgb/opacity/depth = {err}")
+    assert max(err) <= TOL, err
 
 
 @functools.lru_cache(maxsize=None)
