@@ -4,7 +4,8 @@
     python examples/evaluate_vertex_baked.py --synthetic --root ROOT --num_lobes 6 --log2_hashmap_size 19
                                              --ckpt_path ROOT/fit_sg.pth [--early_stop_eps E] [--mesh_path MESH]
                                              [--size 200] [--views 4] [--up_sample 1] [--shells 2] [--subdivisions 3]
-                                             [--features PATH]
+                                             [--features PATH] [--quantise {linear,sigma}] [--save_quantised PREFIX]
+                                             [--load_quantised PREFIX]
 
 The mesh is ``--mesh_path`` or, without it, the shell mesh ``examples/fit_sg_synthetic.py`` fits on (``--shells``,
 ``--subdivisions``); the field is ``--ckpt_path``'s ``radiance_field`` (what ``fit_sg_synthetic.py --out`` wrote) or, if
@@ -15,7 +16,11 @@ scored by ``metrics.FrameScorer`` against the SG field's own render of the view 
 inside a triangle costs.  Prints PSNR / SSIM (and one JSON line); with ``--early_stop_eps`` the frame is rendered front to
 back with early ray termination and the share of the samples that were shaded is printed too.  ``--features PATH`` loads
 a [V, 3 + 7L + 1] table (``vertex_features.npy``, or what ``examples/finetune_vertex_baked.py`` wrote) instead of baking
-one; nothing is written then.
+one; nothing is written then.  ``--quantise {linear,sigma}`` quantises the baked or loaded table to 64-byte uint8 records
+with that colour codec (``baking.quantise_vertex_features``, DESIGN.md section 3.5f) and renders from the records;
+``--save_quantised PREFIX`` writes its uint8 PNG set (``PREFIX + alpha.png`` ...), ``--load_quantised PREFIX`` reads one
+(written with the codec ``--quantise`` names, default linear) instead of quantising.  The PSNR against the fp32 vertex
+frame is then printed too.
 """
 import argparse
 import json
@@ -47,6 +52,10 @@ def parse(argv):
     ap.add_argument("--shells", type=int, default=2)
     ap.add_argument("--subdivisions", type=int, default=3)
     ap.add_argument("--features", type=str, default="", help="load this vertex table (.npy) instead of baking one")
+    ap.add_argument("--quantise", choices=("linear", "sigma"), default=None,
+                    help="quantise the vertex table to uint8 records with this colour codec before rendering")
+    ap.add_argument("--save_quantised", type=str, default="", help="write the quantised table's PNG set under this prefix")
+    ap.add_argument("--load_quantised", type=str, default="", help="read the quantised table's PNG set from this prefix")
     return ap.parse_args(argv)
 
 
@@ -87,6 +96,20 @@ def main(argv=None):
             path = os.path.join(args.root, "vertex_features.npy")
             np.save(path, features.cpu().numpy())
             print(f"baked {features.shape[0]} vertices x {features.shape[1]} columns ({features.numel() * 4 / 1e6:.2f} MB) -> {path}")
+        asset = features
+        if args.load_quantised:
+            asset = baking.QuantisedVertexFeatures.load(args.load_quantised, features.shape[0], args.num_lobes,
+                                                        compression_type=args.quantise or "linear", device=device)
+            print(f"loaded the quantised table of {asset.n_vertices} vertices from {args.load_quantised}*.png")
+        elif args.quantise or args.save_quantised:
+            asset = baking.quantise_vertex_features(features, compression_type=args.quantise or "linear")
+            print(f"quantised {asset.n_vertices} vertices to {asset.records().shape[0]} records of 64 bytes "
+                  f"({asset.records().numel() / 1e6:.2f} MB)")
+        if args.save_quantised and asset is not features:
+            os.makedirs(os.path.dirname(args.save_quantised) or ".", exist_ok=True)
+            asset.save(args.save_quantised)
+            print(f"wrote {args.save_quantised}*.png")
+        sq_err, n_px = torch.zeros((), dtype=torch.float64, device=device), 0
         renderer = FrameRenderer(mesh_intersect, sg, render_step_size=5e-3)
         size = args.size
         focal = synthetic.lego_focal(size)
@@ -97,11 +120,15 @@ def main(argv=None):
             pixels = renderer.render(o, d, camera=make_camera(c2w, focal, size, size))[0]        # the field's own frame
             o, d = synthetic.camera_rays(c2w, focal * factor, size * factor, size * factor, device=device)
             camera = make_camera(c2w, focal * factor, size * factor, size * factor)
-            rgb, _, depth, n_samples = renderer.render_vertex_baked(o, d, features, camera=camera,
+            rgb, _, depth, n_samples = renderer.render_vertex_baked(o, d, asset, camera=camera,
                                                                     early_stop_eps=args.early_stop_eps)
             if args.early_stop_eps is not None and n_samples:
                 shaded += int(mesh_intersect.rayintersector.last_frame.shaded_count.sum())
                 samples += n_samples
+            if asset is not features:                   # the same frame from the fp32 table: what the codes cost
+                rgb32 = renderer.render_vertex_baked(o, d, features, camera=camera, early_stop_eps=args.early_stop_eps)[0]
+                sq_err += ((rgb.double() - rgb32.double()) ** 2).sum()
+                n_px += rgb.numel()
             scorer.score(rgb, pixels)
         res = scorer.results()
     out = {"psnr": res["psnr_avg"], "ssim": res["ssim_avg"], "psnrs": res["psnr"].tolist(), "ssims": res["ssim"].tolist(),
@@ -111,6 +138,10 @@ def main(argv=None):
     if args.early_stop_eps is not None:
         out["shaded_share"] = shaded / max(samples, 1)
         print(f"samples shaded (early_stop_eps {args.early_stop_eps}): {shaded} of {samples} = {out['shaded_share']:.4f}")
+    if asset is not features:
+        mse = float(sq_err) / max(n_px, 1)
+        out["psnr_vs_fp32_vertex"] = -10.0 * float(np.log10(mse)) if mse > 0 else float("inf")
+        print("psnr vs fp32 vertex frame: ", out["psnr_vs_fp32_vertex"])
     print(json.dumps(out))
     return out
 

@@ -87,6 +87,12 @@ class VertexBakedShading(Structure):
                 ("n_lobes", c_int32)]
 
 
+class VertexQuantShading(Structure):
+    """qf_vertex_quant_shading (include/qf_vertex_quant.h): the quantised vertex records of a vertex-baked frame."""
+    _fields_ = [("records", c_void_p), ("tri_records", c_void_p), ("n_vertices", c_int64), ("n_lobes", c_int32),
+                ("sigmoid_codec", c_int32), ("lambda_thres", c_float)]
+
+
 class FrontScratch(Structure):
     """qf_front_scratch (include/qf_hip.h): what qf_frame_render_front keeps between its launches."""
     _fields_ = [("state", c_void_p), ("win_count", c_void_p), ("win_total", c_void_p), ("win_order", c_void_p)]
@@ -247,6 +253,16 @@ _VERTEX_TRAIN_SIGNATURES = {
     "qf_vertex_shade_points_backward": (c_int, [_P, c_int32, c_int32, _P, c_int64, _P, _P, _P, _P, c_int64, _P, _P, _P, _P, _P]),
 }
 
+# include/qf_vertex_quant.h: the vertex table as 64-byte uint8 records, additive in the same way
+_VERTEX_QUANT_SIGNATURES = {
+    "qf_vertex_quant_decode": (c_int, [_P, c_int64, c_int32, c_int32, c_float, _P, c_int32, _P]),
+    "qf_vertex_quant_shade_points": (c_int, [_P, c_int64, c_int32, c_int32, c_float, _P, _P, _P, _P, _P, c_int64, _P, _P, _P, _P,
+                                             _P]),
+    "qf_vertex_quant_composite_tiles": (c_int, [_P, c_int64, c_int32, c_int32, c_float, _P, _P, _P, _P, _P, _P, c_int32, _P,
+                                                c_int32, c_int32, c_float, c_int32, _P, c_float, _P, _P, _P, _P, _P, _P]),
+    "qf_frame_render_vertex_quant": (c_int, [_P, POINTER(FrameJob), POINTER(VertexQuantShading), c_float, _P, _P]),
+}
+
 
 def vertex_row_stride(n_lobes: int) -> int:
     """Floats per row of a vertex table: the width 3 + 7L + 1 rounded up to a 64-byte line (16 / 32 / 48 / 64 for
@@ -266,7 +282,7 @@ def lib() -> ctypes.CDLL:
                 "(hipcc --offload-arch=gfx950).  quadraturefields_amd has no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
         for name, (restype, argtypes) in (list(_SIGNATURES.items()) + list(_VERTEX_BAKED_SIGNATURES.items())
-                                          + list(_VERTEX_TRAIN_SIGNATURES.items())):
+                                          + list(_VERTEX_TRAIN_SIGNATURES.items()) + list(_VERTEX_QUANT_SIGNATURES.items())):
             fn = getattr(handle, name)   # AttributeError if the symbol is not exported
             fn.restype = restype
             fn.argtypes = argtypes

@@ -12,10 +12,14 @@
   features once per mesh vertex.
 * ``VertexBakedFeatures`` / ``finetune_vertex_features``: that table as a trainable module, and the loop that fits it to
   images through the differentiable vertex shading.
+* ``quantise_vertex_features`` / ``QuantisedVertexFeatures``: that table as 64-byte uint8 records in the reference's
+  texture format, shaded in place by the ``qf_vertex_quant_*`` kernels and stored as the uint8 PNG set (DESIGN.md section
+  3.5f).
 * ``triangle_max_weights`` / ``prune_faces``: ``examples/prune_mesh_after_finetuning.py:323-373`` -- per-triangle
   maximum compositing weight over the training views, faces below 1e-3 dropped.
 """
 import ctypes
+import math
 
 import numpy as np
 import torch
@@ -175,7 +179,7 @@ def bake_texture_set(radiance_field_sg, radiance_field, V, compressor, rows_per_
             _C.check(lib.qf_bake_encode_texels(ctypes.byref(tex), _C.ptr(features), width, _C.ptr(density.reshape(-1)),
                                                _C.ptr(texel), rows * t, _C.ptr(n_dev), _C.stream()),
                      "qf_bake_encode_texels")
-    compressor._records = None            # the planes changed behind torch's version counters: rebuild on next use
+    compressor.invalidate_records()       # the planes changed behind torch's version counters: rebuild on next use
     return mask, counts.sum()
 
 
@@ -246,6 +250,115 @@ class VertexBakedFeatures(torch.nn.Module):
             raise ValueError(f"vertex_features must have V = {n_vertices} rows, got {tuple(self.table.shape)}")
 
 
+def vertex_texture_size(n_vertices: int) -> int:
+    """Side T = ceil(sqrt(V)) of the "vertex texture" that holds a V-row quantised vertex table: vertex v lives at texel
+    (v // T, v % T)."""
+    n = int(n_vertices)
+    if n < 1:
+        raise ValueError(f"n_vertices must be >= 1, got {n_vertices!r}")
+    return math.isqrt(n - 1) + 1
+
+
+class QuantisedVertexFeatures:
+    """The vertex-baked asset quantised to the reference's texture format: a
+    ``FeatureCompression`` of side ``vertex_texture_size(V)`` whose texel (v // T, v % T) holds vertex v and whose texels
+    ``>= V`` are zero, so that ``compressor.records()`` is the [T*T, 64] uint8 vertex record table (row v = vertex v) the
+    ``qf_vertex_quant_*`` kernels read, and ``compressor.save_to_file`` its on-disk form (the uint8 PNG set).  Inference
+    only, no ``nn.Module``: every function that takes ``vertex_features`` takes this and dispatches on the type; where a
+    gradient is wanted (``finetune_vertex_features``) it is refused with ``TypeError`` -- ``dequantise()`` gives the fp32
+    table a ``VertexBakedFeatures`` can go on fitting.  Built by ``quantise_vertex_features`` or ``load``."""
+
+    def __init__(self, compressor, n_vertices: int):
+        n_vertices = int(n_vertices)
+        t = vertex_texture_size(n_vertices)
+        if tuple(compressor.alpha.shape) != (t, t):
+            raise ValueError(f"a vertex texture of {n_vertices} vertices is {t} x {t}, the texture set is "
+                             f"{tuple(compressor.alpha.shape)}")
+        self.compressor = compressor
+        self.n_vertices = n_vertices
+        self.n_lobes = int(compressor.num_lobes)
+
+    @property
+    def width(self) -> int:
+        return 3 + 7 * self.n_lobes + 1
+
+    @property
+    def device(self):
+        return self.compressor.alpha.device
+
+    @property
+    def sigmoid_codec(self) -> int:
+        return 1 if self.compressor.compression_type == "sigma" else 0     # the reference's string test (B-7)
+
+    def records(self) -> torch.Tensor:
+        """[T*T, 64] uint8 on the device: row v is vertex v's record (``FeatureCompression.records``, cached)."""
+        return self.compressor.records()
+
+    def check_rows(self, n_vertices: int) -> None:
+        if self.n_vertices != n_vertices:
+            raise ValueError(f"vertex_features must have V = {n_vertices} rows, got {self.n_vertices}")
+
+    def save(self, path_prefix: str) -> None:
+        """The PNG set of ``FeatureCompression.save_to_file``: 2 + 2L files ``path_prefix + name``."""
+        self.compressor.save_to_file(path_prefix)
+
+    @classmethod
+    def load(cls, path_prefix: str, n_vertices: int, num_lobes: int, compression_type: str = "linear",
+             lambda_thres: float = 7.5, device="cuda:0"):
+        from .texture_utils import FeatureCompression
+        comp = FeatureCompression(num_lobes, path=path_prefix, compression_type=compression_type, lambda_thres=lambda_thres,
+                                  device=device)
+        return cls(comp, n_vertices)
+
+    @torch.no_grad()
+    def dequantise(self, padded: bool = False) -> torch.Tensor:
+        """The decoded table, float32 [V, 3 + 7L + 1] (``padded``: [V, ``_C.vertex_row_stride(L)``], the kernels' layout):
+        row v is what ``get_features_from_texture_map`` returns for vertex v's texel, bit for bit
+        (``qf_vertex_quant_decode``).  The shading of this object equals the fp32 route's on this table bit for bit."""
+        records = self.records()
+        stride = _C.vertex_row_stride(self.n_lobes) if padded else self.width
+        out = torch.empty((self.n_vertices, stride), dtype=torch.float32, device=records.device)
+        with torch.cuda.device(records.device):
+            _C.check(_C.lib().qf_vertex_quant_decode(_C.ptr(records), self.n_vertices, self.n_lobes, self.sigmoid_codec,
+                                                     float(self.compressor.lambda_thres), _C.ptr(out), stride, _C.stream()),
+                     "qf_vertex_quant_decode")
+        return out
+
+
+@torch.no_grad()
+def quantise_vertex_features(vertex_features, compression_type: str = "linear", lambda_thres: float = 7.5,
+                             device=None) -> QuantisedVertexFeatures:
+    """Quantise a vertex table -- a [V, 3 + 7L + 1] tensor or a ``VertexBakedFeatures``, e.g. one that
+    ``finetune_vertex_features`` fitted -- with the codecs of the texture bake: ONE ``qf_bake_encode_texels`` launch on a
+    zeroed T x T set with ``texel = arange(V)`` and the density taken from the last column, so the codes are exactly what
+    ``bake_texture_set`` would write for those rows.  ``device``: where the asset lives (default: the table's)."""
+    from .texture_utils import FeatureCompression
+    feats = vertex_features.features() if isinstance(vertex_features, VertexBakedFeatures) else torch.as_tensor(vertex_features)
+    if feats.dim() != 2 or feats.shape[0] < 1:
+        raise ValueError(f"vertex features must be [V, 3 + 7L + 1] with V >= 1, got {tuple(feats.shape)}")
+    lobes, rest = divmod(int(feats.shape[1]) - 4, 7)
+    if rest or not 1 <= lobes <= _C.QF_MAX_LOBES:
+        raise ValueError(f"vertex features must have 3 + 7 L + 1 columns with 1 <= L <= {_C.QF_MAX_LOBES}, got {feats.shape[1]}")
+    n = int(feats.shape[0])
+    t = vertex_texture_size(n)
+    if t > MAX_TEXTURE_SIDE:
+        raise ValueError(f"{n} vertices need a {t} x {t} vertex texture, the limit is {MAX_TEXTURE_SIDE}")
+    dev = _C.resolve_device(feats.device if device is None else device)
+    feats = _C.f32c(feats.detach().to(dev))
+    comp = FeatureCompression(lobes, initialize=True, texture_size=t, compression_type=compression_type,
+                              lambda_thres=lambda_thres, device=dev)
+    with torch.cuda.device(dev):
+        density = feats[:, -1].contiguous()
+        texel = torch.arange(n, dtype=torch.int32, device=dev)
+        n_dev = torch.full((1,), n, dtype=torch.int64, device=dev)
+        tex = comp.texture_set()
+        _C.check(_C.lib().qf_bake_encode_texels(ctypes.byref(tex), _C.ptr(feats), int(feats.shape[1]), _C.ptr(density),
+                                                _C.ptr(texel), n, _C.ptr(n_dev), _C.stream()), "qf_bake_encode_texels")
+        comp.invalidate_records()             # the planes changed behind torch's version counters
+        comp.records()                        # packed here, on the encoding stream: ordered for any later consumer
+    return QuantisedVertexFeatures(comp, n)
+
+
 def finetune_vertex_features(module, mesh_intersect, next_batch, steps: int, lr: float = 1e-2, train_density: bool = False,
                              bg_color="white", render_step_size=None):
     """Fit a ``VertexBakedFeatures`` to images: ``steps`` times ``next_batch() -> (Rays,
@@ -259,7 +372,8 @@ def finetune_vertex_features(module, mesh_intersect, next_batch, steps: int, lr:
     from . import utils
     from .optim import Adam
     if not isinstance(module, VertexBakedFeatures):
-        raise TypeError("finetune_vertex_features takes a VertexBakedFeatures")
+        raise TypeError("finetune_vertex_features takes a VertexBakedFeatures (a QuantisedVertexFeatures is inference only: "
+                        "fit VertexBakedFeatures(q.dequantise()) and quantise the result)")
     # the renderer composites with the mesh's step (the loader's pack carries no deltas): a value given here replaces it
     # for the run
     was_step = mesh_intersect.render_step_size

@@ -17,7 +17,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libqf_hip.so")
 ARCH = "gfx950"
 
 # (source, extra flags).  No FMA contraction in the index-exact stages (exact_common.h: bvh_traverse, raster, sample_pack,
-# texture, baked_frame, vertex_baked, vertex_train, front_frame, grid_march and volumetric carry every integer-deciding comparison), bake.hip (the fp32 codecs), texel_fill.hip (the fp64 rules of the texel-position
+# texture, baked_frame, vertex_baked, vertex_train, vertex_quant, front_frame, grid_march and volumetric carry every integer-deciding comparison), bake.hip (the fp32 codecs), texel_fill.hip (the fp64 rules of the texel-position
 # map), marching_cubes.hip (the fp32 vertex rule and the fp64 face decider), vertex_clustering.hip (the fp64 cell, mean
 # and quadric rules), uv_atlas.hip (the fp64 measure, class and corner rules) and bvh_build_device.hip (the fp32 Morton
 # keys of the device BVH build).
@@ -40,6 +40,7 @@ SOURCES = [
     ("baked_frame.hip", ["-ffp-contract=off"]),
     ("vertex_baked.hip", ["-ffp-contract=off"]),
     ("vertex_train.hip", ["-ffp-contract=off"]),
+    ("vertex_quant.hip", ["-ffp-contract=off"]),
     ("front_frame.hip", ["-ffp-contract=off"]),
     ("bake.hip", ["-ffp-contract=off"]),
     ("grid_march.hip", ["-ffp-contract=off"]),
@@ -67,6 +68,7 @@ def _hipcc() -> str:
 def _deps(src: str):
     deps = [os.path.join(CSRC, src), os.path.join(ROOT, "include", "qf_hip.h"),
             os.path.join(ROOT, "include", "qf_vertex_baked.h"), os.path.join(ROOT, "include", "qf_vertex_train.h"),
+            os.path.join(ROOT, "include", "qf_vertex_quant.h"),
             os.path.abspath(__file__)]
     deps += [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     return deps

@@ -6,10 +6,12 @@
 // qf_composite_tiles_trimax (the tile compositor that folds its weights into the triangles); qf_frame_render_baked is the
 // sampling half (no field) followed by qf_texture_composite_tiles (the baked-texture frame, shaded and composited front to
 // back in one launch) and qf_frame_render_vertex_baked the same with qf_vertex_composite_tiles (the vertex-baked frame,
-// include/qf_vertex_baked.h); qf_frame_render_front is the sequence up to the tile pack followed by the rank windows of
+// include/qf_vertex_baked.h) and qf_frame_render_vertex_quant with qf_vertex_quant_composite_tiles (its quantised table,
+// include/qf_vertex_quant.h); qf_frame_render_front is the sequence up to the tile pack followed by the rank windows of
 // front_frame.hip (select launches + one field launch per window) and their finish: the field frame front to back with
 // early ray termination.
 #include "qf_common.h"
+#include "qf_vertex_quant.h"
 #include "vertex_baked_device.h"
 
 namespace {
@@ -205,6 +207,31 @@ extern "C" int qf_frame_render_vertex_baked(qf_bvh *bvh, const qf_frame_job *job
                                      j.depth_c, j.tri_c, j.final_count, j.max_hits, j.tile_base, j.camera->width,
                                      j.camera->height, j.delta_const, j.bg_mode, j.bkgd, stop_tau, j.out_rgb, j.out_alpha,
                                      j.out_depth, j.out_packed, shaded_count, stream);
+}
+
+extern "C" int qf_frame_render_vertex_quant(qf_bvh *bvh, const qf_frame_job *job, const qf_vertex_quant_shading *shading,
+                                            float stop_tau, int32_t *shaded_count, void *stream)
+{
+    if (!bvh || !job || !job->camera || !shading) return QF_ERR_INVALID_ARGUMENT;
+    const qf_frame_job &j = *job;
+    // The whole job is checked before the first launch, as in qf_frame_render_vertex_baked: no field -- the colours come
+    // from the vertex records --, the samples' triangle ids, then what qf_vertex_quant_composite_tiles tests.
+    if (j.field || !j.tri_c) return QF_ERR_INVALID_ARGUMENT;
+    if (!shading->records || reinterpret_cast<uintptr_t>(shading->records) % 16 != 0 || !shading->tri_records ||
+        shading->n_vertices < 1 || shading->n_vertices > 0x7fffffff)
+        return QF_ERR_INVALID_ARGUMENT;
+    if (shading->n_lobes < 1 || shading->n_lobes > QF_MAX_LOBES) return QF_ERR_UNSUPPORTED;
+    if (j.bg_mode < 0 || j.bg_mode > 3) return QF_ERR_INVALID_ARGUMENT;
+    if (!j.out_packed && (!j.out_rgb || !j.out_alpha || !j.out_depth)) return QF_ERR_INVALID_ARGUMENT;
+    if (j.bg_mode == QF_BG_CUSTOM && !j.bkgd) return QF_ERR_INVALID_ARGUMENT;
+    if (!(stop_tau >= 0.0f)) return QF_ERR_INVALID_ARGUMENT;                  // NaN or negative
+    int rc = frame_sequence(bvh, job, nullptr, stream);                      // intersection ... tile pack (per-ray lists)
+    if (rc != QF_OK) return rc;
+    return qf_vertex_quant_composite_tiles(shading->records, shading->n_vertices, shading->n_lobes, shading->sigmoid_codec,
+                                           shading->lambda_thres, shading->tri_records, j.xyz_c, j.dirs_c, j.depth_c, j.tri_c,
+                                           j.final_count, j.max_hits, j.tile_base, j.camera->width, j.camera->height,
+                                           j.delta_const, j.bg_mode, j.bkgd, stop_tau, j.out_rgb, j.out_alpha, j.out_depth,
+                                           j.out_packed, shaded_count, stream);
 }
 
 extern "C" int qf_frame_render_front(qf_bvh *bvh, const qf_frame_job *job, float stop_tau, const int32_t *rank_windows,

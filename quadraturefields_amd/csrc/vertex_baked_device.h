@@ -38,6 +38,14 @@ __device__ __forceinline__ void vertex_barycentrics(const VertexTriRecord &r, fl
     b[2] = (float)bd[2];
 }
 
+// One column of the blend: (f0 * b0 + f1 * b1) + f2 * b2, each operation rounded on its own.  The one definition every
+// vertex route blends with (the fp32 table here, the quantised records of vertex_quant_device.h): the same bits in all.
+__device__ __forceinline__ float vertex_blend_column(float f0, float f1, float f2, const float b[3])
+{
+#pragma clang fp contract(off)
+    return (f0 * b[0] + f1 * b[1]) + f2 * b[2];
+}
+
 // blend[c] = (f0[c] * b0 + f1[c] * b1) + f2[c] * b2 for the columns of the n16 data-carrying 16-byte pieces, f_k = row v_k
 // of the table; the columns past them are zero and not read.  The blend accumulates piece by piece: three 16-byte loads,
 // four columns, next piece -- three whole rows are never live.  Every index of `blend` is a compile-time constant.
@@ -53,10 +61,10 @@ __device__ __forceinline__ void vertex_blend(const float *__restrict__ table, in
         float4 q = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         if (k < n16) {                             // wave-uniform
             const float4 f0 = r0[k], f1 = r1[k], f2 = r2[k];
-            q.x = (f0.x * b[0] + f1.x * b[1]) + f2.x * b[2];
-            q.y = (f0.y * b[0] + f1.y * b[1]) + f2.y * b[2];
-            q.z = (f0.z * b[0] + f1.z * b[1]) + f2.z * b[2];
-            q.w = (f0.w * b[0] + f1.w * b[1]) + f2.w * b[2];
+            q.x = vertex_blend_column(f0.x, f1.x, f2.x, b);
+            q.y = vertex_blend_column(f0.y, f1.y, f2.y, b);
+            q.z = vertex_blend_column(f0.z, f1.z, f2.z, b);
+            q.w = vertex_blend_column(f0.w, f1.w, f2.w, b);
         }
         blend[4 * k] = q.x; blend[4 * k + 1] = q.y; blend[4 * k + 2] = q.z; blend[4 * k + 3] = q.w;
     }

@@ -433,7 +433,11 @@ class FrameRenderer:
         if prepared is not None:
             job, frame, token = prepared
             dev, n = ri.device, frame.width * frame.height
-            shading, keep = utils.vertex_baked_shading_struct(self.mesh_intersect, vertex_features)
+            quant = isinstance(vertex_features, utils.QuantisedVertexFeatures)
+            if quant:
+                shading, keep = utils.vertex_quant_shading_struct(self.mesh_intersect, vertex_features)
+            else:
+                shading, keep = utils.vertex_baked_shading_struct(self.mesh_intersect, vertex_features)
             rgb = torch.empty((n, 3), dtype=torch.float32, device=dev)
             alpha = torch.empty((n, 1), dtype=torch.float32, device=dev)
             depth = torch.empty((n, 1), dtype=torch.float32, device=dev)
@@ -441,8 +445,9 @@ class FrameRenderer:
             job.out_rgb, job.out_alpha, job.out_depth = rgb.data_ptr(), alpha.data_ptr(), depth.data_ptr()
             job.delta_const, job.bg_mode = float(self.render_step_size), utils._BG.get(self.bg_color, _C.BG_CUSTOM)
             ri.last_route = "frame+cull" if job.cull_chunks & 1 else "frame"
-            _C.check(_C.lib().qf_frame_render_vertex_baked(ri._handle, ctypes.byref(job), ctypes.byref(shading), stop_tau,
-                                                           _C.ptr(shaded), _C.stream()), "qf_frame_render_vertex_baked")
+            bound = _C.lib().qf_frame_render_vertex_quant if quant else _C.lib().qf_frame_render_vertex_baked
+            _C.check(bound(ri._handle, ctypes.byref(job), ctypes.byref(shading), stop_tau, _C.ptr(shaded), _C.stream()),
+                     "qf_frame_render_vertex_quant" if quant else "qf_frame_render_vertex_baked")
             ri.fused_frame_done(frame, token)
             frame._keep = frame._keep + keep      # referenced until their readers ran
         else:
@@ -476,13 +481,15 @@ class FrameRenderer:
         reading vertex rows once the transmittance in front of the next sample has fallen below it
         (``qf_vertex_composite_tiles`` -- the one bound call ``qf_frame_render_vertex_baked`` when the frame is the
         library's fixed sequence; 0 never stops and gives the route above bit for bit).  ``last_frame.shaded_count`` of
-        the intersector then holds the samples of each pixel that contributed.  Returns (rgb, alpha, depth, n_samples)."""
+        the intersector then holds the samples of each pixel that contributed.  A ``baking.QuantisedVertexFeatures`` takes
+        the same routes through the ``qf_vertex_quant_*`` kernels (64-byte uint8 records per vertex, DESIGN.md section
+        3.5f): the pixels of its ``dequantise()`` table, bit for bit.  Returns (rgb, alpha, depth, n_samples)."""
         n_rays = origins.shape[0]
         if early_stop_eps is not None:
             stop_tau = utils.early_stop_tau(early_stop_eps)
             if camera is None:
                 raise NotImplementedError("early_stop_eps needs a camera frame: the ray-major route shades every sample")
-        utils.vertex_baked_shading(self.mesh_intersect, vertex_features)      # a malformed table raises before any sampling
+        utils.check_vertex_features(self.mesh_intersect, vertex_features)     # a malformed table raises before any sampling
         if early_stop_eps is not None:
             ri = self.mesh_intersect.rayintersector
             rgb, alpha, depth, frame = self._render_vertex_baked_front_to_back(origins, viewdirs, vertex_features, camera,

@@ -186,6 +186,11 @@ class FeatureCompression:
             cache = self._records = _C.StreamCached(tuple((p.data_ptr(), p._version) for p in planes), rec, [rec])
         return cache.get()                 # ordered for a consumer on another stream than the one that packed them
 
+    def invalidate_records(self) -> None:
+        """Drop the cached records: for a caller that wrote the planes through raw pointers (a kernel launch), which
+        torch's version counters do not see.  The next ``records()`` packs them again."""
+        self._records = None
+
     def shade(self, indices, dirs):
         """Fused fetch + dequantise + spherical-Gaussian shading: (rgb [S,3], sigma [S]) from the interleaved texel
         records (one sector per sample)."""

@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _C
-from .baking import VertexBakedFeatures
+from .baking import QuantisedVertexFeatures, VertexBakedFeatures
 from .datasets.utils import Rays, namedtuple_map
 from .field import Field as _Field
 from .mesh_utils import SampleSet, SampleWindow
@@ -666,7 +666,7 @@ def _vertex_lobes(width: int) -> int:
 
 
 def _vertex_features_lobes(vertex_features) -> int:
-    if isinstance(vertex_features, VertexBakedFeatures):
+    if isinstance(vertex_features, (VertexBakedFeatures, QuantisedVertexFeatures)):
         return vertex_features.n_lobes
     return _vertex_lobes(vertex_features.shape[1])
 
@@ -728,6 +728,38 @@ def vertex_baked_shading_struct(mesh_intersect, vertex_features):
     return s, (table, records)
 
 
+def vertex_quant_shading(mesh_intersect, quantised):
+    """What the quantised vertex kernels read, on the device: (records, tri_records).
+    ``records``: the [T*T, 64] uint8 vertex records of a ``baking.QuantisedVertexFeatures`` (its texture set's texel
+    records, cached there and ordered across streams); ``tri_records``: the mesh's 128-byte vertex-triangle records, the
+    fp32 route's own cache."""
+    quantised.check_rows(mesh_intersect.mesh.vertices.shape[0])
+    records = quantised.records()
+    if records.device != _C.resolve_device(mesh_intersect.device) or records.data_ptr() % 16:
+        raise ValueError(f"the QuantisedVertexFeatures records must be 16-byte aligned and on {mesh_intersect.device}, "
+                         f"they are on {records.device}")
+    return records, _vertex_records(mesh_intersect)[1].get()[0]
+
+
+def vertex_quant_shading_struct(mesh_intersect, quantised):
+    """The ``qf_vertex_quant_shading`` of a (mesh, ``QuantisedVertexFeatures``): (struct, tensors it points at -- keep them
+    referenced until the launch that reads them ran)."""
+    records, tri_records = vertex_quant_shading(mesh_intersect, quantised)
+    s = _C.VertexQuantShading()
+    s.records, s.tri_records = records.data_ptr(), tri_records.data_ptr()
+    s.n_vertices, s.n_lobes = quantised.n_vertices, quantised.n_lobes
+    s.sigmoid_codec, s.lambda_thres = quantised.sigmoid_codec, float(quantised.compressor.lambda_thres)
+    return s, (records, tri_records)
+
+
+def check_vertex_features(mesh_intersect, vertex_features) -> None:
+    """Raises for a table that does not fit the mesh (either kind), before anything is sampled."""
+    if isinstance(vertex_features, QuantisedVertexFeatures):
+        vertex_quant_shading(mesh_intersect, vertex_features)
+    else:
+        vertex_baked_shading(mesh_intersect, vertex_features)
+
+
 class _VertexShadeFn(torch.autograd.Function):
     """Differentiable vertex shading: forward = ``qf_vertex_shade_points`` on the padded table,
     backward = ``qf_vertex_shade_points_backward`` into a zero-filled [V, stride] gradient.  Only inputs are saved: the
@@ -769,6 +801,26 @@ def _vertex_table_trains(vertex_features) -> bool:
             and vertex_features.table.requires_grad)
 
 
+@torch.no_grad()
+def _shade_vertex_quant_points(mesh_intersect, quantised, points, index_tri, dirs, n_device, want_features):
+    records, tri_records = vertex_quant_shading(mesh_intersect, quantised)
+    lobes = quantised.n_lobes
+    points, dirs = _C.f32c(points), _C.f32c(dirs)
+    tri32 = index_tri.contiguous() if index_tri.dtype == torch.int32 else None
+    tri64 = None if tri32 is not None else _C.i64c(index_tri)
+    n = points.shape[0]
+    rgb = torch.empty((n, 3), dtype=torch.float32, device=points.device)
+    sigma = torch.empty((n,), dtype=torch.float32, device=points.device)
+    feats = torch.empty((n, 3 + 7 * lobes + 1), dtype=torch.float32, device=points.device) if want_features else None
+    _C.check(_C.lib().qf_vertex_quant_shade_points(
+        _C.ptr(records), quantised.n_vertices, lobes, quantised.sigmoid_codec, float(quantised.compressor.lambda_thres),
+        _C.ptr(tri_records), _C.ptr(points), _C.ptr(tri64), _C.ptr(tri32), _C.ptr(dirs), n, _C.ptr(n_device, torch.int64),
+        _C.ptr(feats), _C.ptr(rgb), _C.ptr(sigma), _C.stream()), "qf_vertex_quant_shade_points")
+    if want_features:
+        return rgb, sigma, feats
+    return rgb, sigma
+
+
 def shade_vertex_baked_points(mesh_intersect, vertex_features, points, index_tri, dirs, n_device=None,
                               want_features: bool = False):
     """(rgb [n,3], sigma [n]) of samples given by position and triangle from the vertex-baked features: the unclamped
@@ -778,7 +830,11 @@ def shade_vertex_baked_points(mesh_intersect, vertex_features, points, index_tri
     ``vertex_features``: a [V, 3 + 7L + 1] tensor (inference only: detached, padded once, cached) or a
     ``baking.VertexBakedFeatures``, whose table is read in place.  With such a module whose table requires a gradient,
     while autograd is recording, rgb and sigma carry a graph to the table (``_VertexShadeFn``; ``want_features`` is then
-    not offered); every other call runs without one, as before."""
+    not offered); every other call runs without one, as before.  A ``baking.QuantisedVertexFeatures`` is shaded from its
+    64-byte records (``qf_vertex_quant_shade_points``): the values of this function on its ``dequantise()`` table, bit for
+    bit."""
+    if isinstance(vertex_features, QuantisedVertexFeatures):
+        return _shade_vertex_quant_points(mesh_intersect, vertex_features, points, index_tri, dirs, n_device, want_features)
     if _vertex_table_trains(vertex_features):
         if want_features:
             raise ValueError("want_features is an inference-only output")
@@ -816,10 +872,15 @@ def shade_composite_vertex_baked_frame(mesh_intersect, vertex_features, xyz_c, d
     walks every pixel front to back (``qf_vertex_composite_tiles``) and stops reading vertex rows once the optical depth
     in front of a pixel's next sample exceeds ``stop_tau`` (``early_stop_tau``; ``inf`` never stops and gives the two
     calls' pixels bit for bit).  Arguments and returns as ``shade_composite_baked_frame``; ``vertex_features`` a tensor or a
-    ``baking.VertexBakedFeatures`` (inference either way: the tile-order frame has no backward)."""
+    ``baking.VertexBakedFeatures`` (inference either way: the tile-order frame has no backward), or a
+    ``baking.QuantisedVertexFeatures`` (``qf_vertex_quant_composite_tiles``)."""
     if getattr(frame, "band_rows", 0) or frame.tri_c is None:
         raise ValueError("shade_composite_vertex_baked_frame: an unbanded frame with triangle ids (want_tri) is required")
-    shading, keep = vertex_baked_shading_struct(mesh_intersect, vertex_features)
+    quant = isinstance(vertex_features, QuantisedVertexFeatures)          # qf_vertex_quant_composite_tiles: same pixels as
+    if quant:                                                             # on its dequantise() table
+        shading, keep = vertex_quant_shading_struct(mesh_intersect, vertex_features)
+    else:
+        shading, keep = vertex_baked_shading_struct(mesh_intersect, vertex_features)
     xyz_c, dirs_c = _C.f32c(xyz_c), _C.f32c(dirs_c)
     dev = xyz_c.device
     n = frame.depth_c.shape[0]
@@ -837,6 +898,16 @@ def shade_composite_vertex_baked_frame(mesh_intersect, vertex_features, xyz_c, d
         alpha = torch.empty((n_rays, 1), dtype=torch.float32, device=dev)
         depth = torch.empty((n_rays, 1), dtype=torch.float32, device=dev)
     shaded = torch.empty((n_rays,), dtype=torch.int32, device=dev)
+    if quant:
+        _C.check(_C.lib().qf_vertex_quant_composite_tiles(
+            shading.records, shading.n_vertices, shading.n_lobes, shading.sigmoid_codec, shading.lambda_thres,
+            shading.tri_records, _C.ptr(xyz_c), _C.ptr(dirs_c), _C.ptr(frame.depth_c), _C.ptr(frame.tri_c, torch.int32),
+            _C.ptr(frame.hit_count), frame.max_hits, _C.ptr(frame.tile_base), frame.width, frame.height,
+            float(render_step_size), mode, _C.ptr(bk), float(stop_tau), _C.ptr(rgb), _C.ptr(alpha), _C.ptr(depth), _C.ptr(out5),
+            _C.ptr(shaded), _C.stream()), "qf_vertex_quant_composite_tiles")
+        if packed:
+            return out5, None, None, shaded
+        return rgb, alpha, depth, shaded
     _C.check(_C.lib().qf_vertex_composite_tiles(
         shading.table, shading.stride, shading.n_lobes, shading.records, _C.ptr(xyz_c), _C.ptr(dirs_c), _C.ptr(frame.depth_c),
         _C.ptr(frame.tri_c, torch.int32), _C.ptr(frame.hit_count), frame.max_hits, _C.ptr(frame.tile_base), frame.width,
@@ -865,7 +936,8 @@ def render_image_finetune_baking_with_occgrid(
     ``vertex_features`` may also be a ``baking.VertexBakedFeatures``, whose table is read in place.  With such a module
     whose table requires a gradient, while autograd is recording, colors, opacities and depths carry a graph to the table
     (``_VertexShadeFn`` followed by the differentiable ``derive_properties``); every other call
-    runs under ``torch.no_grad()`` and returns tensors without a graph, as before."""
+    runs under ``torch.no_grad()`` and returns tensors without a graph, as before.  A ``baking.QuantisedVertexFeatures``
+    (inference only) is shaded from its uint8 records: the values of its ``dequantise()`` table, bit for bit."""
     with torch.set_grad_enabled(_vertex_table_trains(vertex_features)):
         return _render_vertex_baked_ray_major(radiance_field, rays, data, timestamps, mesh_intersect, vertex_features, bg_color)
 
