@@ -2,13 +2,17 @@
 
     python examples/prune_mesh_after_finetuning.py --scene lego --data_root DATA --ckpt_path CKPT --mesh_path DIR/mesh.ply
                                                    --max_hits 25 --up_sample 2 --log2_hashmap_size 19 [--num_lobes N]
-                                                   [--num_layers L] [--scale 1.5]
+                                                   [--num_layers L] [--scale 1.5] [--compact] [--min_component_faces N]
 
 Every view of the train split is rendered at ``up_sample`` through the finetuned field (``ckpt["radiance_field"]``) and
 folded into each triangle's maximum compositing weight (``pruning.MeshPruner.add_view``: one bound call per view, no host
 wait); the faces whose maximum is not above 1e-3 are dropped.  Next to the mesh it writes ``triangle_weights.npy``,
 ``mesh_updated.ply`` -- what ``examples/generate_uv_atlas.py ROOT mesh_updated.ply ...`` reads --, ``num_samples.npy`` and
-``num_valid_samples.npy``.  The script's other flags are accepted and unused.
+``num_valid_samples.npy``.  The script's other flags are accepted and unused.  ``--compact`` also removes the vertices no
+kept face uses (and, with ``--min_component_faces N``, the vertex-connected islands of fewer than N faces) on the device
+(``mc_utils.compact_mesh``): ``mesh_updated.ply`` is then the cleaned mesh, ``face_map.npy`` and
+``vertex_map.npy`` name the source face / vertex of its rows, and V, F, the clean-up counts and the bytes of a per-vertex
+table (64-byte records) are printed before and after.
 
     python examples/prune_mesh_after_finetuning.py --synthetic OUT [--size 400] [--views 16] [--shells 6] [--subdivisions 4]
 
@@ -38,6 +42,9 @@ def parse(argv):
     ap.add_argument("--scale", type=float, default=1.5)
     ap.add_argument("--num_lobes", type=int, default=0)
     ap.add_argument("--num_layers", type=int, default=1)
+    ap.add_argument("--compact", action="store_true", help="remove the unreferenced vertices too; writes face_map.npy and vertex_map.npy")
+    ap.add_argument("--min_component_faces", type=int, default=0,
+                    help="with --compact: drop vertex-connected components of fewer faces (0 or 1: none)")
     ap.add_argument("--synthetic", metavar="OUT", type=str, default=None, help="run on the synthetic scene, write into OUT")
     ap.add_argument("--size", type=int, default=400, help="--synthetic: image width and height before up_sample")
     ap.add_argument("--views", type=int, default=16, help="--synthetic: orbit cameras")
@@ -109,8 +116,19 @@ def main(argv=None):
     for origins, viewdirs, camera in views:
         pruner.add_view(origins, viewdirs, camera)
     print("Number of faces before pruning: ", mi.mesh.faces.shape[0])
-    pruned = pruner.save(os.path.dirname(os.path.abspath(mesh_path)))
+    if args.min_component_faces and not args.compact:
+        sys.exit("prune_mesh_after_finetuning.py: --min_component_faces needs --compact")
+    pruned = pruner.save(os.path.dirname(os.path.abspath(mesh_path)), compact=args.compact,
+                         min_component_faces=args.min_component_faces)
     print("Number of faces after pruning: ", pruned.faces.shape[0])
+    if args.compact:
+        from quadraturefields_amd import mc_utils
+        stats = mc_utils.compact_mesh(mi.mesh, pruner.keep_mask(), min_component_faces=args.min_component_faces,
+                                      return_stats=True)[3]
+        v0, f0, v1, f1 = mi.mesh.vertices.shape[0], mi.mesh.faces.shape[0], pruned.vertices.shape[0], pruned.faces.shape[0]
+        print(f"before: V = {v0}, F = {f0}, vertex table {64 * v0} bytes")
+        print(f"after:  V = {v1}, F = {f1}, vertex table {64 * v1} bytes")
+        print("counts:", ", ".join(f"{k} = {v}" for k, v in stats.items()))
 
 
 if __name__ == "__main__":

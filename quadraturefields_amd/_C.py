@@ -263,6 +263,18 @@ _VERTEX_QUANT_SIGNATURES = {
     "qf_frame_render_vertex_quant": (c_int, [_P, POINTER(FrameJob), POINTER(VertexQuantShading), c_float, _P, _P]),
 }
 
+# include/qf_mesh_compact.h: mesh clean-up and the visibility mask, additive in the same way
+MESH_REMOVE_DEGENERATE, MESH_REMOVE_DUPLICATES, MESH_REMOVE_UNREFERENCED = 1, 2, 4
+MESH_COMPACT_COUNTS = ("faces", "vertices", "dropped_mask", "dropped_degenerate", "dropped_duplicate", "dropped_island",
+                       "components", "invalid_faces")
+_MESH_COMPACT_SIGNATURES = {
+    "qf_mesh_compact_workspace_bytes": (c_int64, [c_int64, c_int64]),
+    "qf_mesh_compact_count": (c_int, [_P, c_int64, _P, c_int64, _P, c_int32, c_int64, _P, c_int64, _P, _P]),
+    "qf_mesh_compact_emit": (c_int, [_P, c_int64, _P, c_int64, _P, c_int32, c_int64, _P, c_int64, _P, c_int64, _P, c_int64,
+                                     _P, _P, _P]),
+    "qf_mark_hit_faces": (c_int, [_P, _P, c_int64, c_int32, c_int64, _P, _P, _P]),
+}
+
 
 def vertex_row_stride(n_lobes: int) -> int:
     """Floats per row of a vertex table: the width 3 + 7L + 1 rounded up to a 64-byte line (16 / 32 / 48 / 64 for
@@ -282,7 +294,8 @@ def lib() -> ctypes.CDLL:
                 "(hipcc --offload-arch=gfx950).  quadraturefields_amd has no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
         for name, (restype, argtypes) in (list(_SIGNATURES.items()) + list(_VERTEX_BAKED_SIGNATURES.items())
-                                          + list(_VERTEX_TRAIN_SIGNATURES.items()) + list(_VERTEX_QUANT_SIGNATURES.items())):
+                                          + list(_VERTEX_TRAIN_SIGNATURES.items()) + list(_VERTEX_QUANT_SIGNATURES.items())
+                                          + list(_MESH_COMPACT_SIGNATURES.items())):
             fn = getattr(handle, name)   # AttributeError if the symbol is not exported
             fn.restype = restype
             fn.argtypes = argtypes

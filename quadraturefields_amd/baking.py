@@ -424,17 +424,64 @@ def triangle_max_weights(weights: torch.Tensor, index_tri: torch.Tensor, out: to
     return out
 
 
-def prune_faces(mesh: TriMesh, triangle_weights, threshold: float = 1e-3) -> TriMesh:
+def prune_faces(mesh: TriMesh, triangle_weights, threshold: float = 1e-3, compact: bool = False,
+                min_component_faces: int = 0, return_maps: bool = False):
     """Mesh with the faces whose maximum weight is <= threshold removed (vertices kept, as ``update_faces``).
     ``triangle_weights`` may also be a boolean keep mask, and either may be a device tensor: the faces are then selected
-    on the device (the weights / mask make no round trip; only the kept faces come back for the ``TriMesh``)."""
+    on the device (the weights / mask make no round trip; only the kept faces come back for the ``TriMesh``).
+    ``compact``: the unreferenced vertices are removed as well and the faces remapped, and with ``min_component_faces``
+    >= 2 the vertex-connected components of fewer faces are dropped (``mc_utils.compact_mesh``, DESIGN.md section 3.9b,
+    on the device); ``return_maps`` then returns ``(mesh, face_map, vertex_map)``, the source face / vertex of every
+    output row.  The defaults give the uncompacted mesh, where the maps are the kept faces and every vertex."""
+    if not compact and min_component_faces:
+        raise ValueError("min_component_faces needs compact=True")
+    if compact:
+        from . import mc_utils
+        if isinstance(triangle_weights, torch.Tensor):
+            t = triangle_weights.detach().reshape(-1)
+            keep = t if t.dtype == torch.bool else t > threshold
+        else:
+            tw = np.asarray(triangle_weights).reshape(-1)
+            keep = tw if tw.dtype == np.bool_ else tw > threshold
+        if keep.shape[0] != mesh.faces.shape[0]:
+            raise ValueError(f"{keep.shape[0]} weights for {mesh.faces.shape[0]} faces")
+        out = mc_utils.compact_mesh(mesh, keep, min_component_faces=min_component_faces, remove_unreferenced=True)
+        return out if return_maps else out[0]
     if isinstance(triangle_weights, torch.Tensor) and triangle_weights.is_cuda:
         t = triangle_weights.detach().reshape(-1)
         keep = t if t.dtype == torch.bool else t > threshold
         if keep.shape[0] != mesh.faces.shape[0]:
             raise ValueError(f"{keep.shape[0]} weights for {mesh.faces.shape[0]} faces")
         faces = torch.from_numpy(np.ascontiguousarray(mesh.faces)).to(t.device)[keep]
-        return TriMesh(mesh.vertices.copy(), faces.cpu().numpy(), mesh.visual.uv)
-    tw = triangle_weights.detach().cpu().numpy() if isinstance(triangle_weights, torch.Tensor) else np.asarray(triangle_weights)
-    keep = tw.reshape(-1) if tw.dtype == np.bool_ else tw.reshape(-1) > threshold
-    return TriMesh(mesh.vertices.copy(), mesh.faces[keep], mesh.visual.uv)
+        pruned = TriMesh(mesh.vertices.copy(), faces.cpu().numpy(), mesh.visual.uv)
+        keep = keep.cpu().numpy()
+    else:
+        tw = triangle_weights.detach().cpu().numpy() if isinstance(triangle_weights, torch.Tensor) else np.asarray(triangle_weights)
+        keep = tw.reshape(-1) if tw.dtype == np.bool_ else tw.reshape(-1) > threshold
+        pruned = TriMesh(mesh.vertices.copy(), mesh.faces[keep], mesh.visual.uv)
+    if return_maps:
+        return pruned, np.nonzero(keep)[0].astype(np.int64), np.arange(mesh.vertices.shape[0], dtype=np.int64)
+    return pruned
+
+
+def remap_vertex_features(vertex_features, vertex_map):
+    """The per-vertex table of a compacted mesh: rows ``vertex_map`` (``mc_utils.compact_mesh``'s, int64 [V'], array or
+    tensor) of ``vertex_features``.  A tensor [V, W] comes back as a tensor, a ``VertexBakedFeatures`` as a new module
+    (same lobes, same ``train_density``, on the same device) whose table holds the selected rows bit for bit.  A
+    ``QuantisedVertexFeatures`` is refused with ``TypeError``: its records sit in a vertex texture laid out by V, so
+    quantise after compaction (``quantise_vertex_features`` of the remapped fp32 table)."""
+    if isinstance(vertex_features, QuantisedVertexFeatures):
+        raise TypeError("remap_vertex_features: a QuantisedVertexFeatures cannot be remapped (its vertex texture is laid "
+                        "out by V); compact the mesh first, remap the fp32 table and quantise after compaction")
+    table = vertex_features.table.detach() if isinstance(vertex_features, VertexBakedFeatures) else vertex_features
+    if not isinstance(table, torch.Tensor) or table.dim() != 2:
+        raise TypeError("vertex_features must be a [V, W] tensor or a VertexBakedFeatures")
+    idx = torch.as_tensor(np.asarray(vertex_map) if not isinstance(vertex_map, torch.Tensor) else vertex_map)
+    if idx.dim() != 1 or idx.dtype not in (torch.int64, torch.int32):
+        raise ValueError(f"vertex_map must be an int64 vector, got {idx.dtype} {tuple(idx.shape)}")
+    idx = idx.to(device=table.device, dtype=torch.int64)
+    if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= table.shape[0]):
+        raise IndexError(f"vertex_map reaches outside the table's {table.shape[0]} rows")
+    if isinstance(vertex_features, VertexBakedFeatures):
+        return VertexBakedFeatures(vertex_features.features()[idx], train_density=vertex_features.train_density)
+    return table[idx]

@@ -5,8 +5,13 @@ scikit-image's marching cubes there, twice: over ``sin(omega * q)`` for the nest
 density.  Here the marching cubes is the HIP kernel of ``csrc/marching_cubes.hip`` (``qf_marching_cubes_count`` /
 ``qf_marching_cubes_emit``, rules in DESIGN.md section 3.8); the steps around it stay torch ops on the device.
 ``transmittance_mask`` is the device form of ``grid_transmittance_synthetic`` (examples/mc_utils.py:462-570).
+``compact_mesh_device`` / ``compact_mesh`` clean a mesh (keep mask, degenerate and duplicate faces, small islands,
+unreferenced vertices; ``csrc/mesh_compact.hip``, rules in DESIGN.md section 3.9b), and ``prunning_mesh_train_visibility``
+/ ``prunning_mesh_train_visibility_complement`` are the reference's visibility pruning (examples/mc_utils.py:272-345) on
+top of them.
 """
 import math
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -272,3 +277,179 @@ def transmittance_mask(radiance_field, estimator, views, *, max_samples=1024, ch
         mark_visited_cells(radiance_field.normalize(positions)[1], mask)
     up = F.interpolate(mask[None, None].to(torch.float32), size=(int(size),) * 3, mode="trilinear", align_corners=False)
     return up[0, 0] > 0.5
+
+
+# ---- mesh clean-up (include/qf_mesh_compact.h) ---------------------------------------------------
+
+CompactedMesh = namedtuple("CompactedMesh", ["vertices", "faces", "face_map", "vertex_map", "stats"])
+
+
+def _device_keep(keep, n_faces: int, device) -> torch.Tensor:
+    """A keep mask (tensor or array, bool or integer) as a contiguous device uint8 [F]; None stays None."""
+    if keep is None:
+        return None
+    k = keep if isinstance(keep, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(keep))
+    k = k.reshape(-1)
+    if k.shape[0] != n_faces:
+        raise ValueError(f"{k.shape[0]} keep flags for {n_faces} faces")
+    if k.is_floating_point() or k.is_complex():
+        raise TypeError(f"keep must be a bool or integer mask, got {k.dtype}")
+    k = k.to(device)
+    return (k if k.dtype == torch.uint8 else (k != 0).to(torch.uint8)).contiguous()
+
+
+def compact_mesh_device(vertices: torch.Tensor, faces: torch.Tensor, keep=None, *, remove_degenerate: bool = False,
+                        remove_duplicates: bool = False, min_component_faces: int = 0,
+                        remove_unreferenced: bool = True) -> CompactedMesh:
+    """Clean a mesh on the device under the rules of DESIGN.md section 3.9b, in this order: faces with ``keep[f] == 0``
+    dropped; faces with two equal indices dropped (``remove_degenerate``); faces whose sorted index triple an earlier
+    surviving face has dropped (``remove_duplicates``); faces of vertex-connected components with fewer than
+    ``min_component_faces`` faces dropped (when >= 2); vertices no surviving face uses removed and the faces remapped
+    (``remove_unreferenced``).  ``vertices``: device float [V,3] (fp32 is widened exactly), ``faces``: device int64 or
+    int32 [F,3], ``keep``: bool / integer [F] or None.  Returns ``CompactedMesh(vertices fp64 [V',3], faces int64
+    [F',3], face_map int64 [F'], vertex_map int64 [V'], stats)``: the maps name the source face / vertex of every output
+    row, ``stats`` is a dict of the eight counts (``_C.MESH_COMPACT_COUNTS``).  One host wait, for the counts.  Raises
+    ValueError for host tensors, bad shapes and, with their number, faces that index outside [0, V)."""
+    if not isinstance(vertices, torch.Tensor) or not isinstance(faces, torch.Tensor):
+        raise TypeError("vertices and faces must be torch.Tensors")
+    if vertices.ndim != 2 or vertices.shape[1] != 3 or faces.ndim != 2 or faces.shape[1] != 3:
+        raise ValueError(f"vertices and faces must be [N,3], got {tuple(vertices.shape)} and {tuple(faces.shape)}")
+    if not vertices.is_floating_point():
+        raise TypeError(f"vertices must be floating point, got {vertices.dtype}")
+    if faces.dtype not in (torch.int64, torch.int32):
+        raise TypeError(f"faces must be int64 or int32, got {faces.dtype}")
+    m = int(min_component_faces)
+    if m != min_component_faces or m < 0 or m >= 2 ** 31:
+        raise ValueError(f"min_component_faces must be an integer in [0, 2^31), got {min_component_faces}")
+    if not vertices.is_cuda or not faces.is_cuda:
+        raise ValueError("compact_mesh_device needs device tensors (quadraturefields_amd has no CPU fallback)")
+    if vertices.device != faces.device:
+        raise ValueError(f"vertices on {vertices.device} and faces on {faces.device}")
+    n_v, n_f = vertices.shape[0], faces.shape[0]
+    if n_v >= 2 ** 31 or n_f >= 2 ** 31:
+        raise ValueError(f"the mesh has {n_v} vertices and {n_f} faces; both must be < 2^31")
+    dev = vertices.device
+    k = _device_keep(keep, n_f, dev)
+    flags = ((_C.MESH_REMOVE_DEGENERATE if remove_degenerate else 0) | (_C.MESH_REMOVE_DUPLICATES if remove_duplicates else 0)
+             | (_C.MESH_REMOVE_UNREFERENCED if remove_unreferenced else 0))
+    if n_v == 0:
+        if n_f:
+            raise ValueError(f"{n_f} faces have an index outside [0, 0)")
+        empty = torch.empty((0,), dtype=torch.int64, device=dev)
+        return CompactedMesh(torch.empty((0, 3), dtype=torch.float64, device=dev), empty.reshape(0, 3), empty,
+                             empty.clone(), dict.fromkeys(_C.MESH_COMPACT_COUNTS, 0))
+    v = vertices.to(torch.float64).contiguous()
+    f = faces.to(torch.int64).contiguous()
+    lib = _C.lib()
+    with torch.cuda.device(dev):
+        ws_bytes = int(lib.qf_mesh_compact_workspace_bytes(n_v, n_f))
+        if ws_bytes < 0:
+            raise RuntimeError(f"qf_mesh_compact_workspace_bytes refused V={n_v}, F={n_f}")
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+        counts = torch.empty((8,), dtype=torch.int64, device=dev)
+        _C.check(lib.qf_mesh_compact_count(_C.ptr(v), n_v, _C.ptr(f), n_f, _C.ptr(k), flags, m, _C.ptr(ws), ws_bytes,
+                                           _C.ptr(counts), _C.stream()), "qf_mesh_compact_count")
+        stats = dict(zip(_C.MESH_COMPACT_COUNTS, counts.tolist()))
+        if stats["invalid_faces"]:
+            raise ValueError(f"{stats['invalid_faces']} faces have an index outside [0, {n_v})")
+        out_v = torch.empty((stats["vertices"], 3), dtype=torch.float64, device=dev)
+        out_f = torch.empty((stats["faces"], 3), dtype=torch.int64, device=dev)
+        face_map = torch.empty((stats["faces"],), dtype=torch.int64, device=dev)
+        vertex_map = torch.empty((stats["vertices"],), dtype=torch.int64, device=dev)
+        _C.check(lib.qf_mesh_compact_emit(_C.ptr(v), n_v, _C.ptr(f), n_f, _C.ptr(k), flags, m, _C.ptr(ws), ws_bytes,
+                                          _C.ptr(out_v), out_v.shape[0], _C.ptr(out_f), out_f.shape[0], _C.ptr(face_map),
+                                          _C.ptr(vertex_map), _C.stream()), "qf_mesh_compact_emit")
+    return CompactedMesh(out_v, out_f, face_map, vertex_map, stats)
+
+
+def compact_mesh(mesh: TriMesh, keep=None, device="cuda", return_stats: bool = False, **options):
+    """``compact_mesh_device`` on a ``TriMesh``: ``(TriMesh, face_map, vertex_map)`` with numpy int64 maps (and the
+    stats dict fourth with ``return_stats``).  Per-vertex ``visual.uv`` is carried through ``vertex_map``.  ``keep`` may
+    be a device tensor: it then makes no round trip."""
+    dev = keep.device if isinstance(keep, torch.Tensor) and keep.is_cuda else _C.resolve_device(device)
+    out = compact_mesh_device(torch.from_numpy(np.asarray(mesh.vertices, np.float64)).to(dev),
+                              torch.from_numpy(np.asarray(mesh.faces, np.int64)).to(dev), keep, **options)
+    vertex_map = out.vertex_map.cpu().numpy()
+    uv = None if mesh.visual.uv is None else np.asarray(mesh.visual.uv)[vertex_map]
+    cleaned = TriMesh(out.vertices.cpu().numpy(), out.faces.cpu().numpy(), uv)
+    res = (cleaned, out.face_map.cpu().numpy(), vertex_map)
+    return res + (out.stats,) if return_stats else res
+
+
+def mark_hit_faces(hit_tri: torch.Tensor, hit_count, mask: torch.Tensor, out_of_range: torch.Tensor = None) -> None:
+    """``mask[id] = 1`` for the triangle ids of an intersector's lists (``qf_mark_hit_faces``), in place, one launch, no
+    host wait: ``hit_tri`` device int32 [n_rays, max_hits] (-1 padded), ``hit_count`` device int32 [n_rays] (slots
+    ``k < min(hit_count[r], max_hits)`` are considered) or None (every slot with an id >= 0 is), ``mask`` device uint8
+    or bool [n_faces].  An id outside [0, n_faces) writes nothing and adds one to ``out_of_range`` (device int64 [1],
+    optional).  Only ever sets bytes: views accumulate into one mask."""
+    if not isinstance(hit_tri, torch.Tensor) or not isinstance(mask, torch.Tensor):
+        raise TypeError("hit_tri and mask must be torch.Tensors")
+    if not hit_tri.is_cuda or not mask.is_cuda:
+        raise ValueError("mark_hit_faces needs device tensors (quadraturefields_amd has no CPU fallback)")
+    if hit_tri.ndim != 2 or hit_tri.shape[1] < 1:
+        raise ValueError(f"hit_tri must be [n_rays, max_hits >= 1], got shape {tuple(hit_tri.shape)}")
+    if mask.ndim != 1 or not mask.is_contiguous() or mask.dtype not in (torch.uint8, torch.bool):
+        raise ValueError(f"mask must be a contiguous uint8 or bool vector, got {mask.dtype} {tuple(mask.shape)}")
+    n_rays, k = hit_tri.shape
+    if hit_count is not None and (hit_count.dtype != torch.int32 or hit_count.numel() != n_rays
+                                  or hit_count.device != hit_tri.device):
+        raise ValueError("hit_count must be int32 [n_rays] on hit_tri's device")
+    if out_of_range is not None and (out_of_range.dtype != torch.int64 or out_of_range.numel() != 1
+                                     or out_of_range.device != mask.device):
+        raise ValueError("out_of_range must be one int64 on the mask's device")
+    with torch.cuda.device(mask.device):
+        _C.check(_C.lib().qf_mark_hit_faces(_C.ptr(hit_tri.contiguous(), torch.int32),
+                                            _C.ptr(hit_count.contiguous()) if hit_count is not None else None, n_rays, k,
+                                            mask.shape[0], _C.ptr(mask.view(torch.uint8)), _C.ptr(out_of_range),
+                                            _C.stream()), "qf_mark_hit_faces")
+
+
+@torch.no_grad()
+def train_visibility_mask(mesh, train_dataset, max_hits: int = 5, bvh_builder: str = "host", device="cuda"):
+    """``(mesh, mask)``: the ``TriMesh`` and the device uint8 [F] mask of the faces some training ray hits among its
+    first ``max_hits`` hits -- the loop of the reference's ``prunning_mesh_train_visibility`` (examples/mc_utils.py:
+    309-339).  ``mesh``: a ``TriMesh`` (an intersector is built for it, ``bvh_builder`` as ``RayIntersector``'s) or a
+    ``MeshIntersection`` (its intersector is used).  Per item of ``train_dataset`` (the first ``len(images)`` when it has
+    ``images``) the rays ``item["rays"].origins / .viewdirs`` go through the intersector's id lists (``hits``) and
+    ``qf_mark_hit_faces``; nothing waits on the host per view.  Raises IndexError when an id fell outside the mesh."""
+    from .mesh_utils import MeshIntersection, RayIntersector
+    if isinstance(mesh, MeshIntersection):
+        ri, tri_mesh = mesh.rayintersector, mesh.mesh
+    elif isinstance(mesh, TriMesh):
+        ri, tri_mesh = RayIntersector(mesh, max_hits=int(max_hits), device=device, builder=bvh_builder), mesh
+    else:
+        raise TypeError("mesh must be a TriMesh or a MeshIntersection")
+    n_faces = int(tri_mesh.faces.shape[0])
+    mask = torch.zeros((n_faces,), dtype=torch.uint8, device=ri.device)
+    bad = torch.zeros((1,), dtype=torch.int64, device=ri.device)
+    n_views = len(train_dataset.images) if hasattr(train_dataset, "images") else None
+    for j, data in enumerate(train_dataset):
+        if n_views is not None and j == n_views:
+            break
+        rays = data["rays"]
+        hit_tri, _, hit_count, _, _ = ri.hits(rays.origins.reshape(-1, 3), rays.viewdirs.reshape(-1, 3), int(max_hits))
+        mark_hit_faces(hit_tri, hit_count, mask, bad)
+    n_bad = int(bad.item())
+    if n_bad:
+        raise IndexError(f"{n_bad} hit(s) carried a triangle id outside [0, {n_faces})")
+    return tri_mesh, mask
+
+
+def prunning_mesh_train_visibility(mesh, train_dataset, max_hits=5, bvh_builder="host", device="cuda"):
+    """The reference's ``prunning_mesh_train_visibility`` (examples/mc_utils.py:309-345) on the device: ``(mesh, mask)``,
+    the mesh without the faces no training ray hits among its first ``max_hits`` hits, duplicate faces and unreferenced
+    vertices removed (``compact_mesh``), and the numpy bool [F] visibility mask over the input's faces."""
+    tri_mesh, mask = train_visibility_mask(mesh, train_dataset, max_hits, bvh_builder, device)
+    cleaned = compact_mesh(tri_mesh, mask, remove_duplicates=True, remove_unreferenced=True)[0]
+    return cleaned, mask.cpu().numpy().astype(bool)
+
+
+def prunning_mesh_train_visibility_complement(mesh, train_dataset, max_hits=5, bvh_builder="host", device="cuda"):
+    """The reference's ``prunning_mesh_train_visibility_complement`` (examples/mc_utils.py:272-306): ``(mesh, mesh_c,
+    mask)``, the visible and the invisible half of the faces, both with every vertex kept and nothing else cleaned, as
+    the reference's ``update_faces`` leaves them."""
+    tri_mesh, mask = train_visibility_mask(mesh, train_dataset, max_hits, bvh_builder, device)
+    m = mask.cpu().numpy().astype(bool)
+    uv = tri_mesh.visual.uv
+    return (TriMesh(tri_mesh.vertices.copy(), tri_mesh.faces[m], uv), TriMesh(tri_mesh.vertices.copy(), tri_mesh.faces[~m], uv),
+            m)

@@ -20,18 +20,28 @@ from .radiance_fields.ngp import NGPRadianceField, NGPRadianceFieldSGNew
 from .render import FrameRenderer
 
 FILES = ("triangle_weights.npy", "mesh_updated.ply", "num_samples.npy", "num_valid_samples.npy")
+MAP_FILES = ("face_map.npy", "vertex_map.npy")           # written beside FILES with ``compact``
 
 
 def write_pruning_files(out_dir: str, mesh: TriMesh, triangle_weights, num_samples, num_valid_samples,
-                        threshold: float = 1e-3) -> TriMesh:
+                        threshold: float = 1e-3, compact: bool = False, min_component_faces: int = 0) -> TriMesh:
     """The stage's four files (``FILES``) in ``out_dir``: the float32 maxima [F], the pruned mesh (vertices kept), the
-    per-view int64 counts [n_views].  Returns the pruned mesh."""
+    per-view int64 counts [n_views].  With ``compact`` the mesh written is the cleaned one (``baking.prune_faces``) and
+    ``MAP_FILES`` are written beside the four: the source face / vertex of its rows; the three per-face and per-view
+    arrays still describe the original mesh.  Returns the pruned mesh."""
     tw = triangle_weights.detach().cpu().numpy() if isinstance(triangle_weights, torch.Tensor) else np.asarray(triangle_weights)
     tw = np.ascontiguousarray(tw, dtype=np.float32).reshape(-1)
     if tw.shape[0] != mesh.faces.shape[0]:
         raise ValueError(f"{tw.shape[0]} triangle weights for {mesh.faces.shape[0]} faces")
-    pruned = baking.prune_faces(mesh, tw, threshold)
+    if compact:
+        pruned, face_map, vertex_map = baking.prune_faces(mesh, tw, threshold, compact=True,
+                                                          min_component_faces=min_component_faces, return_maps=True)
+    else:
+        pruned = baking.prune_faces(mesh, tw, threshold)
     os.makedirs(out_dir, exist_ok=True)
+    if compact:
+        np.save(os.path.join(out_dir, MAP_FILES[0]), face_map)
+        np.save(os.path.join(out_dir, MAP_FILES[1]), vertex_map)
     np.save(os.path.join(out_dir, FILES[0]), tw)
     pruned.export(os.path.join(out_dir, FILES[1]))
     np.save(os.path.join(out_dir, FILES[2]), np.asarray(num_samples, dtype=np.int64).reshape(-1))
@@ -150,13 +160,16 @@ class MeshPruner:
         """Device bool [F]: ``triangle_weights > threshold``."""
         return self.triangle_weights > self.threshold
 
-    def pruned_mesh(self) -> TriMesh:
+    def pruned_mesh(self, compact: bool = False, min_component_faces: int = 0) -> TriMesh:
         """The mesh with the masked-out faces removed, face order preserved; vertices (and per-vertex UVs) kept as they
-        are, as ``trimesh.update_faces`` leaves them."""
-        return baking.prune_faces(self.mesh_intersect.mesh, self.keep_mask())
+        are, as ``trimesh.update_faces`` leaves them.  ``compact``: the vertices no kept face uses are removed too, and
+        with ``min_component_faces`` >= 2 the small islands (``baking.prune_faces``)."""
+        return baking.prune_faces(self.mesh_intersect.mesh, self.keep_mask(), compact=compact,
+                                  min_component_faces=min_component_faces)
 
-    def save(self, out_dir: str) -> TriMesh:
-        """Write the reference's four files into ``out_dir``; returns the pruned mesh."""
+    def save(self, out_dir: str, compact: bool = False, min_component_faces: int = 0) -> TriMesh:
+        """Write the reference's four files into ``out_dir`` (with ``compact`` the cleaned mesh and its two maps,
+        ``write_pruning_files``); returns the pruned mesh."""
         num_samples, num_valid = self.sample_counts()
         return write_pruning_files(out_dir, self.mesh_intersect.mesh, self.triangle_weights, num_samples, num_valid,
-                                   self.threshold)
+                                   self.threshold, compact=compact, min_component_faces=min_component_faces)
