@@ -275,6 +275,21 @@ _MESH_COMPACT_SIGNATURES = {
     "qf_mark_hit_faces": (c_int, [_P, _P, c_int64, c_int32, c_int64, _P, _P, _P]),
 }
 
+# include/qf_mesh_subdivide.h: the edges of a mesh and the conforming midpoint split, additive in
+# the same way
+MESH_EDGES_COUNTS = ("edges", "degenerate_faces", "invalid_faces", "boundary_edges")
+MESH_SUBDIVIDE_COUNTS = ("faces", "vertices", "faces_0_marked", "faces_1_marked", "faces_2_marked", "faces_3_marked",
+                         "invalid_faces")
+_MESH_SUBDIVIDE_SIGNATURES = {
+    "qf_mesh_edges_workspace_bytes": (c_int64, [c_int64, c_int64]),
+    "qf_mesh_edges_count": (c_int, [_P, c_int64, c_int64, _P, c_int64, _P, _P]),
+    "qf_mesh_edges_emit": (c_int, [_P, c_int64, c_int64, _P, c_int64, _P, c_int64, _P, _P]),
+    "qf_mesh_subdivide_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64]),
+    "qf_mesh_subdivide_count": (c_int, [_P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, _P, _P]),
+    "qf_mesh_subdivide_emit": (c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, _P, c_int64, _P, c_int64, _P,
+                                       _P, _P]),
+}
+
 
 def vertex_row_stride(n_lobes: int) -> int:
     """Floats per row of a vertex table: the width 3 + 7L + 1 rounded up to a 64-byte line (16 / 32 / 48 / 64 for
@@ -295,7 +310,8 @@ def lib() -> ctypes.CDLL:
         handle = ctypes.CDLL(LIB_PATH)
         for name, (restype, argtypes) in (list(_SIGNATURES.items()) + list(_VERTEX_BAKED_SIGNATURES.items())
                                           + list(_VERTEX_TRAIN_SIGNATURES.items()) + list(_VERTEX_QUANT_SIGNATURES.items())
-                                          + list(_MESH_COMPACT_SIGNATURES.items())):
+                                          + list(_MESH_COMPACT_SIGNATURES.items())
+                                          + list(_MESH_SUBDIVIDE_SIGNATURES.items())):
             fn = getattr(handle, name)   # AttributeError if the symbol is not exported
             fn.restype = restype
             fn.argtypes = argtypes

@@ -17,9 +17,13 @@
   3.5f).
 * ``triangle_max_weights`` / ``prune_faces``: ``examples/prune_mesh_after_finetuning.py:323-373`` -- per-triangle
   maximum compositing weight over the training views, faces below 1e-3 dropped.
+* ``subdivide_vertex_features`` / ``vertex_edge_error`` / ``refine_vertex_baked``: the vertex table carried through a
+  midpoint split of the mesh, the per-edge error of the table against the field, and the loop that splits the mesh where
+  that error is above a tolerance.
 """
 import ctypes
 import math
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -485,3 +489,177 @@ def remap_vertex_features(vertex_features, vertex_map):
     if isinstance(vertex_features, VertexBakedFeatures):
         return VertexBakedFeatures(vertex_features.features()[idx], train_density=vertex_features.train_density)
     return table[idx]
+
+
+# ---- refining the vertex-baked asset -------------------------------------------------------------
+
+RefinedVertexBaked = namedtuple("RefinedVertexBaked", ["mesh", "table", "face_map", "vertex_parents", "levels"])
+AXIS_DIRECTIONS = ((1.0, 0.0, 0.0), (-1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, -1.0, 0.0), (0.0, 0.0, 1.0), (0.0, 0.0, -1.0))
+
+
+@torch.no_grad()
+def _field_features(radiance_field, positions: torch.Tensor, batch_size: int = 1000000) -> torch.Tensor:
+    """``radiance_field.features`` at float32 positions, in the chunks of ``bake_vertex_features``."""
+    from .radiance_fields.ngp import NGPRadianceFieldSGNew
+    if not isinstance(radiance_field, NGPRadianceFieldSGNew):
+        raise NotImplementedError("the vertex table holds the SG features of an NGPRadianceFieldSGNew")
+    x = _C.f32c(positions)
+    out = torch.empty((x.shape[0], 3 + 7 * radiance_field.num_g_lobes + 1), dtype=torch.float32, device=x.device)
+    for b in range(0, x.shape[0], int(batch_size)):
+        out[b:b + batch_size] = radiance_field.features(x[b:b + batch_size])
+    return out
+
+
+@torch.no_grad()
+def subdivide_vertex_features(vertex_features, vertex_parents, radiance_field=None, vertices=None):
+    """The per-vertex table of a refined mesh (``mc_utils.subdivide_mesh_device`` / ``subdivide_mesh``): the old rows
+    copied bit for bit, one new row per row ``vertex_parents`` (int64 [V',2], array or tensor) adds.  Without a field a
+    new row is ``(row[a] + row[b]) * 0.5`` in fp32 over its two parents -- the function the renderer interpolates is then
+    what it was, which is how a fine-tuned ``VertexBakedFeatures`` is carried along; parents that are themselves new rows
+    (maps chained over several levels) are resolved level by level.  With ``radiance_field`` a new row is the field's own
+    ``features`` at the new vertex, float32 of ``vertices`` (the refined mesh's, [V',3], required then).  A tensor [V, W]
+    comes back as a tensor [V', W], a ``VertexBakedFeatures`` as a new module (same lobes, same ``train_density``, same
+    device).  Device-agnostic without a field.  A ``QuantisedVertexFeatures`` is refused with ``TypeError``: its records
+    sit in a vertex texture laid out by V, so quantise after refining."""
+    if isinstance(vertex_features, QuantisedVertexFeatures):
+        raise TypeError("subdivide_vertex_features: a QuantisedVertexFeatures cannot be refined (its vertex texture is laid "
+                        "out by V); refine the fp32 table and quantise after refining")
+    module = vertex_features if isinstance(vertex_features, VertexBakedFeatures) else None
+    table = module.features() if module is not None else vertex_features
+    if not isinstance(table, torch.Tensor) or table.dim() != 2 or not table.is_floating_point():
+        raise TypeError("vertex_features must be a floating-point [V, W] tensor or a VertexBakedFeatures")
+    par = torch.as_tensor(np.asarray(vertex_parents) if not isinstance(vertex_parents, torch.Tensor) else vertex_parents)
+    if par.dim() != 2 or par.shape[1] != 2 or par.dtype not in (torch.int64, torch.int32):
+        raise ValueError(f"vertex_parents must be an int64 [V',2] array, got {par.dtype} {tuple(par.shape)}")
+    par = par.to(device=table.device, dtype=torch.int64)
+    n_old, n_new = table.shape[0], par.shape[0]
+    if n_new < n_old:
+        raise ValueError(f"vertex_parents has {n_new} rows for a table of {n_old}")
+    own = torch.arange(n_old, device=table.device)
+    if not bool(((par[:n_old, 0] == own) & (par[:n_old, 1] == own)).all()):
+        raise ValueError(f"the first {n_old} rows of vertex_parents must be (v, v): the vertices the table already has")
+    if n_new > n_old and (int(par[n_old:].min()) < 0 or int(par[n_old:].max()) >= n_new):
+        raise IndexError(f"vertex_parents reaches outside its own {n_new} rows")
+    out = torch.empty((n_new, table.shape[1]), dtype=table.dtype, device=table.device)
+    out[:n_old] = table
+    if radiance_field is not None:
+        if vertices is None or tuple(vertices.shape) != (n_new, 3):
+            raise ValueError(f"with a field, vertices must be the refined mesh's [{n_new}, 3] positions")
+        if table.dtype != torch.float32:
+            raise TypeError(f"with a field the table must be float32, got {table.dtype}")
+        pos = torch.as_tensor(vertices)[n_old:].to(device=table.device, dtype=torch.float32)
+        feats = _field_features(radiance_field, pos)
+        if feats.shape[1] != table.shape[1]:
+            raise ValueError(f"the field has {feats.shape[1]} features per point, the table {table.shape[1]} columns")
+        out[n_old:] = feats
+    else:
+        start = n_old
+        while start < n_new:                    # one level per pass: its rows' parents all lie below `start`
+            ready = (par[start:].max(dim=1).values < start).to(torch.int64)
+            n_level = int(torch.cumprod(ready, dim=0).sum())
+            if n_level == 0:
+                raise ValueError(f"vertex_parents row {start} names a vertex that is not above it: not a chain of levels")
+            a, b = par[start:start + n_level, 0], par[start:start + n_level, 1]
+            out[start:start + n_level] = (out[a] + out[b]) * 0.5
+            start += n_level
+    if module is not None:
+        return VertexBakedFeatures(out, train_density=module.train_density)
+    return out
+
+
+@torch.no_grad()
+def vertex_edge_error(radiance_field, vertices, edges, table, render_step_size: float, dirs=None,
+                      return_midpoint_features: bool = False):
+    """How far the vertex table is from the field at the midpoint of every edge, in the units of a composited pixel:
+    float32 [E] on the device.  With ``f_m`` the field's features at the midpoint ``0.5 * (p[a] + p[b])`` (in the
+    vertices' precision, then float32: the position a split would create) and ``f_i = (table[a] + table[b]) * 0.5`` (what
+    the renderer interpolates there), ``alpha(f) = 1 - exp(-sigma(f) * render_step_size)`` and
+
+        e = max(|alpha(f_m) - alpha(f_i)|,  max(alpha(f_m), alpha(f_i)) * max_d max_c |rgb(f_m, d) - rgb(f_i, d)|_c),
+
+    ``d`` over ``dirs`` ([D,3] unit vectors; the six axis directions by default).  Built from ``radiance_field.features``
+    and ``features_to_rgb``.  ``return_midpoint_features``: also ``f_m`` [E, W], which is the new row of every edge a
+    refinement splits."""
+    v = torch.as_tensor(vertices)
+    e = torch.as_tensor(edges)
+    if v.dim() != 2 or v.shape[1] != 3 or e.dim() != 2 or e.shape[1] != 2:
+        raise ValueError(f"vertices must be [V,3] and edges [E,2], got {tuple(v.shape)} and {tuple(e.shape)}")
+    t = table.features() if isinstance(table, VertexBakedFeatures) else table
+    if t.shape[0] != v.shape[0]:
+        raise ValueError(f"the table has {t.shape[0]} rows for {v.shape[0]} vertices")
+    dev = t.device
+    v, e = v.to(dev), e.to(device=dev, dtype=torch.int64)
+    a, b = e[:, 0], e[:, 1]
+    mid = (0.5 * (v[a] + v[b])).to(torch.float32)
+    f_m = _field_features(radiance_field, mid)
+    f_i = ((t[a] + t[b]) * 0.5).to(torch.float32)
+    step = float(render_step_size)
+    alpha_m = 1.0 - torch.exp(-f_m[:, -1] * step)
+    alpha_i = 1.0 - torch.exp(-f_i[:, -1] * step)
+    d_all = torch.tensor(AXIS_DIRECTIONS, dtype=torch.float32, device=dev) if dirs is None else _C.f32c(torch.as_tensor(dirs)).to(dev)
+    if d_all.dim() != 2 or d_all.shape[1] != 3 or d_all.shape[0] < 1:
+        raise ValueError(f"dirs must be [D,3] with D >= 1, got {tuple(d_all.shape)}")
+    colour = torch.zeros_like(alpha_m)
+    for d in d_all:
+        dd = d.expand(e.shape[0], 3).contiguous()
+        diff = (radiance_field.features_to_rgb(f_m, dd) - radiance_field.features_to_rgb(f_i, dd)).abs().max(dim=1).values
+        colour = torch.maximum(colour, diff)
+    err = torch.maximum((alpha_m - alpha_i).abs(), torch.maximum(alpha_m, alpha_i) * colour)
+    return (err, f_m) if return_midpoint_features else err
+
+
+@torch.no_grad()
+def refine_vertex_baked(mesh: TriMesh, radiance_field, tol: float, max_levels: int = 3, max_vertices: int = None,
+                        render_step_size: float = 0.005, device="cuda", uniform: bool = False,
+                        keep_level_arrays: bool = False) -> RefinedVertexBaked:
+    """Refine a mesh where its vertex-baked table is too coarse for the field.  Per level: the edges of the current mesh
+    (``mc_utils.mesh_edges_device``), ``vertex_edge_error`` of the current table, the edges with ``e > tol`` marked, the
+    conforming split (``mc_utils.subdivide_mesh_device``).  The table is baked once, on the input mesh; afterwards the
+    field is evaluated at edge midpoints only, and the row of a new vertex is the midpoint's features the error pass
+    already has (the same float32 position, so the same bits as ``bake_vertex_features`` of the refined mesh).  With
+    ``max_vertices`` a level marks at most ``max_vertices - V`` edges, the largest errors first (ties: the lower edge id).
+    Stops after ``max_levels`` levels or at the first level that marks nothing.  ``uniform``: every edge is marked,
+    whatever its error (``tol`` is still reported against).
+
+    Returns ``RefinedVertexBaked(mesh, table, face_map, vertex_parents, levels)``: the refined ``TriMesh`` (fp64
+    vertices; a midpoint split does not move the surface), the float32 [V', W] device table, numpy maps composed over the
+    levels as ``mc_utils.subdivide_mesh`` composes them, and one dict per level (vertices, faces and edges before the
+    split, marked edges, edges above ``tol``, the largest and the mean error; with ``keep_level_arrays`` also the device
+    tensors ``edges``, ``errors`` and ``marks``)."""
+    from . import mc_utils
+    dev = _C.resolve_device(device)
+    v = torch.from_numpy(np.asarray(mesh.vertices, np.float64)).to(dev)
+    f = torch.from_numpy(np.asarray(mesh.faces, np.int64)).to(dev)
+    if max_vertices is not None and int(max_vertices) < v.shape[0]:
+        raise ValueError(f"max_vertices = {max_vertices} is below the mesh's {v.shape[0]} vertices")
+    table = _field_features(radiance_field, v.to(torch.float32))
+    n_f0 = f.shape[0]
+    face_map = torch.arange(n_f0, dtype=torch.int64, device=dev)
+    parents = torch.arange(v.shape[0], dtype=torch.int64, device=dev)[:, None].repeat(1, 2)
+    levels = []
+    for level in range(int(max_levels)):
+        edges, face_edges, _ = mc_utils.mesh_edges_device(f, v.shape[0])
+        err, f_m = vertex_edge_error(radiance_field, v, edges, table, render_step_size, return_midpoint_features=True)
+        above = err > float(tol)
+        mark = torch.ones_like(above) if uniform else above
+        if max_vertices is not None and int(mark.sum()) > int(max_vertices) - v.shape[0]:
+            room = int(max_vertices) - v.shape[0]
+            order = torch.sort(torch.where(mark, err, torch.full_like(err, -1.0)), descending=True, stable=True).indices
+            mark = torch.zeros_like(mark)
+            mark[order[:room]] = True
+        n_mark = int(mark.sum())
+        record = dict(level=level, vertices=v.shape[0], faces=f.shape[0], edges=edges.shape[0], marked=n_mark,
+                      above_tol=int(above.sum()), max_error=float(err.max()) if err.numel() else 0.0,
+                      mean_error=float(err.mean()) if err.numel() else 0.0)
+        if keep_level_arrays:
+            record.update(edges_tensor=edges, errors=err, marks=mark)
+        levels.append(record)
+        if n_mark == 0:
+            break
+        out = mc_utils.subdivide_mesh_device(v, f, mark, edges, face_edges)
+        table = torch.cat([table, f_m[mark]])
+        v, f = out.vertices, out.faces
+        face_map = face_map[out.face_map]
+        parents = mc_utils.chain_vertex_parents(parents, out.vertex_parents)
+    refined = TriMesh(v.cpu().numpy(), f.cpu().numpy(), None)
+    return RefinedVertexBaked(refined, table, face_map.cpu().numpy(), parents.cpu().numpy(), levels)

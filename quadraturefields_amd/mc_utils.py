@@ -9,6 +9,8 @@ density.  Here the marching cubes is the HIP kernel of ``csrc/marching_cubes.hip
 unreferenced vertices; ``csrc/mesh_compact.hip``, rules in DESIGN.md section 3.9b), and ``prunning_mesh_train_visibility``
 / ``prunning_mesh_train_visibility_complement`` are the reference's visibility pruning (examples/mc_utils.py:272-345) on
 top of them.
+``mesh_edges_device`` / ``subdivide_mesh_device`` / ``subdivide_mesh`` number a mesh's edges and split its faces at the
+midpoints of any marked subset of them, conformingly (``csrc/mesh_subdivide.hip``, rules in DESIGN.md section 3.9c).
 """
 import math
 from collections import namedtuple
@@ -453,3 +455,179 @@ def prunning_mesh_train_visibility_complement(mesh, train_dataset, max_hits=5, b
     uv = tri_mesh.visual.uv
     return (TriMesh(tri_mesh.vertices.copy(), tri_mesh.faces[m], uv), TriMesh(tri_mesh.vertices.copy(), tri_mesh.faces[~m], uv),
             m)
+
+
+# ---- mesh refinement (include/qf_mesh_subdivide.h) -----------------------------------------------
+
+MeshEdges = namedtuple("MeshEdges", ["edges", "face_edges", "stats"])
+SubdividedMesh = namedtuple("SubdividedMesh", ["vertices", "faces", "face_map", "vertex_parents", "stats"])
+
+
+def _device_faces(faces, what: str) -> torch.Tensor:
+    if not isinstance(faces, torch.Tensor):
+        raise TypeError("faces must be a torch.Tensor")
+    if faces.ndim != 2 or faces.shape[1] != 3:
+        raise ValueError(f"faces must be [F,3], got {tuple(faces.shape)}")
+    if faces.dtype not in (torch.int64, torch.int32):
+        raise TypeError(f"faces must be int64 or int32, got {faces.dtype}")
+    if not faces.is_cuda:
+        raise ValueError(f"{what} needs device tensors (quadraturefields_amd has no CPU fallback)")
+    return faces.to(torch.int64).contiguous()
+
+
+def mesh_edges_device(faces: torch.Tensor, n_vertices: int) -> MeshEdges:
+    """The undirected edges of a mesh, numbered on the device in the order of their first appearance (stage A of DESIGN.md
+    section 3.9c).  ``faces``: device int64 or int32 [F,3] over ``n_vertices`` vertices.  Returns ``MeshEdges(edges int64
+    [E,2] as (min, max), face_edges int64 [F,3], stats)``: ``face_edges[f, k]`` is the edge between corners k and k + 1 of
+    face f, -1 on a degenerate face (two equal indices), which contributes no edge; ``stats`` is a dict of the four
+    counts (``_C.MESH_EDGES_COUNTS``).  One host wait, for the counts.  Raises ValueError for host tensors, bad shapes
+    and, with their number, faces that index outside [0, n_vertices)."""
+    f = _device_faces(faces, "mesh_edges_device")
+    n_v, n_f = int(n_vertices), f.shape[0]
+    if n_v != n_vertices or n_v < 0 or n_v >= 2 ** 31 or 3 * n_f >= 2 ** 31:
+        raise ValueError(f"the mesh has {n_vertices} vertices and {n_f} faces; V and 3 F must be < 2^31")
+    dev = f.device
+    if n_v == 0:
+        if n_f:
+            raise ValueError(f"{n_f} faces have an index outside [0, 0)")
+        return MeshEdges(torch.empty((0, 2), dtype=torch.int64, device=dev), torch.empty((0, 3), dtype=torch.int64, device=dev),
+                         dict.fromkeys(_C.MESH_EDGES_COUNTS, 0))
+    lib = _C.lib()
+    with torch.cuda.device(dev):
+        ws_bytes = int(lib.qf_mesh_edges_workspace_bytes(n_v, n_f))
+        if ws_bytes < 0:
+            raise RuntimeError(f"qf_mesh_edges_workspace_bytes refused V={n_v}, F={n_f}")
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+        counts = torch.empty((len(_C.MESH_EDGES_COUNTS),), dtype=torch.int64, device=dev)
+        _C.check(lib.qf_mesh_edges_count(_C.ptr(f), n_f, n_v, _C.ptr(ws), ws_bytes, _C.ptr(counts), _C.stream()),
+                 "qf_mesh_edges_count")
+        stats = dict(zip(_C.MESH_EDGES_COUNTS, counts.tolist()))
+        if stats["invalid_faces"]:
+            raise ValueError(f"{stats['invalid_faces']} faces have an index outside [0, {n_v})")
+        edges = torch.empty((stats["edges"], 2), dtype=torch.int64, device=dev)
+        face_edges = torch.empty((n_f, 3), dtype=torch.int64, device=dev)
+        _C.check(lib.qf_mesh_edges_emit(_C.ptr(f), n_f, n_v, _C.ptr(ws), ws_bytes, _C.ptr(edges), edges.shape[0],
+                                        _C.ptr(face_edges), _C.stream()), "qf_mesh_edges_emit")
+    return MeshEdges(edges, face_edges, stats)
+
+
+def _device_marks(edge_mark, n_edges: int, device) -> torch.Tensor:
+    """Edge marks (tensor or array, bool or integer; None marks every edge) as a contiguous device uint8 [E]."""
+    if edge_mark is None:
+        return torch.ones((n_edges,), dtype=torch.uint8, device=device)
+    k = edge_mark if isinstance(edge_mark, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(edge_mark))
+    k = k.reshape(-1)
+    if k.shape[0] != n_edges:
+        raise ValueError(f"{k.shape[0]} edge marks for {n_edges} edges")
+    if k.is_floating_point() or k.is_complex():
+        raise TypeError(f"edge_mark must be a bool or integer mask, got {k.dtype}")
+    k = k.to(device)
+    return (k if k.dtype == torch.uint8 else (k != 0).to(torch.uint8)).contiguous()
+
+
+def subdivide_mesh_device(vertices: torch.Tensor, faces: torch.Tensor, edge_mark=None, edges: torch.Tensor = None,
+                          face_edges: torch.Tensor = None) -> SubdividedMesh:
+    """Split the faces of a mesh at the midpoints of its marked edges, on the device, under the rules of DESIGN.md section
+    3.9c: a marked edge ``e`` gets vertex ``V + (marked edges with a smaller id)`` at ``0.5 * (p[min] + p[max])`` in fp64;
+    a face becomes 1, 2, 3 or 4 children by its number of marked edges, consecutive, with the parent's winding; every
+    face that uses a marked edge is split at the same vertex, so the result has no T-junction whatever the marks are.
+    ``vertices``: device float [V,3] (fp32 is widened exactly), ``faces``: device int64 or int32 [F,3], ``edge_mark``:
+    bool / integer [E] over the edges of ``mesh_edges_device`` (None marks every edge), ``edges`` / ``face_edges``: that
+    function's result when the caller already has it (both or neither).  Returns ``SubdividedMesh(vertices fp64 [V',3],
+    faces int64 [F',3], face_map int64 [F'], vertex_parents int64 [V',2], stats)``: ``face_map`` names every child's
+    parent, ``vertex_parents`` is (min, max) of the split edge for a new vertex and (v, v) for an old one, and the first
+    V rows of the vertices are the input's, bit for bit; ``stats`` is a dict of the seven counts
+    (``_C.MESH_SUBDIVIDE_COUNTS``).  One host wait per stage, for the counts."""
+    if not isinstance(vertices, torch.Tensor):
+        raise TypeError("vertices and faces must be torch.Tensors")
+    f = _device_faces(faces, "subdivide_mesh_device")
+    if vertices.ndim != 2 or vertices.shape[1] != 3:
+        raise ValueError(f"vertices must be [V,3], got {tuple(vertices.shape)}")
+    if not vertices.is_floating_point():
+        raise TypeError(f"vertices must be floating point, got {vertices.dtype}")
+    if not vertices.is_cuda:
+        raise ValueError("subdivide_mesh_device needs device tensors (quadraturefields_amd has no CPU fallback)")
+    if vertices.device != f.device:
+        raise ValueError(f"vertices on {vertices.device} and faces on {f.device}")
+    if (edges is None) != (face_edges is None):
+        raise ValueError("pass both edges and face_edges (mesh_edges_device's) or neither")
+    n_v, n_f = vertices.shape[0], f.shape[0]
+    dev = vertices.device
+    if edges is None:
+        edges, face_edges, _ = mesh_edges_device(f, n_v)
+    else:
+        if edges.ndim != 2 or edges.shape[1] != 2 or tuple(face_edges.shape) != (n_f, 3):
+            raise ValueError(f"edges must be [E,2] and face_edges [F,3], got {tuple(edges.shape)} and {tuple(face_edges.shape)}")
+        if edges.device != dev or face_edges.device != dev or face_edges.dtype != torch.int64:
+            raise ValueError("edges and face_edges must be mesh_edges_device's int64 tensors on the vertices' device")
+        face_edges = face_edges.contiguous()
+    n_e = edges.shape[0]
+    mark = _device_marks(edge_mark, n_e, dev)
+    if n_f >= 2 ** 29 or n_v + n_e >= 2 ** 31:
+        raise ValueError(f"the mesh has {n_v} vertices, {n_e} edges and {n_f} faces; V + E must be < 2^31 and F < 2^29")
+    v = vertices.to(torch.float64).contiguous()
+    if n_v == 0:
+        empty = torch.empty((0,), dtype=torch.int64, device=dev)
+        return SubdividedMesh(v, empty.reshape(0, 3), empty, empty.reshape(0, 2), dict.fromkeys(_C.MESH_SUBDIVIDE_COUNTS, 0))
+    lib = _C.lib()
+    with torch.cuda.device(dev):
+        ws_bytes = int(lib.qf_mesh_subdivide_workspace_bytes(n_v, n_f, n_e))
+        if ws_bytes < 0:
+            raise RuntimeError(f"qf_mesh_subdivide_workspace_bytes refused V={n_v}, F={n_f}, E={n_e}")
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+        counts = torch.empty((len(_C.MESH_SUBDIVIDE_COUNTS),), dtype=torch.int64, device=dev)
+        args = (_C.ptr(f), n_f, n_v, _C.ptr(face_edges), n_e, _C.ptr(mark), _C.ptr(ws), ws_bytes)
+        _C.check(lib.qf_mesh_subdivide_count(*args, _C.ptr(counts), _C.stream()), "qf_mesh_subdivide_count")
+        stats = dict(zip(_C.MESH_SUBDIVIDE_COUNTS, counts.tolist()))
+        if stats["invalid_faces"]:
+            raise ValueError(f"{stats['invalid_faces']} faces have a vertex index outside [0, {n_v}) or an edge id outside "
+                             f"[0, {n_e})")
+        out_v = torch.empty((stats["vertices"], 3), dtype=torch.float64, device=dev)
+        out_f = torch.empty((stats["faces"], 3), dtype=torch.int64, device=dev)
+        face_map = torch.empty((stats["faces"],), dtype=torch.int64, device=dev)
+        parents = torch.empty((stats["vertices"], 2), dtype=torch.int64, device=dev)
+        _C.check(lib.qf_mesh_subdivide_emit(_C.ptr(v), *args, _C.ptr(out_v), out_v.shape[0], _C.ptr(out_f), out_f.shape[0],
+                                            _C.ptr(face_map), _C.ptr(parents), _C.stream()), "qf_mesh_subdivide_emit")
+    return SubdividedMesh(out_v, out_f, face_map, parents, stats)
+
+
+def chain_vertex_parents(before: torch.Tensor, level: torch.Tensor) -> torch.Tensor:
+    """``vertex_parents`` over several levels: a level's rows name vertices of its own input, whose indices the levels
+    before it left as they were, so the rows each level adds are appended.  Row v then names two vertices of smaller index,
+    or (v, v) for a vertex of the first input."""
+    return torch.cat([before, level[before.shape[0]:]])
+
+
+def subdivide_mesh(mesh: TriMesh, edge_mark=None, levels: int = 1, device="cuda"):
+    """``subdivide_mesh_device`` on a ``TriMesh``, ``levels`` times: ``(TriMesh, face_map, vertex_parents)`` with numpy
+    int64 maps composed over the levels -- ``face_map[child]`` is the face of the INPUT mesh the child lies in, and
+    ``vertex_parents[v]`` names two vertices of smaller index (the ends of the edge v split, at the level that made it), or
+    (v, v) for a vertex of the input, so every chain ends at input vertices.  ``edge_mark`` (over the edges of
+    ``mesh_edges_device``, None = every edge) applies to the first level; further levels split every edge.  Per-vertex
+    ``visual.uv`` is carried along by the same midpoint rule."""
+    levels = int(levels)
+    if levels < 1:
+        raise ValueError(f"levels must be >= 1, got {levels}")
+    dev = edge_mark.device if isinstance(edge_mark, torch.Tensor) and edge_mark.is_cuda else _C.resolve_device(device)
+    v = torch.from_numpy(np.asarray(mesh.vertices, np.float64)).to(dev)
+    f = torch.from_numpy(np.asarray(mesh.faces, np.int64)).to(dev)
+    uv = None if mesh.visual.uv is None else np.asarray(mesh.visual.uv, np.float64)
+    face_map, parents = None, None
+    for level in range(levels):
+        out = subdivide_mesh_device(v, f, edge_mark if level == 0 else None)
+        if uv is not None:
+            added = out.vertex_parents[v.shape[0]:].cpu().numpy()
+            uv = np.concatenate([uv, 0.5 * (uv[added[:, 0]] + uv[added[:, 1]])])
+        v, f = out.vertices, out.faces
+        face_map = out.face_map if face_map is None else face_map[out.face_map]
+        parents = out.vertex_parents if parents is None else chain_vertex_parents(parents, out.vertex_parents)
+    return TriMesh(v.cpu().numpy(), f.cpu().numpy(), uv), face_map.cpu().numpy(), parents.cpu().numpy()
+
+
+def mark_edges_longer_than(vertices: torch.Tensor, edges: torch.Tensor, length: float) -> torch.Tensor:
+    """uint8 [E]: 1 where the edge ``(a, b)`` of ``edges`` (int64 [E,2]) is longer than ``length`` in the vertices'
+    precision; torch ops on the tensors' device."""
+    if vertices.ndim != 2 or vertices.shape[1] != 3 or edges.ndim != 2 or edges.shape[1] != 2:
+        raise ValueError(f"vertices must be [V,3] and edges [E,2], got {tuple(vertices.shape)} and {tuple(edges.shape)}")
+    d = vertices[edges[:, 0]] - vertices[edges[:, 1]]
+    return ((d * d).sum(dim=1) > float(length) ** 2).to(torch.uint8)
