@@ -1,0 +1,49 @@
+"""Decimate a mesh to a face count on the GPU (rounds of independent quadric edge collapses; the
+rules are this project's own, parity with the reference's fast_simplification is unpinned).
+
+    python examples/decimate_mesh.py IN.ply OUT.ply (--target_faces N | --ratio R) [--max_cost C] [--max_rounds K]
+
+Writes OUT.ply and, beside it, ``face_map.npy`` (the source face of every output face) and ``vertex_target.npy`` (the
+output vertex every input vertex ended in, -1 if it was dropped), and prints the stats as one JSON line.  Boundary and
+non-manifold edges are never collapsed, so a mesh made of them is returned as it is."""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("mesh_in")
+    ap.add_argument("mesh_out")
+    goal = ap.add_mutually_exclusive_group(required=True)
+    goal.add_argument("--target_faces", type=int)
+    goal.add_argument("--ratio", type=float, help="target = floor(ratio * F)")
+    ap.add_argument("--max_cost", type=float, default=None)
+    ap.add_argument("--max_rounds", type=int, default=128)
+    ap.add_argument("--device", default="cuda")
+    args = ap.parse_args(argv)
+    from quadraturefields_amd import mc_utils
+    from quadraturefields_amd.mesh_io import load_mesh
+    mesh = load_mesh(args.mesh_in)
+    n_f = mesh.faces.shape[0]
+    if args.ratio is not None and not 0.0 <= args.ratio <= 1.0:
+        ap.error("--ratio must lie in [0, 1]")
+    target = args.target_faces if args.target_faces is not None else int(args.ratio * n_f)
+    out, face_map, vertex_target, stats = mc_utils.decimate_mesh(mesh, target, max_cost=args.max_cost,
+                                                                 max_rounds=args.max_rounds, return_stats=True,
+                                                                 device=args.device)
+    out.export(args.mesh_out)
+    folder = os.path.dirname(os.path.abspath(args.mesh_out))
+    np.save(os.path.join(folder, "face_map.npy"), face_map)
+    np.save(os.path.join(folder, "vertex_target.npy"), vertex_target)
+    print(json.dumps(dict(stats, faces_in=n_f, vertices_in=int(mesh.vertices.shape[0]), target_faces=target,
+                          faces_out=int(out.faces.shape[0]), vertices_out=int(out.vertices.shape[0]))))
+
+
+if __name__ == "__main__":
+    main()

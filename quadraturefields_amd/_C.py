@@ -290,6 +290,20 @@ _MESH_SUBDIVIDE_SIGNATURES = {
                                        _P, _P]),
 }
 
+# include/qf_mesh_decimate.h: rounds of independent quadric edge collapses, additive in the same
+# way
+MESH_QUADRIC_COUNTS = ("nonfinite_vertices", "invalid_faces")
+MESH_COLLAPSE_COUNTS = ("candidates", "legal", "selected", "taken", "locked_vertices", "invalid")
+_MESH_DECIMATE_SIGNATURES = {
+    "qf_mesh_decimate_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64]),
+    "qf_mesh_vertex_quadrics": (c_int, [_P, c_int64, _P, c_int64, _P, _P, c_int64, _P, _P]),
+    "qf_mesh_collapse_select": (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, _P, _P, _P, c_double, c_int64, c_int64, _P,
+                                        c_int64, _P, _P]),
+    "qf_mesh_collapse_apply": (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P]),
+    "qf_mesh_collapse_gather": (c_int, [_P, _P, _P, c_int64, c_int64, _P, c_int64, _P, c_int64, _P, _P, _P, _P, c_int64, _P,
+                                        c_int64, _P]),
+}
+
 
 def vertex_row_stride(n_lobes: int) -> int:
     """Floats per row of a vertex table: the width 3 + 7L + 1 rounded up to a 64-byte line (16 / 32 / 48 / 64 for
@@ -311,7 +325,8 @@ def lib() -> ctypes.CDLL:
         for name, (restype, argtypes) in (list(_SIGNATURES.items()) + list(_VERTEX_BAKED_SIGNATURES.items())
                                           + list(_VERTEX_TRAIN_SIGNATURES.items()) + list(_VERTEX_QUANT_SIGNATURES.items())
                                           + list(_MESH_COMPACT_SIGNATURES.items())
-                                          + list(_MESH_SUBDIVIDE_SIGNATURES.items())):
+                                          + list(_MESH_SUBDIVIDE_SIGNATURES.items())
+                                          + list(_MESH_DECIMATE_SIGNATURES.items())):
             fn = getattr(handle, name)   # AttributeError if the symbol is not exported
             fn.restype = restype
             fn.argtypes = argtypes

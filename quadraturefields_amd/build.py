@@ -20,7 +20,8 @@ ARCH = "gfx950"
 # texture, baked_frame, vertex_baked, vertex_train, vertex_quant, front_frame, grid_march and volumetric carry every integer-deciding comparison), bake.hip (the fp32 codecs), texel_fill.hip (the fp64 rules of the texel-position
 # map), marching_cubes.hip (the fp32 vertex rule and the fp64 face decider), vertex_clustering.hip (the fp64 cell, mean
 # and quadric rules), mesh_compact.hip (integer rules only; the flag keeps it with its neighbour), mesh_subdivide.hip (the
-# fp64 midpoint is one add and one multiply, never a fused one), uv_atlas.hip (the fp64 measure, class and corner rules) and bvh_build_device.hip (the fp32 Morton
+# fp64 midpoint is one add and one multiply, never a fused one), mesh_decimate.hip (the fp64 quadric, point, cost and
+# side rules), uv_atlas.hip (the fp64 measure, class and corner rules) and bvh_build_device.hip (the fp32 Morton
 # keys of the device BVH build).
 SOURCES = [
     ("field_eval.hip", []),
@@ -51,6 +52,7 @@ SOURCES = [
     ("vertex_clustering.hip", ["-ffp-contract=off"]),
     ("mesh_compact.hip", ["-ffp-contract=off"]),
     ("mesh_subdivide.hip", ["-ffp-contract=off"]),
+    ("mesh_decimate.hip", ["-ffp-contract=off"]),
     ("uv_atlas.hip", ["-ffp-contract=off"]),
     ("bvh_build_device.hip", ["-ffp-contract=off"]),
     ("bvh_build.cpp", ["-x", "hip"]),
@@ -72,7 +74,7 @@ def _deps(src: str):
     deps = [os.path.join(CSRC, src), os.path.join(ROOT, "include", "qf_hip.h"),
             os.path.join(ROOT, "include", "qf_vertex_baked.h"), os.path.join(ROOT, "include", "qf_vertex_train.h"),
             os.path.join(ROOT, "include", "qf_vertex_quant.h"), os.path.join(ROOT, "include", "qf_mesh_compact.h"),
-            os.path.join(ROOT, "include", "qf_mesh_subdivide.h"),
+            os.path.join(ROOT, "include", "qf_mesh_subdivide.h"), os.path.join(ROOT, "include", "qf_mesh_decimate.h"),
             os.path.abspath(__file__)]
     deps += [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     return deps

@@ -1,0 +1,681 @@
+// Mesh decimation: rounds of independent quadric edge collapses (the rules are stated in
+// include/qf_mesh_decimate.h and restated in numpy in tests/mesh_decimate_reference.py).  Per round the caller numbers the
+// edges (mesh_subdivide.hip), calls select and apply here, compacts (mesh_compact.hip) and gathers here.
+//
+// Passes of select (one stream, no host wait):
+//   face keys (v << 32 | f per corner of a face without two equal indices) -> radix sort -> the run of every vertex: the
+//   CSR of faces, rows ascending;  edge keys (a << 32 | b and b << 32 | a) -> radix sort -> runs: the CSR of neighbours,
+//   rows ascending;  uses (integer atomicAdd per half-edge) -> locks -> one thread per edge: point, cost, legality, key,
+//   integer atomicMin into m1 of both ends -> m2 per vertex over its row -> selected edges keyed by their cost bits, the
+//   others by all ones -> stable radix sort of (key, e) -> the first max_take that are not all ones are taken.
+// Every valence loop walks a CSR row; no kernel keeps a per-thread list.  Every floating-point value is computed by one
+// thread in a stated order, so results do not depend on the launch shape; the atomics are integer min, add and flags.
+// The file is compiled with -ffp-contract=off: every product and sum is rounded on its own.
+#pragma clang fp contract(off)
+
+#include <cmath>
+#include <cstring>
+
+#include <rocprim/device/device_radix_sort.hpp>
+
+#include "qf_common.h"
+#include "qf_mesh_decimate.h"
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int64_t kMaxCount = int64_t(1) << 31;
+constexpr uint64_t kNone = ~uint64_t(0);        // above every key: keys fit 63 bits
+constexpr double kTau = 1e-6;
+
+inline int64_t align_up(int64_t x) { return (x + 255) & ~int64_t(255); }
+inline int blocks(int64_t n) { return (int)((n + kBlock - 1) / kBlock); }
+
+struct Info {
+    unsigned long long candidates, legal, selected, locked, invalid, nonfinite;
+};
+
+struct Workspace {
+    Info *info;
+    int64_t *fstart, *fend;     // [V] run of each vertex in fkey_b
+    int64_t *nstart, *nend;     // [V] run of each vertex in nkey_b
+    uint64_t *m1, *m2;          // [V]
+    int32_t *remap;             // [V] the kept end of a removed vertex, else -1
+    uint8_t *locked;            // [V]
+    uint64_t *fkey_a, *fkey_b;  // [3F] vertex << 32 | face, then sorted
+    double *plane;              // [4F] (quadrics only)
+    uint64_t *nkey_a, *nkey_b;  // [2E] vertex << 32 | neighbour, then sorted
+    int32_t *uses;              // [E]
+    uint64_t *key;              // [E] the key of a legal candidate, else kNone
+    uint64_t *skey_a, *skey_b;  // [E] cost bits of a legal candidate, then of a selected edge; sorted
+    int32_t *sval_a, *sval_b;   // [E] edge ids; sorted
+    void *temp;
+    size_t temp_bytes;
+    int64_t bytes;
+};
+
+bool sizes_ok(int64_t V, int64_t F, int64_t E)
+{
+    return V >= 1 && V < kMaxCount && F >= 0 && 3 * F < kMaxCount && E >= 0 && E < kMaxCount;
+}
+
+// rocPRIM scratch for the largest of the three sorts (host query, no launch).
+size_t temp_bytes_for(int64_t F, int64_t E, hipStream_t s)
+{
+    size_t need = 1, b = 0;
+    if (rocprim::radix_sort_keys(nullptr, b, (uint64_t *)nullptr, (uint64_t *)nullptr, (size_t)(3 * F > 0 ? 3 * F : 1), 0, 64,
+                                 s) != hipSuccess)
+        return 0;
+    need = b > need ? b : need;
+    if (rocprim::radix_sort_keys(nullptr, b, (uint64_t *)nullptr, (uint64_t *)nullptr, (size_t)(2 * E > 0 ? 2 * E : 1), 0, 64,
+                                 s) != hipSuccess)
+        return 0;
+    need = b > need ? b : need;
+    if (rocprim::radix_sort_pairs(nullptr, b, (uint64_t *)nullptr, (uint64_t *)nullptr, (int32_t *)nullptr,
+                                  (int32_t *)nullptr, (size_t)(E > 0 ? E : 1), 0, 64, s) != hipSuccess)
+        return 0;
+    need = b > need ? b : need;
+    return need;
+}
+
+Workspace carve(void *base, int64_t V, int64_t F, int64_t E, size_t temp)
+{
+    Workspace w;
+    int64_t off = 0;
+    auto take = [&](int64_t bytes) { char *p = static_cast<char *>(base) + off; off += align_up(bytes); return p; };
+    w.info = reinterpret_cast<Info *>(take(sizeof(Info)));
+    w.fstart = reinterpret_cast<int64_t *>(take(8 * V));
+    w.fend = reinterpret_cast<int64_t *>(take(8 * V));
+    w.nstart = reinterpret_cast<int64_t *>(take(8 * V));
+    w.nend = reinterpret_cast<int64_t *>(take(8 * V));
+    w.m1 = reinterpret_cast<uint64_t *>(take(8 * V));
+    w.m2 = reinterpret_cast<uint64_t *>(take(8 * V));
+    w.remap = reinterpret_cast<int32_t *>(take(4 * V));
+    w.locked = reinterpret_cast<uint8_t *>(take(V));
+    w.fkey_a = reinterpret_cast<uint64_t *>(take(24 * F));
+    w.fkey_b = reinterpret_cast<uint64_t *>(take(24 * F));
+    w.plane = reinterpret_cast<double *>(take(32 * F));
+    w.nkey_a = reinterpret_cast<uint64_t *>(take(16 * E));
+    w.nkey_b = reinterpret_cast<uint64_t *>(take(16 * E));
+    w.uses = reinterpret_cast<int32_t *>(take(4 * E));
+    w.key = reinterpret_cast<uint64_t *>(take(8 * E));
+    w.skey_a = reinterpret_cast<uint64_t *>(take(8 * E));
+    w.skey_b = reinterpret_cast<uint64_t *>(take(8 * E));
+    w.sval_a = reinterpret_cast<int32_t *>(take(4 * E));
+    w.sval_b = reinterpret_cast<int32_t *>(take(4 * E));
+    w.temp = take((int64_t)temp);
+    w.temp_bytes = temp;
+    w.bytes = off;
+    return w;
+}
+
+struct Mesh {
+    const double *p;
+    const int64_t *f;
+    const int64_t *edges;
+    const int64_t *face_edges;
+    const double *Q;
+    int64_t V, F, E;
+};
+
+__device__ __forceinline__ int64_t gtid() { return (int64_t)blockIdx.x * blockDim.x + threadIdx.x; }
+
+__device__ __forceinline__ bool face_ok(const int64_t *t, int64_t V)
+{
+    return t[0] >= 0 && t[0] < V && t[1] >= 0 && t[1] < V && t[2] >= 0 && t[2] < V;
+}
+
+// Corner 3f + k -> vertex << 32 | face for a face with three distinct indices in range, else kNone.
+__global__ __launch_bounds__(kBlock) void face_key_kernel(Mesh M, Workspace ws)
+{
+    const int64_t i = gtid();
+    if (i >= 3 * M.F) return;
+    const int64_t f = i / 3, k = i - 3 * f;
+    const int64_t *t = M.f + 3 * f;
+    uint64_t key = kNone;
+    if (!face_ok(t, M.V)) {
+        if (k == 0) atomicAdd(&ws.info->invalid, 1ull);
+    } else if (t[0] != t[1] && t[1] != t[2] && t[0] != t[2]) {
+        key = (uint64_t)t[k] << 32 | (uint64_t)f;
+    }
+    ws.fkey_a[i] = key;
+}
+
+// The two directed copies of edge e, or kNone for an edge that is not 0 <= a < b < V.
+__global__ __launch_bounds__(kBlock) void edge_key_kernel(Mesh M, Workspace ws)
+{
+    const int64_t e = gtid();
+    if (e >= M.E) return;
+    const int64_t a = M.edges[2 * e], b = M.edges[2 * e + 1];
+    const bool ok = a >= 0 && a < b && b < M.V;
+    if (!ok) atomicAdd(&ws.info->invalid, 1ull);
+    ws.nkey_a[2 * e] = ok ? ((uint64_t)a << 32 | (uint64_t)b) : kNone;
+    ws.nkey_a[2 * e + 1] = ok ? ((uint64_t)b << 32 | (uint64_t)a) : kNone;
+}
+
+// start / end of every vertex's run in sorted keys (rows of vertices without a key stay at the memset's 0, 0).
+__global__ __launch_bounds__(kBlock) void range_kernel(const uint64_t *keys, int64_t n, int64_t *start, int64_t *end)
+{
+    const int64_t j = gtid();
+    if (j >= n) return;
+    const uint64_t key = keys[j];
+    if (key == kNone) return;
+    const uint64_t v = key >> 32;
+    if (j == 0 || (keys[j - 1] >> 32) != v) start[v] = j;
+    if (j == n - 1 || keys[j + 1] == kNone || (keys[j + 1] >> 32) != v) end[v] = j + 1;
+}
+
+__device__ __forceinline__ void cross_of(const double *p0, const double *p1, const double *p2, double &n0, double &n1,
+                                         double &n2)
+{
+    const double u0 = p1[0] - p0[0], u1 = p1[1] - p0[1], u2 = p1[2] - p0[2];
+    const double w0 = p2[0] - p0[0], w1 = p2[1] - p0[1], w2 = p2[2] - p0[2];
+    n0 = u1 * w2 - u2 * w1;
+    n1 = u2 * w0 - u0 * w2;
+    n2 = u0 * w1 - u1 * w0;
+}
+
+__global__ __launch_bounds__(kBlock) void plane_kernel(Mesh M, Workspace ws)
+{
+    const int64_t f = gtid();
+    if (f >= M.F) return;
+    const int64_t *t = M.f + 3 * f;
+    double n0 = 0.0, n1 = 0.0, n2 = 0.0, d = 0.0;
+    if (face_ok(t, M.V)) {
+        const double *a = M.p + 3 * t[0];
+        cross_of(a, M.p + 3 * t[1], M.p + 3 * t[2], n0, n1, n2);
+        const double len = sqrt((n0 * n0 + n1 * n1) + n2 * n2);
+        if (len == 0.0) {
+            n0 = n1 = n2 = 0.0;
+        } else {
+            n0 = n0 / len;
+            n1 = n1 / len;
+            n2 = n2 / len;
+            d = -((n0 * a[0] + n1 * a[1]) + n2 * a[2]);
+        }
+    }
+    double *p = ws.plane + 4 * f;
+    p[0] = n0;
+    p[1] = n1;
+    p[2] = n2;
+    p[3] = d;
+}
+
+__global__ __launch_bounds__(kBlock) void quadric_kernel(Mesh M, Workspace ws, double *out)
+{
+    const int64_t v = gtid();
+    if (v >= M.V) return;
+    const double *x = M.p + 3 * v;
+    if (!(isfinite(x[0]) && isfinite(x[1]) && isfinite(x[2]))) atomicAdd(&ws.info->nonfinite, 1ull);
+    double q0 = 0.0, q1 = 0.0, q2 = 0.0, q3 = 0.0, q4 = 0.0, q5 = 0.0, q6 = 0.0, q7 = 0.0, q8 = 0.0, q9 = 0.0;
+    for (int64_t j = ws.fstart[v], je = ws.fend[v]; j < je; ++j) {
+        const double *p = ws.plane + 4 * (int64_t)(ws.fkey_b[j] & 0xffffffffu);
+        const double p0 = p[0], p1 = p[1], p2 = p[2], p3 = p[3];
+        q0 = q0 + p0 * p0;
+        q1 = q1 + p0 * p1;
+        q2 = q2 + p0 * p2;
+        q3 = q3 + p0 * p3;
+        q4 = q4 + p1 * p1;
+        q5 = q5 + p1 * p2;
+        q6 = q6 + p1 * p3;
+        q7 = q7 + p2 * p2;
+        q8 = q8 + p2 * p3;
+        q9 = q9 + p3 * p3;
+    }
+    double *o = out + 10 * v;
+    o[0] = q0; o[1] = q1; o[2] = q2; o[3] = q3; o[4] = q4;
+    o[5] = q5; o[6] = q6; o[7] = q7; o[8] = q8; o[9] = q9;
+}
+
+__global__ void quadric_counts_kernel(Workspace ws, int64_t *counts)
+{
+    counts[0] = (int64_t)ws.info->nonfinite;
+    counts[1] = (int64_t)ws.info->invalid;
+}
+
+__global__ __launch_bounds__(kBlock) void uses_kernel(Mesh M, Workspace ws)
+{
+    const int64_t i = gtid();
+    if (i >= 3 * M.F) return;
+    const int64_t e = M.face_edges[i];
+    if (e >= 0 && e < M.E) atomicAdd(&ws.uses[e], 1);
+    else if (e != -1) atomicAdd(&ws.info->invalid, 1ull);
+}
+
+__global__ __launch_bounds__(kBlock) void lock_init_kernel(int64_t V, const uint8_t *vertex_lock, Workspace ws)
+{
+    const int64_t v = gtid();
+    if (v >= V) return;
+    ws.locked[v] = (vertex_lock && vertex_lock[v]) ? 1 : 0;
+}
+
+// Both ends of a boundary or non-manifold edge (every writer stores the same 1).
+__global__ __launch_bounds__(kBlock) void lock_edge_kernel(Mesh M, Workspace ws)
+{
+    const int64_t e = gtid();
+    if (e >= M.E || ws.nkey_a[2 * e] == kNone || ws.uses[e] == 2) return;
+    ws.locked[M.edges[2 * e]] = 1;
+    ws.locked[M.edges[2 * e + 1]] = 1;
+}
+
+__global__ __launch_bounds__(kBlock) void lock_count_kernel(int64_t V, Workspace ws)
+{
+    const int64_t v = gtid();
+    if (v < V && ws.locked[v]) atomicAdd(&ws.info->locked, 1ull);
+}
+
+// Step 3: Qe, the point z and the cost of edge (a, b).
+__device__ __forceinline__ void collapse_point(const double *p, const double *Q, int64_t a, int64_t b, double *qe,
+                                               double &z0, double &z1, double &z2, double &cost)
+{
+    const double *qa = Q + 10 * a, *qb = Q + 10 * b;
+#pragma unroll
+    for (int k = 0; k < 10; ++k) qe[k] = qa[k] + qb[k];
+    const double *pa = p + 3 * a, *pb = p + 3 * b;
+    const double pa0 = pa[0], pa1 = pa[1], pa2 = pa[2], pb0 = pb[0], pb1 = pb[1], pb2 = pb[2];
+    const double m0 = (pa0 + pb0) * 0.5, m1 = (pa1 + pb1) * 0.5, m2 = (pa2 + pb2) * 0.5;
+    const double a00 = qe[0], a01 = qe[1], a02 = qe[2], a11 = qe[4], a12 = qe[5], a22 = qe[7];
+    const double b0 = -qe[3], b1 = -qe[6], b2 = -qe[8];
+    const double r0 = b0 - ((a00 * m0 + a01 * m1) + a02 * m2);
+    const double r1 = b1 - ((a01 * m0 + a11 * m1) + a12 * m2);
+    const double r2 = b2 - ((a02 * m0 + a12 * m1) + a22 * m2);
+    const double c00 = a11 * a22 - a12 * a12;
+    const double c01 = a12 * a02 - a01 * a22;
+    const double c02 = a01 * a12 - a11 * a02;
+    const double c11 = a00 * a22 - a02 * a02;
+    const double c12 = a01 * a02 - a00 * a12;
+    const double c22 = a00 * a11 - a01 * a01;
+    const double det = (a00 * c00 + a01 * c01) + a02 * c02;
+    const double t3 = ((a00 + a11) + a22) / 3.0;
+    z0 = m0;
+    z1 = m1;
+    z2 = m2;
+    if (det > kTau * ((t3 * t3) * t3)) {
+        const double y0 = m0 + ((c00 * r0 + c01 * r1) + c02 * r2) / det;
+        const double y1 = m1 + ((c01 * r0 + c11 * r1) + c12 * r2) / det;
+        const double y2 = m2 + ((c02 * r0 + c12 * r1) + c22 * r2) / det;
+        const double L = fmax(fmax(fabs(pa0 - pb0), fabs(pa1 - pb1)), fabs(pa2 - pb2));
+        const bool in = y0 >= fmin(pa0, pb0) - L && y0 <= fmax(pa0, pb0) + L && y1 >= fmin(pa1, pb1) - L &&
+                        y1 <= fmax(pa1, pb1) + L && y2 >= fmin(pa2, pb2) - L && y2 <= fmax(pa2, pb2) + L;
+        if (in) {
+            z0 = y0;
+            z1 = y1;
+            z2 = y2;
+        }
+    }
+    const double s0 = ((qe[0] * z0 + qe[1] * z1) + qe[2] * z2) + qe[3];
+    const double s1 = ((qe[1] * z0 + qe[4] * z1) + qe[5] * z2) + qe[6];
+    const double s2 = ((qe[2] * z0 + qe[5] * z1) + qe[7] * z2) + qe[8];
+    const double s3 = ((qe[3] * z0 + qe[6] * z1) + qe[8] * z2) + qe[9];
+    const double c = ((s0 * z0 + s1 * z1) + s2 * z2) + s3;
+    cost = c > 0.0 ? c : 0.0;
+}
+
+// (L3) for face t, in which v appears once: the normal before and after v moves to z.
+__device__ __forceinline__ bool keeps_side(const double *p, const int64_t *t, int64_t v, double z0, double z1, double z2)
+{
+    const double *p0 = p + 3 * t[0], *p1 = p + 3 * t[1], *p2 = p + 3 * t[2];
+    double n0, n1, n2, k0, k1, k2;
+    cross_of(p0, p1, p2, n0, n1, n2);
+    const bool m0 = t[0] == v, m1 = t[1] == v, m2 = t[2] == v;
+    const double a0 = m0 ? z0 : p0[0], a1 = m0 ? z1 : p0[1], a2 = m0 ? z2 : p0[2];
+    const double b0 = m1 ? z0 : p1[0], b1 = m1 ? z1 : p1[1], b2 = m1 ? z2 : p1[2];
+    const double c0 = m2 ? z0 : p2[0], c1 = m2 ? z1 : p2[1], c2 = m2 ? z2 : p2[2];
+    const double u0 = b0 - a0, u1 = b1 - a1, u2 = b2 - a2;
+    const double w0 = c0 - a0, w1 = c1 - a1, w2 = c2 - a2;
+    k0 = u1 * w2 - u2 * w1;
+    k1 = u2 * w0 - u0 * w2;
+    k2 = u0 * w1 - u1 * w0;
+    return (n0 * k0 + n1 * k1) + n2 * k2 > 0.0;
+}
+
+// The other two vertices of face t at v, as (low, high).
+__device__ __forceinline__ void other_pair(const int64_t *t, int64_t v, int64_t &lo, int64_t &hi)
+{
+    const int64_t x = t[0] == v ? t[1] : t[0];
+    const int64_t y = t[2] == v ? t[1] : t[2];
+    lo = x < y ? x : y;
+    hi = x < y ? y : x;
+}
+
+__device__ __forceinline__ uint64_t mix(uint64_t x, uint64_t round)
+{
+    uint64_t s = x + (round + 1) * 0x9E3779B97F4A7C15ull;
+    s ^= s >> 30;
+    s *= 0xBF58476D1CE4E5B9ull;
+    s ^= s >> 27;
+    s *= 0x94D049BB133111EBull;
+    s ^= s >> 31;
+    return s;
+}
+
+// Steps 3 to 5 and m1, one thread per edge.
+__global__ __launch_bounds__(kBlock) void candidate_kernel(Mesh M, Workspace ws, double max_cost, uint64_t round)
+{
+    const int64_t e = gtid();
+    if (e >= M.E) return;
+    ws.key[e] = kNone;
+    ws.skey_a[e] = kNone;
+    if (ws.nkey_a[2 * e] == kNone) return;
+    const int64_t a = M.edges[2 * e], b = M.edges[2 * e + 1];
+    if (ws.locked[a] || ws.locked[b]) return;
+    double qe[10], z0, z1, z2, cost;
+    collapse_point(M.p, M.Q, a, b, qe, z0, z1, z2, cost);
+    if (cost > max_cost) return;
+    atomicAdd(&ws.info->candidates, 1ull);
+
+    // (L1) rows are ascending and hold no vertex twice
+    int common = 0;
+    {
+        int64_t i = ws.nstart[a], j = ws.nstart[b];
+        const int64_t ie = ws.nend[a], je = ws.nend[b];
+        while (i < ie && j < je) {
+            const uint32_t x = (uint32_t)ws.nkey_b[i], y = (uint32_t)ws.nkey_b[j];
+            common += x == y;
+            i += x <= y;
+            j += y <= x;
+        }
+    }
+    if (common != ws.uses[e]) return;
+    // (L2) and (L3) over the faces of a without b, then (L3) over those of b without a
+    const int64_t bs = ws.fstart[b], be = ws.fend[b];
+    for (int64_t i = ws.fstart[a], ie = ws.fend[a]; i < ie; ++i) {
+        const int64_t *t = M.f + 3 * (int64_t)(ws.fkey_b[i] & 0xffffffffu);
+        if (t[0] == b || t[1] == b || t[2] == b) continue;
+        if (!keeps_side(M.p, t, a, z0, z1, z2)) return;
+        int64_t lo, hi;
+        other_pair(t, a, lo, hi);
+        for (int64_t j = bs; j < be; ++j) {
+            const int64_t *u = M.f + 3 * (int64_t)(ws.fkey_b[j] & 0xffffffffu);
+            if (u[0] == a || u[1] == a || u[2] == a) continue;
+            int64_t lo2, hi2;
+            other_pair(u, b, lo2, hi2);
+            if (lo == lo2 && hi == hi2) return;
+        }
+    }
+    for (int64_t j = bs; j < be; ++j) {
+        const int64_t *u = M.f + 3 * (int64_t)(ws.fkey_b[j] & 0xffffffffu);
+        if (u[0] == a || u[1] == a || u[2] == a) continue;
+        if (!keeps_side(M.p, u, b, z0, z1, z2)) return;
+    }
+    atomicAdd(&ws.info->legal, 1ull);
+    const uint64_t bits = (uint64_t)__double_as_longlong(cost);
+    const uint64_t key = (bits >> 52) << 52 | (mix((uint64_t)a << 32 | (uint64_t)b, round) & 0x1FFFFFull) << 31 | (uint64_t)e;
+    ws.key[e] = key;
+    ws.skey_a[e] = bits;
+    atomicMin((unsigned long long *)&ws.m1[a], (unsigned long long)key);
+    atomicMin((unsigned long long *)&ws.m1[b], (unsigned long long)key);
+}
+
+__global__ __launch_bounds__(kBlock) void min2_kernel(int64_t V, Workspace ws)
+{
+    const int64_t v = gtid();
+    if (v >= V) return;
+    uint64_t m = ws.m1[v];
+    for (int64_t i = ws.nstart[v], ie = ws.nend[v]; i < ie; ++i) {
+        const uint64_t x = ws.m1[(uint32_t)ws.nkey_b[i]];
+        m = x < m ? x : m;
+    }
+    ws.m2[v] = m;
+}
+
+// Step 6: the sort key of a selected edge is its cost bits, of any other edge all ones.
+__global__ __launch_bounds__(kBlock) void select_kernel(Mesh M, Workspace ws)
+{
+    const int64_t e = gtid();
+    if (e >= M.E) return;
+    const uint64_t key = ws.key[e];
+    bool sel = key != kNone;
+    if (sel) sel = key == ws.m2[M.edges[2 * e]] && key == ws.m2[M.edges[2 * e + 1]];
+    if (sel) atomicAdd(&ws.info->selected, 1ull);
+    else ws.skey_a[e] = kNone;
+    ws.sval_a[e] = (int32_t)e;
+}
+
+__global__ void collapse_counts_kernel(Workspace ws, int64_t max_take, int64_t *counts)
+{
+    const int64_t sel = (int64_t)ws.info->selected;
+    counts[0] = (int64_t)ws.info->candidates;
+    counts[1] = (int64_t)ws.info->legal;
+    counts[2] = sel;
+    counts[3] = sel < max_take ? sel : max_take;
+    counts[4] = (int64_t)ws.info->locked;
+    counts[5] = (int64_t)ws.info->invalid;
+}
+
+// Step 8 for the i-th edge of the sorted selection.  The ends of two taken edges neither coincide nor neighbour, so no
+// thread reads what another writes.
+__global__ __launch_bounds__(kBlock) void apply_kernel(double *p, double *Q, const int64_t *edges, int64_t n, Workspace ws)
+{
+    const int64_t i = gtid();
+    if (i >= n || ws.skey_b[i] == kNone) return;
+    const int64_t e = ws.sval_b[i];
+    const int64_t a = edges[2 * e], b = edges[2 * e + 1];
+    double qe[10], z0, z1, z2, cost;
+    collapse_point(p, Q, a, b, qe, z0, z1, z2, cost);
+    p[3 * a] = z0;
+    p[3 * a + 1] = z1;
+    p[3 * a + 2] = z2;
+    double *qa = Q + 10 * a;
+#pragma unroll
+    for (int k = 0; k < 10; ++k) qa[k] = qe[k];
+    ws.remap[b] = (int32_t)a;
+}
+
+__global__ __launch_bounds__(kBlock) void remap_kernel(int64_t *idx, int64_t n, int64_t V, const int32_t *remap)
+{
+    const int64_t i = gtid();
+    if (i >= n) return;
+    const int64_t v = idx[i];
+    if (v < 0 || v >= V) return;
+    const int32_t r = remap[v];
+    if (r >= 0) idx[i] = r;
+}
+
+__global__ __launch_bounds__(kBlock) void gather_vertex_kernel(const double *Q, const uint8_t *lock, const int64_t *vertex_map,
+                                                               int64_t V, int64_t n_out, double *out_Q, uint8_t *out_lock,
+                                                               int32_t *inverse)
+{
+    const int64_t j = gtid();
+    if (j >= n_out) return;
+    const int64_t s = vertex_map[j];
+    if (s < 0 || s >= V) return;
+#pragma unroll
+    for (int k = 0; k < 10; ++k) out_Q[10 * j + k] = Q[10 * s + k];
+    if (lock) out_lock[j] = lock[s];
+    inverse[s] = (int32_t)j;
+}
+
+__global__ __launch_bounds__(kBlock) void gather_face_kernel(const int64_t *face_map, const int64_t *compact_face_map,
+                                                             int64_t F, int64_t n_out, int64_t *out_face_map)
+{
+    const int64_t i = gtid();
+    if (i >= n_out) return;
+    const int64_t s = compact_face_map[i];
+    if (s >= 0 && s < F) out_face_map[i] = face_map[s];
+}
+
+__global__ __launch_bounds__(kBlock) void target_kernel(int64_t *target, int64_t n, int64_t V, const int32_t *inverse)
+{
+    const int64_t i = gtid();
+    if (i >= n) return;
+    const int64_t t = target[i];
+    if (t >= 0 && t < V) target[i] = inverse[t];
+}
+
+// The CSR of faces: keys, sort, runs.
+int build_face_rows(const Mesh &M, Workspace &ws, hipStream_t s)
+{
+    QF_HIP_TRY(hipMemsetAsync(ws.fstart, 0, 8 * (size_t)M.V, s));
+    QF_HIP_TRY(hipMemsetAsync(ws.fend, 0, 8 * (size_t)M.V, s));
+    if (M.F == 0) return QF_OK;
+    const int64_t n = 3 * M.F;
+    hipLaunchKernelGGL(face_key_kernel, dim3(blocks(n)), dim3(kBlock), 0, s, M, ws);
+    QF_LAUNCH_CHECK();
+    size_t tb = ws.temp_bytes;
+    QF_HIP_TRY(rocprim::radix_sort_keys(ws.temp, tb, ws.fkey_a, ws.fkey_b, (size_t)n, 0, 64, s));
+    hipLaunchKernelGGL(range_kernel, dim3(blocks(n)), dim3(kBlock), 0, s, ws.fkey_b, n, ws.fstart, ws.fend);
+    QF_LAUNCH_CHECK();
+    return QF_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t qf_mesh_decimate_workspace_bytes(int64_t n_vertices, int64_t n_faces, int64_t n_edges)
+{
+    if (!sizes_ok(n_vertices, n_faces, n_edges)) return -1;
+    const size_t temp = temp_bytes_for(n_faces, n_edges, nullptr);
+    if (temp == 0) return -1;
+    return carve(nullptr, n_vertices, n_faces, n_edges, temp).bytes;
+}
+
+extern "C" int qf_mesh_vertex_quadrics(const double *vertices, int64_t n_vertices, const int64_t *faces, int64_t n_faces,
+                                       double *quadrics, void *workspace, int64_t workspace_bytes, int64_t *counts,
+                                       void *stream)
+{
+    if (!sizes_ok(n_vertices, n_faces, 0) || !vertices || (n_faces > 0 && !faces) || !quadrics || !workspace || !counts)
+        return QF_ERR_INVALID_ARGUMENT;
+    hipStream_t s = qf_stream(stream);
+    const size_t temp = temp_bytes_for(n_faces, 0, s);
+    if (temp == 0) return QF_ERR_HIP;
+    Workspace ws = carve(workspace, n_vertices, n_faces, 0, temp);
+    if (workspace_bytes < ws.bytes) return QF_ERR_INVALID_ARGUMENT;
+    const Mesh M{vertices, faces, nullptr, nullptr, nullptr, n_vertices, n_faces, 0};
+
+    QF_HIP_TRY(hipMemsetAsync(ws.info, 0, sizeof(Info), s));
+    const int st = build_face_rows(M, ws, s);
+    if (st != QF_OK) return st;
+    if (M.F > 0) {
+        hipLaunchKernelGGL(plane_kernel, dim3(blocks(M.F)), dim3(kBlock), 0, s, M, ws);
+        QF_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(quadric_kernel, dim3(blocks(M.V)), dim3(kBlock), 0, s, M, ws, quadrics);
+    QF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(quadric_counts_kernel, dim3(1), dim3(1), 0, s, ws, counts);
+    QF_LAUNCH_CHECK();
+    return QF_OK;
+}
+
+extern "C" int qf_mesh_collapse_select(const double *vertices, int64_t n_vertices, const int64_t *faces, int64_t n_faces,
+                                       const int64_t *edges, int64_t n_edges, const int64_t *face_edges,
+                                       const double *quadrics, const uint8_t *vertex_lock, double max_cost, int64_t round,
+                                       int64_t max_take, void *workspace, int64_t workspace_bytes, int64_t *counts,
+                                       void *stream)
+{
+    if (!sizes_ok(n_vertices, n_faces, n_edges) || !vertices || (n_faces > 0 && (!faces || !face_edges)) ||
+        (n_edges > 0 && !edges) || !quadrics || !workspace || !counts || !(max_cost >= 0.0) || round < 0 || max_take < 0)
+        return QF_ERR_INVALID_ARGUMENT;
+    hipStream_t s = qf_stream(stream);
+    const size_t temp = temp_bytes_for(n_faces, n_edges, s);
+    if (temp == 0) return QF_ERR_HIP;
+    Workspace ws = carve(workspace, n_vertices, n_faces, n_edges, temp);
+    if (workspace_bytes < ws.bytes) return QF_ERR_INVALID_ARGUMENT;
+    const Mesh M{vertices, faces, edges, face_edges, quadrics, n_vertices, n_faces, n_edges};
+    const int64_t V = M.V, F = M.F, E = M.E;
+
+    QF_HIP_TRY(hipMemsetAsync(ws.info, 0, sizeof(Info), s));
+    QF_HIP_TRY(hipMemsetAsync(ws.nstart, 0, 8 * (size_t)V, s));
+    QF_HIP_TRY(hipMemsetAsync(ws.nend, 0, 8 * (size_t)V, s));
+    QF_HIP_TRY(hipMemsetAsync(ws.m1, 0xff, 8 * (size_t)V, s));
+    const int st = build_face_rows(M, ws, s);
+    if (st != QF_OK) return st;
+    hipLaunchKernelGGL(lock_init_kernel, dim3(blocks(V)), dim3(kBlock), 0, s, V, vertex_lock, ws);
+    QF_LAUNCH_CHECK();
+    if (E > 0) {
+        QF_HIP_TRY(hipMemsetAsync(ws.uses, 0, 4 * (size_t)E, s));
+        hipLaunchKernelGGL(edge_key_kernel, dim3(blocks(E)), dim3(kBlock), 0, s, M, ws);
+        QF_LAUNCH_CHECK();
+        size_t tb = ws.temp_bytes;
+        QF_HIP_TRY(rocprim::radix_sort_keys(ws.temp, tb, ws.nkey_a, ws.nkey_b, (size_t)(2 * E), 0, 64, s));
+        hipLaunchKernelGGL(range_kernel, dim3(blocks(2 * E)), dim3(kBlock), 0, s, ws.nkey_b, 2 * E, ws.nstart, ws.nend);
+        QF_LAUNCH_CHECK();
+        if (F > 0) {
+            hipLaunchKernelGGL(uses_kernel, dim3(blocks(3 * F)), dim3(kBlock), 0, s, M, ws);
+            QF_LAUNCH_CHECK();
+        }
+        hipLaunchKernelGGL(lock_edge_kernel, dim3(blocks(E)), dim3(kBlock), 0, s, M, ws);
+        QF_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(lock_count_kernel, dim3(blocks(V)), dim3(kBlock), 0, s, V, ws);
+    QF_LAUNCH_CHECK();
+    if (E > 0) {
+        hipLaunchKernelGGL(candidate_kernel, dim3(blocks(E)), dim3(kBlock), 0, s, M, ws, max_cost, (uint64_t)round);
+        QF_LAUNCH_CHECK();
+        hipLaunchKernelGGL(min2_kernel, dim3(blocks(V)), dim3(kBlock), 0, s, V, ws);
+        QF_LAUNCH_CHECK();
+        hipLaunchKernelGGL(select_kernel, dim3(blocks(E)), dim3(kBlock), 0, s, M, ws);
+        QF_LAUNCH_CHECK();
+        size_t tb = ws.temp_bytes;
+        QF_HIP_TRY(rocprim::radix_sort_pairs(ws.temp, tb, ws.skey_a, ws.skey_b, ws.sval_a, ws.sval_b, (size_t)E, 0, 64, s));
+    }
+    hipLaunchKernelGGL(collapse_counts_kernel, dim3(1), dim3(1), 0, s, ws, max_take, counts);
+    QF_LAUNCH_CHECK();
+    return QF_OK;
+}
+
+extern "C" int qf_mesh_collapse_apply(double *vertices, int64_t n_vertices, int64_t *faces, int64_t n_faces,
+                                      const int64_t *edges, int64_t n_edges, double *quadrics, int64_t max_take,
+                                      int64_t *vertex_target, int64_t n_targets, void *workspace, int64_t workspace_bytes,
+                                      void *stream)
+{
+    if (!sizes_ok(n_vertices, n_faces, n_edges) || !vertices || (n_faces > 0 && !faces) || (n_edges > 0 && !edges) ||
+        !quadrics || !workspace || max_take < 0 || n_targets < 0 || n_targets >= kMaxCount || (n_targets > 0 && !vertex_target))
+        return QF_ERR_INVALID_ARGUMENT;
+    hipStream_t s = qf_stream(stream);
+    const size_t temp = temp_bytes_for(n_faces, n_edges, s);
+    if (temp == 0) return QF_ERR_HIP;
+    Workspace ws = carve(workspace, n_vertices, n_faces, n_edges, temp);
+    if (workspace_bytes < ws.bytes) return QF_ERR_INVALID_ARGUMENT;
+
+    QF_HIP_TRY(hipMemsetAsync(ws.remap, 0xff, 4 * (size_t)n_vertices, s));
+    const int64_t n = max_take < n_edges ? max_take : n_edges;
+    if (n > 0) {
+        hipLaunchKernelGGL(apply_kernel, dim3(blocks(n)), dim3(kBlock), 0, s, vertices, quadrics, edges, n, ws);
+        QF_LAUNCH_CHECK();
+    }
+    if (n_faces > 0) {
+        hipLaunchKernelGGL(remap_kernel, dim3(blocks(3 * n_faces)), dim3(kBlock), 0, s, faces, 3 * n_faces, n_vertices,
+                           ws.remap);
+        QF_LAUNCH_CHECK();
+    }
+    if (n_targets > 0) {
+        hipLaunchKernelGGL(remap_kernel, dim3(blocks(n_targets)), dim3(kBlock), 0, s, vertex_target, n_targets, n_vertices,
+                           ws.remap);
+        QF_LAUNCH_CHECK();
+    }
+    return QF_OK;
+}
+
+extern "C" int qf_mesh_collapse_gather(const double *quadrics, const uint8_t *vertex_lock, const int64_t *face_map,
+                                       int64_t n_vertices, int64_t n_faces, const int64_t *vertex_map,
+                                       int64_t n_out_vertices, const int64_t *compact_face_map, int64_t n_out_faces,
+                                       double *out_quadrics, uint8_t *out_lock, int64_t *out_face_map,
+                                       int64_t *vertex_target, int64_t n_targets, void *workspace, int64_t workspace_bytes,
+                                       void *stream)
+{
+    if (!sizes_ok(n_vertices, n_faces, 0) || n_out_vertices < 0 || n_out_vertices > n_vertices || n_out_faces < 0 ||
+        n_out_faces > n_faces || !quadrics || (n_faces > 0 && !face_map) || (!vertex_lock != !out_lock) ||
+        (n_out_vertices > 0 && (!vertex_map || !out_quadrics)) || (n_out_faces > 0 && (!compact_face_map || !out_face_map)) ||
+        n_targets < 0 || n_targets >= kMaxCount || (n_targets > 0 && !vertex_target) || !workspace ||
+        workspace_bytes < 4 * n_vertices)
+        return QF_ERR_INVALID_ARGUMENT;
+    hipStream_t s = qf_stream(stream);
+    int32_t *inverse = static_cast<int32_t *>(workspace);
+    QF_HIP_TRY(hipMemsetAsync(inverse, 0xff, 4 * (size_t)n_vertices, s));
+    if (n_out_vertices > 0) {
+        hipLaunchKernelGGL(gather_vertex_kernel, dim3(blocks(n_out_vertices)), dim3(kBlock), 0, s, quadrics, vertex_lock,
+                           vertex_map, n_vertices, n_out_vertices, out_quadrics, out_lock, inverse);
+        QF_LAUNCH_CHECK();
+    }
+    if (n_out_faces > 0) {
+        hipLaunchKernelGGL(gather_face_kernel, dim3(blocks(n_out_faces)), dim3(kBlock), 0, s, face_map, compact_face_map,
+                           n_faces, n_out_faces, out_face_map);
+        QF_LAUNCH_CHECK();
+    }
+    if (n_targets > 0) {
+        hipLaunchKernelGGL(target_kernel, dim3(blocks(n_targets)), dim3(kBlock), 0, s, vertex_target, n_targets, n_vertices,
+                           inverse);
+        QF_LAUNCH_CHECK();
+    }
+    return QF_OK;
+}

@@ -631,3 +631,184 @@ def mark_edges_longer_than(vertices: torch.Tensor, edges: torch.Tensor, length: 
         raise ValueError(f"vertices must be [V,3] and edges [E,2], got {tuple(vertices.shape)} and {tuple(edges.shape)}")
     d = vertices[edges[:, 0]] - vertices[edges[:, 1]]
     return ((d * d).sum(dim=1) > float(length) ** 2).to(torch.uint8)
+
+
+# ---- mesh decimation (include/qf_mesh_decimate.h) -----------------------------------------------
+
+DecimatedMesh = namedtuple("DecimatedMesh", ["vertices", "faces", "face_map", "vertex_target", "stats"])
+DECIMATE_STOP_TARGET, DECIMATE_STOP_NO_EDGE, DECIMATE_STOP_MAX_ROUNDS = ("target reached", "no edge taken",
+                                                                          "max_rounds reached")
+
+
+def decimate_mesh_device(vertices: torch.Tensor, faces: torch.Tensor, target_faces: int, *, max_cost=None,
+                         vertex_lock=None, max_rounds: int = 128, return_stats: bool = False) -> DecimatedMesh:
+    """Bring a mesh down to ``target_faces`` faces on the device by rounds of independent quadric edge collapses, under
+    the rules of DESIGN.md section 3.9d (this project's own; parity with the reference's ``fast_simplification`` is
+    unpinned).  Per round: the edges are numbered, every edge whose ends are neither locked nor on a boundary or
+    non-manifold edge gets the point that minimises the summed quadrics of its ends and that point's cost, candidates that
+    would break the surface's topology or flip a face are dropped, an independent set of the rest is selected through
+    hashed power-of-two cost buckets, the cheapest of it are collapsed up to the face budget, and the mesh is compacted.
+    ``vertices``: device float [V,3] (fp32 is widened exactly), all finite; ``faces``: device int64 or int32 [F,3];
+    ``max_cost``: candidates that cost more are dropped (None: no limit); ``vertex_lock``: bool / integer [V], vertices
+    that neither move nor disappear.  Returns ``DecimatedMesh(vertices fp64 [V',3], faces int64 [F',3], face_map int64
+    [F'], vertex_target int64 [V], stats)``: output faces keep their winding and relative order, ``face_map`` names the
+    source face of each, ``vertex_target[v]`` is the output vertex that input vertex v ended in (-1 if it was dropped as
+    unreferenced).  With ``return_stats`` ``stats`` is a dict: ``rounds``, the per-round lists ``faces`` (after the round),
+    ``candidates``, ``legal``, ``selected``, ``taken``, and ``stop`` (one of the ``DECIMATE_STOP_*`` strings); else None.
+    ``target_faces >= F`` returns copies of the input, bit for bit.  Two host waits per round, for the edge count and for
+    the compaction's counts (the round's own counts come with the latter).  Raises ValueError for host tensors, bad
+    shapes and, with their number, faces that index outside [0, V) and vertices that are not finite."""
+    if not isinstance(vertices, torch.Tensor):
+        raise TypeError("vertices and faces must be torch.Tensors")
+    f = _device_faces(faces, "decimate_mesh_device")
+    if vertices.ndim != 2 or vertices.shape[1] != 3:
+        raise ValueError(f"vertices must be [V,3], got {tuple(vertices.shape)}")
+    if not vertices.is_floating_point():
+        raise TypeError(f"vertices must be floating point, got {vertices.dtype}")
+    if not vertices.is_cuda:
+        raise ValueError("decimate_mesh_device needs device tensors (quadraturefields_amd has no CPU fallback)")
+    if vertices.device != f.device:
+        raise ValueError(f"vertices on {vertices.device} and faces on {f.device}")
+    target, max_rounds = int(target_faces), int(max_rounds)
+    if target != target_faces or target < 0 or max_rounds < 0:
+        raise ValueError(f"target_faces and max_rounds must be integers >= 0, got {target_faces} and {max_rounds}")
+    cost_cap = math.inf if max_cost is None else float(max_cost)
+    if not cost_cap >= 0.0:
+        raise ValueError(f"max_cost must be >= 0, got {max_cost}")
+    dev = vertices.device
+    n_v0, n_f0 = vertices.shape[0], f.shape[0]
+    if n_v0 >= 2 ** 31 or 3 * n_f0 >= 2 ** 31:
+        raise ValueError(f"the mesh has {n_v0} vertices and {n_f0} faces; V and 3 F must be < 2^31")
+    lock = None if vertex_lock is None else _device_keep(vertex_lock, n_v0, dev)
+    v = vertices.to(torch.float64).contiguous().clone()
+    f = f.clone()
+    face_map = torch.arange(n_f0, dtype=torch.int64, device=dev)
+    vertex_target = torch.arange(n_v0, dtype=torch.int64, device=dev)
+    stats = {"rounds": 0, "faces": [], "candidates": [], "legal": [], "selected": [], "taken": [], "stop": None}
+    lib = _C.lib()
+    flags = _C.MESH_REMOVE_DEGENERATE | _C.MESH_REMOVE_UNREFERENCED
+    quadrics = None
+
+    def workspace(n_v, n_f, n_e):
+        n = int(lib.qf_mesh_decimate_workspace_bytes(n_v, n_f, n_e))
+        if n < 0:
+            raise RuntimeError(f"qf_mesh_decimate_workspace_bytes refused V={n_v}, F={n_f}, E={n_e}")
+        return torch.empty((n,), dtype=torch.uint8, device=dev), n
+
+    with torch.cuda.device(dev):
+        while True:
+            n_v, n_f = v.shape[0], f.shape[0]
+            if n_f <= target:
+                stats["stop"] = DECIMATE_STOP_TARGET
+                break
+            if stats["rounds"] >= max_rounds:
+                stats["stop"] = DECIMATE_STOP_MAX_ROUNDS
+                break
+            if n_v == 0:
+                raise ValueError(f"{n_f} faces have an index outside [0, 0)")
+            if quadrics is None:
+                quadrics = torch.empty((n_v, 10), dtype=torch.float64, device=dev)
+                quadric_counts = torch.empty((len(_C.MESH_QUADRIC_COUNTS),), dtype=torch.int64, device=dev)
+                ws, ws_bytes = workspace(n_v, n_f, 0)
+                _C.check(lib.qf_mesh_vertex_quadrics(_C.ptr(v), n_v, _C.ptr(f), n_f, _C.ptr(quadrics), _C.ptr(ws), ws_bytes,
+                                                     _C.ptr(quadric_counts), _C.stream()), "qf_mesh_vertex_quadrics")
+                edges, face_edges, _ = mesh_edges_device(f, n_v)          # raises for faces out of range
+                n_bad = quadric_counts.tolist()[0]                        # the stream has drained: no further wait
+                if n_bad:
+                    raise ValueError(f"{n_bad} vertices are not finite")
+            else:
+                edges, face_edges, _ = mesh_edges_device(f, n_v)
+            n_e = edges.shape[0]
+            max_take = (n_f - target + 1) // 2
+            ws, ws_bytes = workspace(n_v, n_f, n_e)
+            counts = torch.empty((len(_C.MESH_COLLAPSE_COUNTS),), dtype=torch.int64, device=dev)
+            _C.check(lib.qf_mesh_collapse_select(_C.ptr(v), n_v, _C.ptr(f), n_f, _C.ptr(edges), n_e, _C.ptr(face_edges),
+                                                 _C.ptr(quadrics), _C.ptr(lock), cost_cap, stats["rounds"], max_take,
+                                                 _C.ptr(ws), ws_bytes, _C.ptr(counts), _C.stream()),
+                     "qf_mesh_collapse_select")
+            _C.check(lib.qf_mesh_collapse_apply(_C.ptr(v), n_v, _C.ptr(f), n_f, _C.ptr(edges), n_e, _C.ptr(quadrics),
+                                                max_take, _C.ptr(vertex_target), n_v0, _C.ptr(ws), ws_bytes, _C.stream()),
+                     "qf_mesh_collapse_apply")
+            c_bytes = int(lib.qf_mesh_compact_workspace_bytes(n_v, n_f))
+            if c_bytes < 0:
+                raise RuntimeError(f"qf_mesh_compact_workspace_bytes refused V={n_v}, F={n_f}")
+            c_ws = torch.empty((c_bytes,), dtype=torch.uint8, device=dev)
+            c_counts = torch.empty((len(_C.MESH_COMPACT_COUNTS),), dtype=torch.int64, device=dev)
+            c_args = (_C.ptr(v), n_v, _C.ptr(f), n_f, None, flags, 0, _C.ptr(c_ws), c_bytes)
+            _C.check(lib.qf_mesh_compact_count(*c_args, _C.ptr(c_counts), _C.stream()), "qf_mesh_compact_count")
+            both = torch.cat([c_counts, counts]).tolist()                 # the round's second host wait
+            compacted = dict(zip(_C.MESH_COMPACT_COUNTS, both))
+            collapse = dict(zip(_C.MESH_COLLAPSE_COUNTS, both[len(_C.MESH_COMPACT_COUNTS):]))
+            stats["rounds"] += 1
+            for name in ("candidates", "legal", "selected", "taken"):
+                stats[name].append(collapse[name])
+            if collapse["taken"] == 0:
+                stats["faces"].append(n_f)
+                stats["stop"] = DECIMATE_STOP_NO_EDGE
+                break
+            m_v, m_f = compacted["vertices"], compacted["faces"]
+            out_v = torch.empty((m_v, 3), dtype=torch.float64, device=dev)
+            out_f = torch.empty((m_f, 3), dtype=torch.int64, device=dev)
+            c_face_map = torch.empty((m_f,), dtype=torch.int64, device=dev)
+            c_vertex_map = torch.empty((m_v,), dtype=torch.int64, device=dev)
+            _C.check(lib.qf_mesh_compact_emit(*c_args, _C.ptr(out_v), m_v, _C.ptr(out_f), m_f, _C.ptr(c_face_map),
+                                              _C.ptr(c_vertex_map), _C.stream()), "qf_mesh_compact_emit")
+            out_q = torch.empty((m_v, 10), dtype=torch.float64, device=dev)
+            out_lock = None if lock is None else torch.empty((m_v,), dtype=torch.uint8, device=dev)
+            out_face_map = torch.empty((m_f,), dtype=torch.int64, device=dev)
+            _C.check(lib.qf_mesh_collapse_gather(_C.ptr(quadrics), _C.ptr(lock), _C.ptr(face_map), n_v, n_f,
+                                                 _C.ptr(c_vertex_map), m_v, _C.ptr(c_face_map), m_f, _C.ptr(out_q),
+                                                 _C.ptr(out_lock), _C.ptr(out_face_map), _C.ptr(vertex_target), n_v0,
+                                                 _C.ptr(ws), ws_bytes, _C.stream()), "qf_mesh_collapse_gather")
+            v, f, quadrics, lock, face_map = out_v, out_f, out_q, out_lock, out_face_map
+            stats["faces"].append(m_f)
+    return DecimatedMesh(v, f, face_map, vertex_target, stats if return_stats else None)
+
+
+def decimate_mesh(mesh: TriMesh, target_faces: int, *, max_cost=None, vertex_lock=None, max_rounds: int = 128,
+                  return_stats: bool = False, device="cuda"):
+    """``decimate_mesh_device`` on a ``TriMesh``: ``(TriMesh, face_map, vertex_target)`` with numpy int64 maps (and the
+    stats dict fourth with ``return_stats``).  An output vertex takes the per-vertex ``visual.uv`` of the input vertex
+    with the lowest index among those that ended in it: the end a collapse keeps."""
+    dev = _C.resolve_device(device)
+    out = decimate_mesh_device(torch.from_numpy(np.asarray(mesh.vertices, np.float64)).to(dev),
+                               torch.from_numpy(np.asarray(mesh.faces, np.int64)).to(dev), target_faces,
+                               max_cost=max_cost, vertex_lock=vertex_lock, max_rounds=max_rounds, return_stats=True)
+    vertex_target = out.vertex_target.cpu().numpy()
+    uv = None
+    if mesh.visual.uv is not None:
+        ends, first = np.unique(vertex_target, return_index=True)
+        uv = np.zeros((out.vertices.shape[0], 2), dtype=np.asarray(mesh.visual.uv).dtype)
+        uv[ends[ends >= 0]] = np.asarray(mesh.visual.uv)[first[ends >= 0]]
+    res = (TriMesh(out.vertices.cpu().numpy(), out.faces.cpu().numpy(), uv), out.face_map.cpu().numpy(), vertex_target)
+    return res + (out.stats,) if return_stats else res
+
+
+def down_sample_quadraic(mesh: TriMesh, agg=None, verbose: bool = False, device="cuda") -> TriMesh:
+    """The reference's ``down_sample_quadraic`` (examples/mc_utils.py:214-219) on the device: the mesh decimated to
+    ``F // 10`` faces by ``decimate_mesh``.  The reference calls ``fast_simplification.simplify``; this is the project's
+    own rule and parity with it is unpinned.  ``agg``, fast_simplification's aggressiveness, has
+    no counterpart and is unused."""
+    out, _, _, stats = decimate_mesh(mesh, mesh.faces.shape[0] // 10, return_stats=True, device=device)
+    if verbose:
+        print(f"decimated {mesh.faces.shape[0]} -> {out.faces.shape[0]} faces in {stats['rounds']} rounds ({stats['stop']})")
+    return out
+
+
+def clean_mesh(mesh: TriMesh, agg=None, remove_duplicate_faces: bool = False, remove_non_manifold_edges: bool = False,
+               verbose: bool = False, device="cuda") -> TriMesh:
+    """The reference's ``clean_mesh`` (examples/mc_utils.py:222-242) on the device.  ``remove_duplicate_faces`` goes
+    through ``compact_mesh`` (every vertex kept, as trimesh's call leaves them); decimation to ``F // 10`` runs iff
+    ``agg > 0`` (``agg=None`` skips it; the reference would raise) -- ``agg``'s value is otherwise unused, since
+    fast_simplification's aggressiveness has no counterpart in DESIGN.md section 3.9d's rule, and parity with
+    fast_simplification is unpinned.  ``remove_non_manifold_edges=True`` (open3d's removal) is not built and raises
+    NotImplementedError, before any work."""
+    if remove_non_manifold_edges:
+        raise NotImplementedError("remove_non_manifold_edges (open3d's removal) is not built: DESIGN.md section 3.9d")
+    if remove_duplicate_faces:
+        mesh = compact_mesh(mesh, device=device, remove_duplicates=True, remove_unreferenced=False)[0]
+        if verbose:
+            print(f"after removing duplicate faces: {mesh.faces.shape[0]} faces")
+    if agg is not None and agg > 0:
+        mesh = down_sample_quadraic(mesh, agg, verbose=verbose, device=device)
+    return mesh
