@@ -2,10 +2,13 @@
 rules are this project's own, parity with the reference's fast_simplification is unpinned).
 
     python examples/decimate_mesh.py IN.ply OUT.ply (--target_faces N | --ratio R) [--max_cost C] [--max_rounds K]
+                                                [--boundary {lock,collapse}] [--boundary_weight W]
 
 Writes OUT.ply and, beside it, ``face_map.npy`` (the source face of every output face) and ``vertex_target.npy`` (the
-output vertex every input vertex ended in, -1 if it was dropped), and prints the stats as one JSON line.  Boundary and
-non-manifold edges are never collapsed, so a mesh made of them is returned as it is."""
+output vertex every input vertex ended in, -1 if it was dropped), and prints the stats as one JSON line.  With the default
+``--boundary lock`` boundary and non-manifold edges are never collapsed, so an open mesh keeps its border and the fine
+triangles along it; ``--boundary collapse`` adds boundary quadrics (weight ``--boundary_weight``) and collapses along the
+border too, so an open mesh reaches its target.  Non-manifold edges are never collapsed."""
 import argparse
 import json
 import os
@@ -25,6 +28,9 @@ def main(argv=None):
     goal.add_argument("--ratio", type=float, help="target = floor(ratio * F)")
     ap.add_argument("--max_cost", type=float, default=None)
     ap.add_argument("--max_rounds", type=int, default=128)
+    ap.add_argument("--boundary", choices=("lock", "collapse"), default="lock")
+    ap.add_argument("--boundary_weight", type=float, default=1.0,
+                    help="weight of a boundary edge's plane in the quadrics of its ends (collapse mode)")
     ap.add_argument("--device", default="cuda")
     args = ap.parse_args(argv)
     from quadraturefields_amd import mc_utils
@@ -36,12 +42,13 @@ def main(argv=None):
     target = args.target_faces if args.target_faces is not None else int(args.ratio * n_f)
     out, face_map, vertex_target, stats = mc_utils.decimate_mesh(mesh, target, max_cost=args.max_cost,
                                                                  max_rounds=args.max_rounds, return_stats=True,
-                                                                 device=args.device)
+                                                                 device=args.device, boundary=args.boundary,
+                                                                 boundary_weight=args.boundary_weight)
     out.export(args.mesh_out)
     folder = os.path.dirname(os.path.abspath(args.mesh_out))
     np.save(os.path.join(folder, "face_map.npy"), face_map)
     np.save(os.path.join(folder, "vertex_target.npy"), vertex_target)
-    print(json.dumps(dict(stats, faces_in=n_f, vertices_in=int(mesh.vertices.shape[0]), target_faces=target,
+    print(json.dumps(dict(stats, boundary=args.boundary, boundary_weight=args.boundary_weight, faces_in=n_f, vertices_in=int(mesh.vertices.shape[0]), target_faces=target,
                           faces_out=int(out.faces.shape[0]), vertices_out=int(out.vertices.shape[0]))))
 
 

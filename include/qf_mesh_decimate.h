@@ -44,7 +44,7 @@
  *                 candidate has exactly two faces, so the caller passes max_take = ceil((F - target_faces) / 2);
  *   8. apply      for a taken edge p[a] = z, Q[a] = Qe, b -> a; faces and vertex_target are remapped; the caller then
  *                 compacts and gathers Q, the locks and the maps through the compaction's maps.
- * Boundary quadrics, and collapsing boundary or non-manifold edges, are out of scope.
+ * Boundary quadrics and collapsing boundary edges are qf_mesh_decimate_open.h's; non-manifold edges never collapse.
  *
  * Invalid input is never followed out of bounds: a face with an index outside [0, V), a face_edges entry outside
  * [-1, E) or an edge that is not 0 <= a < b < V takes no part and is counted.                                        */

@@ -304,6 +304,20 @@ _MESH_DECIMATE_SIGNATURES = {
                                         c_int64, _P]),
 }
 
+# include/qf_mesh_decimate_open.h: the same rounds with boundary quadrics and boundary edge collapses (boundary =
+# "collapse"), additive in the same way
+MESH_BOUNDARY_COUNTS = ("boundary_planes", "invalid")
+MESH_COLLAPSE_OPEN_COUNTS = ("candidates", "legal", "selected", "taken", "locked_vertices", "invalid", "boundary_taken",
+                             "border_vertices")
+_MESH_DECIMATE_OPEN_SIGNATURES = {
+    "qf_mesh_decimate_open_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64]),
+    "qf_mesh_boundary_quadrics": (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, _P, _P, c_double, _P, c_int64, _P, _P]),
+    "qf_mesh_collapse_select_open": (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, _P, _P, _P, c_double, c_int64, c_int64,
+                                             _P, c_int64, _P, _P]),
+    "qf_mesh_collapse_apply_open": (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64,
+                                            _P]),
+}
+
 
 def vertex_row_stride(n_lobes: int) -> int:
     """Floats per row of a vertex table: the width 3 + 7L + 1 rounded up to a 64-byte line (16 / 32 / 48 / 64 for
@@ -326,7 +340,8 @@ def lib() -> ctypes.CDLL:
                                           + list(_VERTEX_TRAIN_SIGNATURES.items()) + list(_VERTEX_QUANT_SIGNATURES.items())
                                           + list(_MESH_COMPACT_SIGNATURES.items())
                                           + list(_MESH_SUBDIVIDE_SIGNATURES.items())
-                                          + list(_MESH_DECIMATE_SIGNATURES.items())):
+                                          + list(_MESH_DECIMATE_SIGNATURES.items())
+                                          + list(_MESH_DECIMATE_OPEN_SIGNATURES.items())):
             fn = getattr(handle, name)   # AttributeError if the symbol is not exported
             fn.restype = restype
             fn.argtypes = argtypes

@@ -75,7 +75,7 @@ def _deps(src: str):
             os.path.join(ROOT, "include", "qf_vertex_baked.h"), os.path.join(ROOT, "include", "qf_vertex_train.h"),
             os.path.join(ROOT, "include", "qf_vertex_quant.h"), os.path.join(ROOT, "include", "qf_mesh_compact.h"),
             os.path.join(ROOT, "include", "qf_mesh_subdivide.h"), os.path.join(ROOT, "include", "qf_mesh_decimate.h"),
-            os.path.abspath(__file__)]
+            os.path.join(ROOT, "include", "qf_mesh_decimate_open.h"), os.path.abspath(__file__)]
     deps += [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     return deps
 

@@ -17,9 +17,11 @@
 #include <cstring>
 
 #include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
 
 #include "qf_common.h"
 #include "qf_mesh_decimate.h"
+#include "qf_mesh_decimate_open.h"
 
 namespace {
 
@@ -264,13 +266,18 @@ __global__ __launch_bounds__(kBlock) void lock_count_kernel(int64_t V, Workspace
     if (v < V && ws.locked[v]) atomicAdd(&ws.info->locked, 1ull);
 }
 
-// Step 3: Qe, the point z and the cost of edge (a, b).
-__device__ __forceinline__ void collapse_point(const double *p, const double *Q, int64_t a, int64_t b, double *qe,
-                                               double &z0, double &z1, double &z2, double &cost)
+// Qe = Q[a] + Q[b] per component.
+__device__ __forceinline__ void edge_quadric(const double *Q, int64_t a, int64_t b, double *qe)
 {
     const double *qa = Q + 10 * a, *qb = Q + 10 * b;
 #pragma unroll
     for (int k = 0; k < 10; ++k) qe[k] = qa[k] + qb[k];
+}
+
+// Step 3's point for edge (a, b): the minimiser of Qe where it is well conditioned and near the edge, else the midpoint.
+__device__ __forceinline__ void optimal_point(const double *p, const double *qe, int64_t a, int64_t b, double &z0, double &z1,
+                                              double &z2)
+{
     const double *pa = p + 3 * a, *pb = p + 3 * b;
     const double pa0 = pa[0], pa1 = pa[1], pa2 = pa[2], pb0 = pb[0], pb1 = pb[1], pb2 = pb[2];
     const double m0 = (pa0 + pb0) * 0.5, m1 = (pa1 + pb1) * 0.5, m2 = (pa2 + pb2) * 0.5;
@@ -303,12 +310,33 @@ __device__ __forceinline__ void collapse_point(const double *p, const double *Q,
             z2 = y2;
         }
     }
+}
+
+// The cost of Qe at z, clamped at zero.
+__device__ __forceinline__ double point_cost(const double *qe, double z0, double z1, double z2)
+{
     const double s0 = ((qe[0] * z0 + qe[1] * z1) + qe[2] * z2) + qe[3];
     const double s1 = ((qe[1] * z0 + qe[4] * z1) + qe[5] * z2) + qe[6];
     const double s2 = ((qe[2] * z0 + qe[5] * z1) + qe[7] * z2) + qe[8];
     const double s3 = ((qe[3] * z0 + qe[6] * z1) + qe[8] * z2) + qe[9];
     const double c = ((s0 * z0 + s1 * z1) + s2 * z2) + s3;
-    cost = c > 0.0 ? c : 0.0;
+    return c > 0.0 ? c : 0.0;
+}
+
+// Step 3: Qe, the point z and the cost of edge (a, b).  With pin >= 0 (collapse mode, an edge from an interior vertex to
+// the border vertex `pin`) z is the position of `pin`, bit for bit.
+__device__ __forceinline__ void collapse_point(const double *p, const double *Q, int64_t a, int64_t b, int64_t pin, double *qe,
+                                               double &z0, double &z1, double &z2, double &cost)
+{
+    edge_quadric(Q, a, b, qe);
+    if (pin >= 0) {
+        z0 = p[3 * pin];
+        z1 = p[3 * pin + 1];
+        z2 = p[3 * pin + 2];
+    } else {
+        optimal_point(p, qe, a, b, z0, z1, z2);
+    }
+    cost = point_cost(qe, z0, z1, z2);
 }
 
 // (L3) for face t, in which v appears once: the normal before and after v moves to z.
@@ -349,21 +377,10 @@ __device__ __forceinline__ uint64_t mix(uint64_t x, uint64_t round)
     return s;
 }
 
-// Steps 3 to 5 and m1, one thread per edge.
-__global__ __launch_bounds__(kBlock) void candidate_kernel(Mesh M, Workspace ws, double max_cost, uint64_t round)
+// Step 4 for edge e = (a, b) collapsing to z.
+__device__ __forceinline__ bool collapse_legal(const Mesh &M, const Workspace &ws, int64_t e, int64_t a, int64_t b, double z0,
+                                               double z1, double z2)
 {
-    const int64_t e = gtid();
-    if (e >= M.E) return;
-    ws.key[e] = kNone;
-    ws.skey_a[e] = kNone;
-    if (ws.nkey_a[2 * e] == kNone) return;
-    const int64_t a = M.edges[2 * e], b = M.edges[2 * e + 1];
-    if (ws.locked[a] || ws.locked[b]) return;
-    double qe[10], z0, z1, z2, cost;
-    collapse_point(M.p, M.Q, a, b, qe, z0, z1, z2, cost);
-    if (cost > max_cost) return;
-    atomicAdd(&ws.info->candidates, 1ull);
-
     // (L1) rows are ascending and hold no vertex twice
     int common = 0;
     {
@@ -376,13 +393,13 @@ __global__ __launch_bounds__(kBlock) void candidate_kernel(Mesh M, Workspace ws,
             j += y <= x;
         }
     }
-    if (common != ws.uses[e]) return;
+    if (common != ws.uses[e]) return false;
     // (L2) and (L3) over the faces of a without b, then (L3) over those of b without a
     const int64_t bs = ws.fstart[b], be = ws.fend[b];
     for (int64_t i = ws.fstart[a], ie = ws.fend[a]; i < ie; ++i) {
         const int64_t *t = M.f + 3 * (int64_t)(ws.fkey_b[i] & 0xffffffffu);
         if (t[0] == b || t[1] == b || t[2] == b) continue;
-        if (!keeps_side(M.p, t, a, z0, z1, z2)) return;
+        if (!keeps_side(M.p, t, a, z0, z1, z2)) return false;
         int64_t lo, hi;
         other_pair(t, a, lo, hi);
         for (int64_t j = bs; j < be; ++j) {
@@ -390,14 +407,33 @@ __global__ __launch_bounds__(kBlock) void candidate_kernel(Mesh M, Workspace ws,
             if (u[0] == a || u[1] == a || u[2] == a) continue;
             int64_t lo2, hi2;
             other_pair(u, b, lo2, hi2);
-            if (lo == lo2 && hi == hi2) return;
+            if (lo == lo2 && hi == hi2) return false;
         }
     }
     for (int64_t j = bs; j < be; ++j) {
         const int64_t *u = M.f + 3 * (int64_t)(ws.fkey_b[j] & 0xffffffffu);
         if (u[0] == a || u[1] == a || u[2] == a) continue;
-        if (!keeps_side(M.p, u, b, z0, z1, z2)) return;
+        if (!keeps_side(M.p, u, b, z0, z1, z2)) return false;
     }
+    return true;
+}
+
+// Steps 3 to 5 and m1, one thread per edge.
+__global__ __launch_bounds__(kBlock) void candidate_kernel(Mesh M, Workspace ws, double max_cost, uint64_t round)
+{
+    const int64_t e = gtid();
+    if (e >= M.E) return;
+    ws.key[e] = kNone;
+    ws.skey_a[e] = kNone;
+    if (ws.nkey_a[2 * e] == kNone) return;
+    const int64_t a = M.edges[2 * e], b = M.edges[2 * e + 1];
+    if (ws.locked[a] || ws.locked[b]) return;
+    double qe[10], z0, z1, z2, cost;
+    collapse_point(M.p, M.Q, a, b, -1, qe, z0, z1, z2, cost);
+    if (cost > max_cost) return;
+    atomicAdd(&ws.info->candidates, 1ull);
+
+    if (!collapse_legal(M, ws, e, a, b, z0, z1, z2)) return;
     atomicAdd(&ws.info->legal, 1ull);
     const uint64_t bits = (uint64_t)__double_as_longlong(cost);
     const uint64_t key = (bits >> 52) << 52 | (mix((uint64_t)a << 32 | (uint64_t)b, round) & 0x1FFFFFull) << 31 | (uint64_t)e;
@@ -452,7 +488,7 @@ __global__ __launch_bounds__(kBlock) void apply_kernel(double *p, double *Q, con
     const int64_t e = ws.sval_b[i];
     const int64_t a = edges[2 * e], b = edges[2 * e + 1];
     double qe[10], z0, z1, z2, cost;
-    collapse_point(p, Q, a, b, qe, z0, z1, z2, cost);
+    collapse_point(p, Q, a, b, -1, qe, z0, z1, z2, cost);
     p[3 * a] = z0;
     p[3 * a + 1] = z1;
     p[3 * a + 2] = z2;
@@ -470,6 +506,282 @@ __global__ __launch_bounds__(kBlock) void remap_kernel(int64_t *idx, int64_t n, 
     if (v < 0 || v >= V) return;
     const int32_t r = remap[v];
     if (r >= 0) idx[i] = r;
+}
+
+// ---- boundary = collapse (include/qf_mesh_decimate_open.h) ---------------------------------------------------------------
+// The same passes with three changes: vertex classes in place of the boundary lock (integer atomicAdd of a vertex's boundary
+// edges, a flag for non-manifold ones), a candidate pass that knows the three edge kinds, and a budget that is a prefix of
+// the sorted selection by summed uses (a device-wide exclusive scan).  Round 0 adds the boundary planes to Q: the boundary
+// edges of a vertex are a CSR row of vertex << 32 | edge keys, so they are summed in ascending edge index by one thread.
+constexpr uint8_t kInterior = 0, kBorder = 1, kLocked = 2;
+
+struct OpenInfo {
+    unsigned long long taken, boundary_taken, border, planes;
+};
+
+struct Open {
+    OpenInfo *info;
+    int32_t *nb;        // [V] boundary edges at the vertex
+    uint8_t *bad;       // [V] an edge at the vertex has uses other than 1 or 2
+    uint8_t *cls;       // [V]
+    uint8_t *iso;       // [E] the edge belongs to a face whose three edges are boundary edges
+    int32_t *weight;    // [E] faces the i-th edge of the sorted selection removes, 0 behind the selection
+    int32_t *before;    // [E] exclusive scan of weight
+    double *eplane;     // [4E] constraint plane of a boundary edge, else zero
+    void *temp;
+    size_t temp_bytes;
+    int64_t bytes;
+};
+
+size_t scan_bytes_for(int64_t E, hipStream_t s)
+{
+    size_t b = 0;
+    if (rocprim::exclusive_scan(nullptr, b, (int32_t *)nullptr, (int32_t *)nullptr, (int32_t)0, (size_t)(E > 0 ? E : 1),
+                                rocprim::plus<int32_t>(), s) != hipSuccess)
+        return 0;
+    return b > 0 ? b : 1;
+}
+
+// The collapse-mode arrays lie behind the lock-mode workspace.
+Open carve_open(void *base, int64_t first, int64_t V, int64_t E, size_t temp)
+{
+    Open o;
+    int64_t off = align_up(first);
+    auto take = [&](int64_t bytes) { char *p = static_cast<char *>(base) + off; off += align_up(bytes); return p; };
+    o.info = reinterpret_cast<OpenInfo *>(take(sizeof(OpenInfo)));
+    o.nb = reinterpret_cast<int32_t *>(take(4 * V));
+    o.bad = reinterpret_cast<uint8_t *>(take(V));
+    o.cls = reinterpret_cast<uint8_t *>(take(V));
+    o.iso = reinterpret_cast<uint8_t *>(take(E));
+    o.weight = reinterpret_cast<int32_t *>(take(4 * E));
+    o.before = reinterpret_cast<int32_t *>(take(4 * E));
+    o.eplane = reinterpret_cast<double *>(take(32 * E));
+    o.temp = take((int64_t)temp);
+    o.temp_bytes = temp;
+    o.bytes = off;
+    return o;
+}
+
+__device__ __forceinline__ bool edge_ok(const int64_t *edges, int64_t e, int64_t V)
+{
+    const int64_t a = edges[2 * e], b = edges[2 * e + 1];
+    return a >= 0 && a < b && b < V;
+}
+
+// One thread per half-edge: the constraint plane of a boundary edge from its one face.
+__global__ __launch_bounds__(kBlock) void boundary_plane_kernel(Mesh M, Workspace ws, Open ox)
+{
+    const int64_t i = gtid();
+    if (i >= 3 * M.F) return;
+    const int64_t e = M.face_edges[i];
+    if (e < 0 || e >= M.E || ws.uses[e] != 1 || !edge_ok(M.edges, e, M.V)) return;
+    const int64_t *t = M.f + 3 * (i / 3);
+    if (!face_ok(t, M.V) || t[0] == t[1] || t[1] == t[2] || t[0] == t[2]) return;
+    const double *p0 = M.p + 3 * t[0];
+    double n0, n1, n2;
+    cross_of(p0, M.p + 3 * t[1], M.p + 3 * t[2], n0, n1, n2);
+    const double len = sqrt((n0 * n0 + n1 * n1) + n2 * n2);
+    if (len == 0.0) return;
+    n0 = n0 / len;
+    n1 = n1 / len;
+    n2 = n2 / len;
+    if (n0 == 0.0 && n1 == 0.0 && n2 == 0.0) return;
+    const double *pa = M.p + 3 * M.edges[2 * e], *pb = M.p + 3 * M.edges[2 * e + 1];
+    const double d0 = pb[0] - pa[0], d1 = pb[1] - pa[1], d2 = pb[2] - pa[2];
+    double m0 = d1 * n2 - d2 * n1;
+    double m1 = d2 * n0 - d0 * n2;
+    double m2 = d0 * n1 - d1 * n0;
+    const double ml = sqrt((m0 * m0 + m1 * m1) + m2 * m2);
+    if (ml == 0.0) return;
+    m0 = m0 / ml;
+    m1 = m1 / ml;
+    m2 = m2 / ml;
+    double *o = ox.eplane + 4 * e;
+    o[0] = m0;
+    o[1] = m1;
+    o[2] = m2;
+    o[3] = -((m0 * pa[0] + m1 * pa[1]) + m2 * pa[2]);
+    atomicAdd(&ox.info->planes, 1ull);
+}
+
+// vertex << 32 | edge for both ends of a boundary edge, else kNone.
+__global__ __launch_bounds__(kBlock) void boundary_key_kernel(Mesh M, Workspace ws)
+{
+    const int64_t e = gtid();
+    if (e >= M.E) return;
+    const bool ok = edge_ok(M.edges, e, M.V);
+    if (!ok) atomicAdd(&ws.info->invalid, 1ull);
+    const bool on = ok && ws.uses[e] == 1;
+    ws.nkey_a[2 * e] = on ? ((uint64_t)M.edges[2 * e] << 32 | (uint64_t)e) : kNone;
+    ws.nkey_a[2 * e + 1] = on ? ((uint64_t)M.edges[2 * e + 1] << 32 | (uint64_t)e) : kNone;
+}
+
+// Q[v] += weight * (m, d)(m, d)^T over the boundary edges of v in ascending edge index.
+__global__ __launch_bounds__(kBlock) void boundary_sum_kernel(int64_t V, Workspace ws, Open ox, double weight, double *Q)
+{
+    const int64_t v = gtid();
+    if (v >= V) return;
+    const int64_t js = ws.nstart[v], je = ws.nend[v];
+    if (js >= je) return;
+    double *o = Q + 10 * v;
+    double q0 = o[0], q1 = o[1], q2 = o[2], q3 = o[3], q4 = o[4], q5 = o[5], q6 = o[6], q7 = o[7], q8 = o[8], q9 = o[9];
+    for (int64_t j = js; j < je; ++j) {
+        const double *p = ox.eplane + 4 * (int64_t)(ws.nkey_b[j] & 0xffffffffu);
+        const double p0 = p[0], p1 = p[1], p2 = p[2], p3 = p[3];
+        if (p0 == 0.0 && p1 == 0.0 && p2 == 0.0) continue;
+        q0 = q0 + weight * (p0 * p0);
+        q1 = q1 + weight * (p0 * p1);
+        q2 = q2 + weight * (p0 * p2);
+        q3 = q3 + weight * (p0 * p3);
+        q4 = q4 + weight * (p1 * p1);
+        q5 = q5 + weight * (p1 * p2);
+        q6 = q6 + weight * (p1 * p3);
+        q7 = q7 + weight * (p2 * p2);
+        q8 = q8 + weight * (p2 * p3);
+        q9 = q9 + weight * (p3 * p3);
+    }
+    o[0] = q0; o[1] = q1; o[2] = q2; o[3] = q3; o[4] = q4;
+    o[5] = q5; o[6] = q6; o[7] = q7; o[8] = q8; o[9] = q9;
+}
+
+__global__ void boundary_counts_kernel(Workspace ws, Open ox, int64_t *counts)
+{
+    counts[0] = (int64_t)ox.info->planes;
+    counts[1] = (int64_t)ws.info->invalid;
+}
+
+// Step 2, per edge: the boundary edges of both ends are counted, the ends of any other edge without two uses flagged.
+__global__ __launch_bounds__(kBlock) void class_edge_kernel(Mesh M, Workspace ws, Open ox)
+{
+    const int64_t e = gtid();
+    if (e >= M.E || ws.nkey_a[2 * e] == kNone) return;
+    const int32_t u = ws.uses[e];
+    if (u == 2) return;
+    const int64_t a = M.edges[2 * e], b = M.edges[2 * e + 1];
+    if (u == 1) {
+        atomicAdd(&ox.nb[a], 1);
+        atomicAdd(&ox.nb[b], 1);
+    } else {
+        ox.bad[a] = 1;
+        ox.bad[b] = 1;
+    }
+}
+
+// Every edge of a face whose three edges are boundary edges (every writer stores the same 1).
+__global__ __launch_bounds__(kBlock) void isolated_kernel(Mesh M, Workspace ws, Open ox)
+{
+    const int64_t f = gtid();
+    if (f >= M.F) return;
+    const int64_t e0 = M.face_edges[3 * f], e1 = M.face_edges[3 * f + 1], e2 = M.face_edges[3 * f + 2];
+    if (e0 < 0 || e0 >= M.E || e1 < 0 || e1 >= M.E || e2 < 0 || e2 >= M.E) return;
+    if (ws.uses[e0] != 1 || ws.uses[e1] != 1 || ws.uses[e2] != 1) return;
+    ox.iso[e0] = 1;
+    ox.iso[e1] = 1;
+    ox.iso[e2] = 1;
+}
+
+__global__ __launch_bounds__(kBlock) void class_vertex_kernel(int64_t V, const uint8_t *vertex_lock, Workspace ws, Open ox)
+{
+    const int64_t v = gtid();
+    if (v >= V) return;
+    const int32_t nb = ox.nb[v];
+    uint8_t c = kLocked;
+    if (!(vertex_lock && vertex_lock[v]) && !ox.bad[v]) c = nb == 0 ? kInterior : nb == 2 ? kBorder : kLocked;
+    ox.cls[v] = c;
+    if (c == kLocked) atomicAdd(&ws.info->locked, 1ull);
+    if (nb == 2 && !ox.bad[v]) atomicAdd(&ox.info->border, 1ull);
+}
+
+// The border end whose position an edge with two uses collapses to, or -1: the edge class that select and apply share.
+__device__ __forceinline__ int64_t pinned_end(const Workspace &ws, const Open &ox, int64_t e, int64_t a, int64_t b)
+{
+    if (ws.uses[e] != 2 || ox.cls[a] == ox.cls[b]) return -1;
+    return ox.cls[a] == kBorder ? a : b;
+}
+
+// Steps 3 to 5 and m1 in collapse mode, one thread per edge.
+__global__ __launch_bounds__(kBlock) void candidate_open_kernel(Mesh M, Workspace ws, Open ox, double max_cost, uint64_t round)
+{
+    const int64_t e = gtid();
+    if (e >= M.E) return;
+    ws.key[e] = kNone;
+    ws.skey_a[e] = kNone;
+    if (ws.nkey_a[2 * e] == kNone) return;
+    const int64_t a = M.edges[2 * e], b = M.edges[2 * e + 1];
+    const uint8_t ca = ox.cls[a], cb = ox.cls[b];
+    if (ca == kLocked || cb == kLocked) return;
+    const int32_t u = ws.uses[e];
+    if (u == 2) {
+        if (ca == kBorder && cb == kBorder) return;        // a chord
+    } else if (u != 1 || ox.iso[e]) {
+        return;
+    }
+    double qe[10], z0, z1, z2, cost;
+    collapse_point(M.p, M.Q, a, b, pinned_end(ws, ox, e, a, b), qe, z0, z1, z2, cost);
+    if (cost > max_cost) return;
+    atomicAdd(&ws.info->candidates, 1ull);
+
+    if (!collapse_legal(M, ws, e, a, b, z0, z1, z2)) return;
+    atomicAdd(&ws.info->legal, 1ull);
+    const uint64_t bits = (uint64_t)__double_as_longlong(cost);
+    const uint64_t key = (bits >> 52) << 52 | (mix((uint64_t)a << 32 | (uint64_t)b, round) & 0x1FFFFFull) << 31 | (uint64_t)e;
+    ws.key[e] = key;
+    ws.skey_a[e] = bits;
+    atomicMin((unsigned long long *)&ws.m1[a], (unsigned long long)key);
+    atomicMin((unsigned long long *)&ws.m1[b], (unsigned long long)key);
+}
+
+// Step 7: the faces the i-th edge of the sorted selection removes.
+__global__ __launch_bounds__(kBlock) void weight_kernel(int64_t E, Workspace ws, Open ox)
+{
+    const int64_t i = gtid();
+    if (i >= E) return;
+    ox.weight[i] = ws.skey_b[i] == kNone ? 0 : ws.uses[ws.sval_b[i]];
+}
+
+__device__ __forceinline__ bool taken_at(const Workspace &ws, const Open &ox, int64_t i, int64_t faces_to_remove)
+{
+    return ws.skey_b[i] != kNone && (int64_t)ox.before[i] < faces_to_remove;
+}
+
+__global__ __launch_bounds__(kBlock) void budget_kernel(int64_t E, int64_t faces_to_remove, Workspace ws, Open ox)
+{
+    const int64_t i = gtid();
+    if (i >= E || !taken_at(ws, ox, i, faces_to_remove)) return;
+    atomicAdd(&ox.info->taken, 1ull);
+    if (ox.weight[i] == 1) atomicAdd(&ox.info->boundary_taken, 1ull);
+}
+
+__global__ void open_counts_kernel(Workspace ws, Open ox, int64_t *counts)
+{
+    counts[0] = (int64_t)ws.info->candidates;
+    counts[1] = (int64_t)ws.info->legal;
+    counts[2] = (int64_t)ws.info->selected;
+    counts[3] = (int64_t)ox.info->taken;
+    counts[4] = (int64_t)ws.info->locked;
+    counts[5] = (int64_t)ws.info->invalid;
+    counts[6] = (int64_t)ox.info->boundary_taken;
+    counts[7] = (int64_t)ox.info->border;
+}
+
+// Step 8 in collapse mode: as apply_kernel, with the edge class select saw.
+__global__ __launch_bounds__(kBlock) void apply_open_kernel(double *p, double *Q, const int64_t *edges, int64_t E, int64_t V,
+                                                            int64_t n, int64_t faces_to_remove, Workspace ws, Open ox)
+{
+    const int64_t i = gtid();
+    if (i >= n || !taken_at(ws, ox, i, faces_to_remove)) return;
+    const int64_t e = ws.sval_b[i];
+    if (e < 0 || e >= E || !edge_ok(edges, e, V)) return;      // a workspace that select did not fill
+    const int64_t a = edges[2 * e], b = edges[2 * e + 1];
+    double qe[10], z0, z1, z2, cost;
+    collapse_point(p, Q, a, b, pinned_end(ws, ox, e, a, b), qe, z0, z1, z2, cost);
+    p[3 * a] = z0;
+    p[3 * a + 1] = z1;
+    p[3 * a + 2] = z2;
+    double *qa = Q + 10 * a;
+#pragma unroll
+    for (int k = 0; k < 10; ++k) qa[k] = qe[k];
+    ws.remap[b] = (int32_t)a;
 }
 
 __global__ __launch_bounds__(kBlock) void gather_vertex_kernel(const double *Q, const uint8_t *lock, const int64_t *vertex_map,
@@ -675,6 +987,188 @@ extern "C" int qf_mesh_collapse_gather(const double *quadrics, const uint8_t *ve
     if (n_targets > 0) {
         hipLaunchKernelGGL(target_kernel, dim3(blocks(n_targets)), dim3(kBlock), 0, s, vertex_target, n_targets, n_vertices,
                            inverse);
+        QF_LAUNCH_CHECK();
+    }
+    return QF_OK;
+}
+
+// ---- boundary = collapse: entry points -----------------------------------------------------------------------------------
+
+namespace {
+
+struct OpenSpace {
+    Workspace ws;
+    Open ox;
+};
+
+// 0 for a rocPRIM size query that failed.
+int64_t carve_both(void *base, int64_t V, int64_t F, int64_t E, hipStream_t s, OpenSpace &out)
+{
+    const size_t temp = temp_bytes_for(F, E, s);
+    const size_t scan = scan_bytes_for(E, s);
+    if (temp == 0 || scan == 0) return 0;
+    out.ws = carve(base, V, F, E, temp);
+    out.ox = carve_open(base, out.ws.bytes, V, E, scan);
+    return out.ox.bytes;
+}
+
+}  // namespace
+
+extern "C" int64_t qf_mesh_decimate_open_workspace_bytes(int64_t n_vertices, int64_t n_faces, int64_t n_edges)
+{
+    if (!sizes_ok(n_vertices, n_faces, n_edges)) return -1;
+    OpenSpace sp;
+    const int64_t bytes = carve_both(nullptr, n_vertices, n_faces, n_edges, nullptr, sp);
+    return bytes > 0 ? bytes : -1;
+}
+
+extern "C" int qf_mesh_boundary_quadrics(const double *vertices, int64_t n_vertices, const int64_t *faces, int64_t n_faces,
+                                         const int64_t *edges, int64_t n_edges, const int64_t *face_edges, double *quadrics,
+                                         double boundary_weight, void *workspace, int64_t workspace_bytes, int64_t *counts,
+                                         void *stream)
+{
+    if (!sizes_ok(n_vertices, n_faces, n_edges) || !vertices || (n_faces > 0 && (!faces || !face_edges)) ||
+        (n_edges > 0 && !edges) || !quadrics || !workspace || !counts || !(boundary_weight >= 0.0) || std::isinf(boundary_weight))
+        return QF_ERR_INVALID_ARGUMENT;
+    hipStream_t s = qf_stream(stream);
+    OpenSpace sp;
+    const int64_t need = carve_both(workspace, n_vertices, n_faces, n_edges, s, sp);
+    if (need == 0) return QF_ERR_HIP;
+    if (workspace_bytes < need) return QF_ERR_INVALID_ARGUMENT;
+    Workspace &ws = sp.ws;
+    Open &ox = sp.ox;
+    const Mesh M{vertices, faces, edges, face_edges, quadrics, n_vertices, n_faces, n_edges};
+    const int64_t V = M.V, F = M.F, E = M.E;
+
+    QF_HIP_TRY(hipMemsetAsync(ws.info, 0, sizeof(Info), s));
+    QF_HIP_TRY(hipMemsetAsync(ox.info, 0, sizeof(OpenInfo), s));
+    if (E > 0) {
+        QF_HIP_TRY(hipMemsetAsync(ws.nstart, 0, 8 * (size_t)V, s));
+        QF_HIP_TRY(hipMemsetAsync(ws.nend, 0, 8 * (size_t)V, s));
+        QF_HIP_TRY(hipMemsetAsync(ws.uses, 0, 4 * (size_t)E, s));
+        QF_HIP_TRY(hipMemsetAsync(ox.eplane, 0, 32 * (size_t)E, s));
+        if (F > 0) {
+            hipLaunchKernelGGL(uses_kernel, dim3(blocks(3 * F)), dim3(kBlock), 0, s, M, ws);
+            QF_LAUNCH_CHECK();
+            hipLaunchKernelGGL(boundary_plane_kernel, dim3(blocks(3 * F)), dim3(kBlock), 0, s, M, ws, ox);
+            QF_LAUNCH_CHECK();
+        }
+        hipLaunchKernelGGL(boundary_key_kernel, dim3(blocks(E)), dim3(kBlock), 0, s, M, ws);
+        QF_LAUNCH_CHECK();
+        size_t tb = ws.temp_bytes;
+        QF_HIP_TRY(rocprim::radix_sort_keys(ws.temp, tb, ws.nkey_a, ws.nkey_b, (size_t)(2 * E), 0, 64, s));
+        hipLaunchKernelGGL(range_kernel, dim3(blocks(2 * E)), dim3(kBlock), 0, s, ws.nkey_b, 2 * E, ws.nstart, ws.nend);
+        QF_LAUNCH_CHECK();
+        hipLaunchKernelGGL(boundary_sum_kernel, dim3(blocks(V)), dim3(kBlock), 0, s, V, ws, ox, boundary_weight, quadrics);
+        QF_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(boundary_counts_kernel, dim3(1), dim3(1), 0, s, ws, ox, counts);
+    QF_LAUNCH_CHECK();
+    return QF_OK;
+}
+
+extern "C" int qf_mesh_collapse_select_open(const double *vertices, int64_t n_vertices, const int64_t *faces, int64_t n_faces,
+                                            const int64_t *edges, int64_t n_edges, const int64_t *face_edges,
+                                            const double *quadrics, const uint8_t *vertex_lock, double max_cost,
+                                            int64_t round, int64_t faces_to_remove, void *workspace, int64_t workspace_bytes,
+                                            int64_t *counts, void *stream)
+{
+    if (!sizes_ok(n_vertices, n_faces, n_edges) || !vertices || (n_faces > 0 && (!faces || !face_edges)) ||
+        (n_edges > 0 && !edges) || !quadrics || !workspace || !counts || !(max_cost >= 0.0) || round < 0 ||
+        faces_to_remove < 0)
+        return QF_ERR_INVALID_ARGUMENT;
+    hipStream_t s = qf_stream(stream);
+    OpenSpace sp;
+    const int64_t need = carve_both(workspace, n_vertices, n_faces, n_edges, s, sp);
+    if (need == 0) return QF_ERR_HIP;
+    if (workspace_bytes < need) return QF_ERR_INVALID_ARGUMENT;
+    Workspace &ws = sp.ws;
+    Open &ox = sp.ox;
+    const Mesh M{vertices, faces, edges, face_edges, quadrics, n_vertices, n_faces, n_edges};
+    const int64_t V = M.V, F = M.F, E = M.E;
+
+    QF_HIP_TRY(hipMemsetAsync(ws.info, 0, sizeof(Info), s));
+    QF_HIP_TRY(hipMemsetAsync(ox.info, 0, sizeof(OpenInfo), s));
+    QF_HIP_TRY(hipMemsetAsync(ws.nstart, 0, 8 * (size_t)V, s));
+    QF_HIP_TRY(hipMemsetAsync(ws.nend, 0, 8 * (size_t)V, s));
+    QF_HIP_TRY(hipMemsetAsync(ws.m1, 0xff, 8 * (size_t)V, s));
+    QF_HIP_TRY(hipMemsetAsync(ox.nb, 0, 4 * (size_t)V, s));
+    QF_HIP_TRY(hipMemsetAsync(ox.bad, 0, (size_t)V, s));
+    const int st = build_face_rows(M, ws, s);
+    if (st != QF_OK) return st;
+    if (E > 0) {
+        QF_HIP_TRY(hipMemsetAsync(ws.uses, 0, 4 * (size_t)E, s));
+        QF_HIP_TRY(hipMemsetAsync(ox.iso, 0, (size_t)E, s));
+        hipLaunchKernelGGL(edge_key_kernel, dim3(blocks(E)), dim3(kBlock), 0, s, M, ws);
+        QF_LAUNCH_CHECK();
+        size_t tb = ws.temp_bytes;
+        QF_HIP_TRY(rocprim::radix_sort_keys(ws.temp, tb, ws.nkey_a, ws.nkey_b, (size_t)(2 * E), 0, 64, s));
+        hipLaunchKernelGGL(range_kernel, dim3(blocks(2 * E)), dim3(kBlock), 0, s, ws.nkey_b, 2 * E, ws.nstart, ws.nend);
+        QF_LAUNCH_CHECK();
+        if (F > 0) {
+            hipLaunchKernelGGL(uses_kernel, dim3(blocks(3 * F)), dim3(kBlock), 0, s, M, ws);
+            QF_LAUNCH_CHECK();
+            hipLaunchKernelGGL(isolated_kernel, dim3(blocks(F)), dim3(kBlock), 0, s, M, ws, ox);
+            QF_LAUNCH_CHECK();
+        }
+        hipLaunchKernelGGL(class_edge_kernel, dim3(blocks(E)), dim3(kBlock), 0, s, M, ws, ox);
+        QF_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(class_vertex_kernel, dim3(blocks(V)), dim3(kBlock), 0, s, V, vertex_lock, ws, ox);
+    QF_LAUNCH_CHECK();
+    if (E > 0) {
+        hipLaunchKernelGGL(candidate_open_kernel, dim3(blocks(E)), dim3(kBlock), 0, s, M, ws, ox, max_cost, (uint64_t)round);
+        QF_LAUNCH_CHECK();
+        hipLaunchKernelGGL(min2_kernel, dim3(blocks(V)), dim3(kBlock), 0, s, V, ws);
+        QF_LAUNCH_CHECK();
+        hipLaunchKernelGGL(select_kernel, dim3(blocks(E)), dim3(kBlock), 0, s, M, ws);
+        QF_LAUNCH_CHECK();
+        size_t tb = ws.temp_bytes;
+        QF_HIP_TRY(rocprim::radix_sort_pairs(ws.temp, tb, ws.skey_a, ws.skey_b, ws.sval_a, ws.sval_b, (size_t)E, 0, 64, s));
+        hipLaunchKernelGGL(weight_kernel, dim3(blocks(E)), dim3(kBlock), 0, s, E, ws, ox);
+        QF_LAUNCH_CHECK();
+        size_t sb = ox.temp_bytes;
+        QF_HIP_TRY(rocprim::exclusive_scan(ox.temp, sb, ox.weight, ox.before, (int32_t)0, (size_t)E, rocprim::plus<int32_t>(), s));
+        hipLaunchKernelGGL(budget_kernel, dim3(blocks(E)), dim3(kBlock), 0, s, E, faces_to_remove, ws, ox);
+        QF_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(open_counts_kernel, dim3(1), dim3(1), 0, s, ws, ox, counts);
+    QF_LAUNCH_CHECK();
+    return QF_OK;
+}
+
+extern "C" int qf_mesh_collapse_apply_open(double *vertices, int64_t n_vertices, int64_t *faces, int64_t n_faces,
+                                           const int64_t *edges, int64_t n_edges, double *quadrics, int64_t faces_to_remove,
+                                           int64_t *vertex_target, int64_t n_targets, void *workspace,
+                                           int64_t workspace_bytes, void *stream)
+{
+    if (!sizes_ok(n_vertices, n_faces, n_edges) || !vertices || (n_faces > 0 && !faces) || (n_edges > 0 && !edges) ||
+        !quadrics || !workspace || faces_to_remove < 0 || n_targets < 0 || n_targets >= kMaxCount ||
+        (n_targets > 0 && !vertex_target))
+        return QF_ERR_INVALID_ARGUMENT;
+    hipStream_t s = qf_stream(stream);
+    OpenSpace sp;
+    const int64_t need = carve_both(workspace, n_vertices, n_faces, n_edges, s, sp);
+    if (need == 0) return QF_ERR_HIP;
+    if (workspace_bytes < need) return QF_ERR_INVALID_ARGUMENT;
+    Workspace &ws = sp.ws;
+
+    QF_HIP_TRY(hipMemsetAsync(ws.remap, 0xff, 4 * (size_t)n_vertices, s));
+    // every taken edge removes at least one face, so no more than faces_to_remove are taken
+    const int64_t n = faces_to_remove < n_edges ? faces_to_remove : n_edges;
+    if (n > 0) {
+        hipLaunchKernelGGL(apply_open_kernel, dim3(blocks(n)), dim3(kBlock), 0, s, vertices, quadrics, edges, n_edges, n_vertices,
+                           n, faces_to_remove, ws, sp.ox);
+        QF_LAUNCH_CHECK();
+    }
+    if (n_faces > 0) {
+        hipLaunchKernelGGL(remap_kernel, dim3(blocks(3 * n_faces)), dim3(kBlock), 0, s, faces, 3 * n_faces, n_vertices,
+                           ws.remap);
+        QF_LAUNCH_CHECK();
+    }
+    if (n_targets > 0) {
+        hipLaunchKernelGGL(remap_kernel, dim3(blocks(n_targets)), dim3(kBlock), 0, s, vertex_target, n_targets, n_vertices,
+                           ws.remap);
         QF_LAUNCH_CHECK();
     }
     return QF_OK;

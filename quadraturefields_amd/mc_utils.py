@@ -640,8 +640,21 @@ DECIMATE_STOP_TARGET, DECIMATE_STOP_NO_EDGE, DECIMATE_STOP_MAX_ROUNDS = ("target
                                                                           "max_rounds reached")
 
 
+DECIMATE_BOUNDARY_MODES = ("lock", "collapse")
+
+
+def _boundary_options(boundary, boundary_weight):
+    if boundary not in DECIMATE_BOUNDARY_MODES:
+        raise ValueError(f"boundary must be one of {DECIMATE_BOUNDARY_MODES}, got {boundary!r}")
+    weight = float(boundary_weight)
+    if not (weight >= 0.0 and math.isfinite(weight)):
+        raise ValueError(f"boundary_weight must be finite and >= 0, got {boundary_weight}")
+    return boundary == "collapse", weight
+
+
 def decimate_mesh_device(vertices: torch.Tensor, faces: torch.Tensor, target_faces: int, *, max_cost=None,
-                         vertex_lock=None, max_rounds: int = 128, return_stats: bool = False) -> DecimatedMesh:
+                         vertex_lock=None, max_rounds: int = 128, return_stats: bool = False, boundary: str = "lock",
+                         boundary_weight: float = 1.0) -> DecimatedMesh:
     """Bring a mesh down to ``target_faces`` faces on the device by rounds of independent quadric edge collapses, under
     the rules of DESIGN.md section 3.9d (this project's own; parity with the reference's ``fast_simplification`` is
     unpinned).  Per round: the edges are numbered, every edge whose ends are neither locked nor on a boundary or
@@ -657,7 +670,16 @@ def decimate_mesh_device(vertices: torch.Tensor, faces: torch.Tensor, target_fac
     ``candidates``, ``legal``, ``selected``, ``taken``, and ``stop`` (one of the ``DECIMATE_STOP_*`` strings); else None.
     ``target_faces >= F`` returns copies of the input, bit for bit.  Two host waits per round, for the edge count and for
     the compaction's counts (the round's own counts come with the latter).  Raises ValueError for host tensors, bad
-    shapes and, with their number, faces that index outside [0, V) and vertices that are not finite."""
+    shapes and, with their number, faces that index outside [0, V) and vertices that are not finite.
+
+    ``boundary="lock"`` (the default) keeps every vertex on a boundary or non-manifold edge.  ``boundary="collapse"``
+    (include/qf_mesh_decimate_open.h) lets an open mesh reach its target: every boundary edge adds a plane through itself,
+    perpendicular to its face, to the quadrics of its ends with weight ``boundary_weight`` (finite, >= 0; 1.0 counts a
+    boundary edge like one face), boundary edges collapse along the border, interior vertices collapse onto border
+    vertices, and the budget counts the one face a boundary collapse removes.  Bow-tie and non-manifold vertices stay
+    locked.  The stats then gain the per-round list ``boundary_taken``; on a closed mesh the result is ``"lock"``'s, bit
+    for bit."""
+    collapse_mode, weight = _boundary_options(boundary, boundary_weight)
     if not isinstance(vertices, torch.Tensor):
         raise TypeError("vertices and faces must be torch.Tensors")
     f = _device_faces(faces, "decimate_mesh_device")
@@ -685,14 +707,20 @@ def decimate_mesh_device(vertices: torch.Tensor, faces: torch.Tensor, target_fac
     face_map = torch.arange(n_f0, dtype=torch.int64, device=dev)
     vertex_target = torch.arange(n_v0, dtype=torch.int64, device=dev)
     stats = {"rounds": 0, "faces": [], "candidates": [], "legal": [], "selected": [], "taken": [], "stop": None}
+    count_names = _C.MESH_COLLAPSE_OPEN_COUNTS if collapse_mode else _C.MESH_COLLAPSE_COUNTS
+    stat_names = ("candidates", "legal", "selected", "taken")
+    if collapse_mode:
+        stats["boundary_taken"] = []
+        stat_names += ("boundary_taken",)
     lib = _C.lib()
     flags = _C.MESH_REMOVE_DEGENERATE | _C.MESH_REMOVE_UNREFERENCED
     quadrics = None
+    ws_name = "qf_mesh_decimate_open_workspace_bytes" if collapse_mode else "qf_mesh_decimate_workspace_bytes"
 
     def workspace(n_v, n_f, n_e):
-        n = int(lib.qf_mesh_decimate_workspace_bytes(n_v, n_f, n_e))
+        n = int(getattr(lib, ws_name)(n_v, n_f, n_e))
         if n < 0:
-            raise RuntimeError(f"qf_mesh_decimate_workspace_bytes refused V={n_v}, F={n_f}, E={n_e}")
+            raise RuntimeError(f"{ws_name} refused V={n_v}, F={n_f}, E={n_e}")
         return torch.empty((n,), dtype=torch.uint8, device=dev), n
 
     with torch.cuda.device(dev):
@@ -716,19 +744,35 @@ def decimate_mesh_device(vertices: torch.Tensor, faces: torch.Tensor, target_fac
                 n_bad = quadric_counts.tolist()[0]                        # the stream has drained: no further wait
                 if n_bad:
                     raise ValueError(f"{n_bad} vertices are not finite")
+                if collapse_mode:
+                    ws, ws_bytes = workspace(n_v, n_f, edges.shape[0])
+                    boundary_counts = torch.empty((len(_C.MESH_BOUNDARY_COUNTS),), dtype=torch.int64, device=dev)
+                    _C.check(lib.qf_mesh_boundary_quadrics(_C.ptr(v), n_v, _C.ptr(f), n_f, _C.ptr(edges), edges.shape[0],
+                                                           _C.ptr(face_edges), _C.ptr(quadrics), weight, _C.ptr(ws),
+                                                           ws_bytes, _C.ptr(boundary_counts), _C.stream()),
+                             "qf_mesh_boundary_quadrics")
             else:
                 edges, face_edges, _ = mesh_edges_device(f, n_v)
             n_e = edges.shape[0]
             max_take = (n_f - target + 1) // 2
             ws, ws_bytes = workspace(n_v, n_f, n_e)
-            counts = torch.empty((len(_C.MESH_COLLAPSE_COUNTS),), dtype=torch.int64, device=dev)
-            _C.check(lib.qf_mesh_collapse_select(_C.ptr(v), n_v, _C.ptr(f), n_f, _C.ptr(edges), n_e, _C.ptr(face_edges),
-                                                 _C.ptr(quadrics), _C.ptr(lock), cost_cap, stats["rounds"], max_take,
-                                                 _C.ptr(ws), ws_bytes, _C.ptr(counts), _C.stream()),
-                     "qf_mesh_collapse_select")
-            _C.check(lib.qf_mesh_collapse_apply(_C.ptr(v), n_v, _C.ptr(f), n_f, _C.ptr(edges), n_e, _C.ptr(quadrics),
-                                                max_take, _C.ptr(vertex_target), n_v0, _C.ptr(ws), ws_bytes, _C.stream()),
-                     "qf_mesh_collapse_apply")
+            counts = torch.empty((len(count_names),), dtype=torch.int64, device=dev)
+            if collapse_mode:
+                _C.check(lib.qf_mesh_collapse_select_open(_C.ptr(v), n_v, _C.ptr(f), n_f, _C.ptr(edges), n_e,
+                                                          _C.ptr(face_edges), _C.ptr(quadrics), _C.ptr(lock), cost_cap,
+                                                          stats["rounds"], n_f - target, _C.ptr(ws), ws_bytes,
+                                                          _C.ptr(counts), _C.stream()), "qf_mesh_collapse_select_open")
+                _C.check(lib.qf_mesh_collapse_apply_open(_C.ptr(v), n_v, _C.ptr(f), n_f, _C.ptr(edges), n_e,
+                                                         _C.ptr(quadrics), n_f - target, _C.ptr(vertex_target), n_v0,
+                                                         _C.ptr(ws), ws_bytes, _C.stream()), "qf_mesh_collapse_apply_open")
+            else:
+                _C.check(lib.qf_mesh_collapse_select(_C.ptr(v), n_v, _C.ptr(f), n_f, _C.ptr(edges), n_e, _C.ptr(face_edges),
+                                                     _C.ptr(quadrics), _C.ptr(lock), cost_cap, stats["rounds"], max_take,
+                                                     _C.ptr(ws), ws_bytes, _C.ptr(counts), _C.stream()),
+                         "qf_mesh_collapse_select")
+                _C.check(lib.qf_mesh_collapse_apply(_C.ptr(v), n_v, _C.ptr(f), n_f, _C.ptr(edges), n_e, _C.ptr(quadrics),
+                                                    max_take, _C.ptr(vertex_target), n_v0, _C.ptr(ws), ws_bytes,
+                                                    _C.stream()), "qf_mesh_collapse_apply")
             c_bytes = int(lib.qf_mesh_compact_workspace_bytes(n_v, n_f))
             if c_bytes < 0:
                 raise RuntimeError(f"qf_mesh_compact_workspace_bytes refused V={n_v}, F={n_f}")
@@ -738,9 +782,9 @@ def decimate_mesh_device(vertices: torch.Tensor, faces: torch.Tensor, target_fac
             _C.check(lib.qf_mesh_compact_count(*c_args, _C.ptr(c_counts), _C.stream()), "qf_mesh_compact_count")
             both = torch.cat([c_counts, counts]).tolist()                 # the round's second host wait
             compacted = dict(zip(_C.MESH_COMPACT_COUNTS, both))
-            collapse = dict(zip(_C.MESH_COLLAPSE_COUNTS, both[len(_C.MESH_COMPACT_COUNTS):]))
+            collapse = dict(zip(count_names, both[len(_C.MESH_COMPACT_COUNTS):]))
             stats["rounds"] += 1
-            for name in ("candidates", "legal", "selected", "taken"):
+            for name in stat_names:
                 stats[name].append(collapse[name])
             if collapse["taken"] == 0:
                 stats["faces"].append(n_f)
@@ -766,14 +810,17 @@ def decimate_mesh_device(vertices: torch.Tensor, faces: torch.Tensor, target_fac
 
 
 def decimate_mesh(mesh: TriMesh, target_faces: int, *, max_cost=None, vertex_lock=None, max_rounds: int = 128,
-                  return_stats: bool = False, device="cuda"):
+                  return_stats: bool = False, device="cuda", boundary: str = "lock", boundary_weight: float = 1.0):
     """``decimate_mesh_device`` on a ``TriMesh``: ``(TriMesh, face_map, vertex_target)`` with numpy int64 maps (and the
     stats dict fourth with ``return_stats``).  An output vertex takes the per-vertex ``visual.uv`` of the input vertex
-    with the lowest index among those that ended in it: the end a collapse keeps."""
+    with the lowest index among those that ended in it: the end a collapse keeps.  ``boundary`` and ``boundary_weight`` are
+    ``decimate_mesh_device``'s."""
+    _boundary_options(boundary, boundary_weight)
     dev = _C.resolve_device(device)
     out = decimate_mesh_device(torch.from_numpy(np.asarray(mesh.vertices, np.float64)).to(dev),
                                torch.from_numpy(np.asarray(mesh.faces, np.int64)).to(dev), target_faces,
-                               max_cost=max_cost, vertex_lock=vertex_lock, max_rounds=max_rounds, return_stats=True)
+                               max_cost=max_cost, vertex_lock=vertex_lock, max_rounds=max_rounds, return_stats=True,
+                               boundary=boundary, boundary_weight=boundary_weight)
     vertex_target = out.vertex_target.cpu().numpy()
     uv = None
     if mesh.visual.uv is not None:
@@ -784,25 +831,26 @@ def decimate_mesh(mesh: TriMesh, target_faces: int, *, max_cost=None, vertex_loc
     return res + (out.stats,) if return_stats else res
 
 
-def down_sample_quadraic(mesh: TriMesh, agg=None, verbose: bool = False, device="cuda") -> TriMesh:
+def down_sample_quadraic(mesh: TriMesh, agg=None, verbose: bool = False, device="cuda", boundary: str = "lock") -> TriMesh:
     """The reference's ``down_sample_quadraic`` (examples/mc_utils.py:214-219) on the device: the mesh decimated to
     ``F // 10`` faces by ``decimate_mesh``.  The reference calls ``fast_simplification.simplify``; this is the project's
     own rule and parity with it is unpinned.  ``agg``, fast_simplification's aggressiveness, has
-    no counterpart and is unused."""
-    out, _, _, stats = decimate_mesh(mesh, mesh.faces.shape[0] // 10, return_stats=True, device=device)
+    no counterpart and is unused.  ``boundary="collapse"`` lets an open mesh get there (``decimate_mesh_device``)."""
+    out, _, _, stats = decimate_mesh(mesh, mesh.faces.shape[0] // 10, return_stats=True, device=device, boundary=boundary)
     if verbose:
         print(f"decimated {mesh.faces.shape[0]} -> {out.faces.shape[0]} faces in {stats['rounds']} rounds ({stats['stop']})")
     return out
 
 
 def clean_mesh(mesh: TriMesh, agg=None, remove_duplicate_faces: bool = False, remove_non_manifold_edges: bool = False,
-               verbose: bool = False, device="cuda") -> TriMesh:
+               verbose: bool = False, device="cuda", boundary: str = "lock") -> TriMesh:
     """The reference's ``clean_mesh`` (examples/mc_utils.py:222-242) on the device.  ``remove_duplicate_faces`` goes
     through ``compact_mesh`` (every vertex kept, as trimesh's call leaves them); decimation to ``F // 10`` runs iff
     ``agg > 0`` (``agg=None`` skips it; the reference would raise) -- ``agg``'s value is otherwise unused, since
     fast_simplification's aggressiveness has no counterpart in DESIGN.md section 3.9d's rule, and parity with
     fast_simplification is unpinned.  ``remove_non_manifold_edges=True`` (open3d's removal) is not built and raises
-    NotImplementedError, before any work."""
+    NotImplementedError, before any work.  ``boundary`` is ``down_sample_quadraic``'s."""
+    _boundary_options(boundary, 1.0)
     if remove_non_manifold_edges:
         raise NotImplementedError("remove_non_manifold_edges (open3d's removal) is not built: DESIGN.md section 3.9d")
     if remove_duplicate_faces:
@@ -810,5 +858,5 @@ def clean_mesh(mesh: TriMesh, agg=None, remove_duplicate_faces: bool = False, re
         if verbose:
             print(f"after removing duplicate faces: {mesh.faces.shape[0]} faces")
     if agg is not None and agg > 0:
-        mesh = down_sample_quadraic(mesh, agg, verbose=verbose, device=device)
+        mesh = down_sample_quadraic(mesh, agg, verbose=verbose, device=device, boundary=boundary)
     return mesh
