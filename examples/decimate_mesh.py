@@ -2,13 +2,17 @@
 rules are this project's own, parity with the reference's fast_simplification is unpinned).
 
     python examples/decimate_mesh.py IN.ply OUT.ply (--target_faces N | --ratio R) [--max_cost C] [--max_rounds K]
-                                                [--boundary {lock,collapse}] [--boundary_weight W]
+                                                [--boundary {lock,collapse}] [--boundary_weight W] [--make_manifold]
 
 Writes OUT.ply and, beside it, ``face_map.npy`` (the source face of every output face) and ``vertex_target.npy`` (the
 output vertex every input vertex ended in, -1 if it was dropped), and prints the stats as one JSON line.  With the default
 ``--boundary lock`` boundary and non-manifold edges are never collapsed, so an open mesh keeps its border and the fine
 triangles along it; ``--boundary collapse`` adds boundary quadrics (weight ``--boundary_weight``) and collapses along the
-border too, so an open mesh reaches its target.  Non-manifold edges are never collapsed."""
+border too, so an open mesh reaches its target.  Non-manifold edges are never collapsed, and bow-tie vertices never move:
+``--make_manifold`` first cuts the mesh along its non-manifold edges and splits every vertex into one copy per fan
+(no face is dropped, no coordinate changes), decimates the cut mesh and also writes
+``cut_vertex_map.npy`` (the input vertex of every vertex of the cut mesh); ``vertex_target.npy`` then refers to the cut
+mesh's vertices, and the JSON line gains ``cut_vertices_added``, ``cut_split_vertices`` and ``cut_complex_edges``."""
 import argparse
 import json
 import os
@@ -31,6 +35,8 @@ def main(argv=None):
     ap.add_argument("--boundary", choices=("lock", "collapse"), default="lock")
     ap.add_argument("--boundary_weight", type=float, default=1.0,
                     help="weight of a boundary edge's plane in the quadrics of its ends (collapse mode)")
+    ap.add_argument("--make_manifold", action="store_true",
+                    help="cut non-manifold edges and split bow-tie vertices first (writes cut_vertex_map.npy)")
     ap.add_argument("--device", default="cuda")
     args = ap.parse_args(argv)
     from quadraturefields_amd import mc_utils
@@ -40,6 +46,11 @@ def main(argv=None):
     if args.ratio is not None and not 0.0 <= args.ratio <= 1.0:
         ap.error("--ratio must lie in [0, 1]")
     target = args.target_faces if args.target_faces is not None else int(args.ratio * n_f)
+    n_v, cut = int(mesh.vertices.shape[0]), {}
+    if args.make_manifold:
+        mesh, cut_vertex_map, cut_stats = mc_utils.make_manifold(mesh, device=args.device, return_stats=True)
+        cut = dict(cut_vertices_added=cut_stats["vertices"] - n_v, cut_split_vertices=cut_stats["split_vertices"],
+                   cut_complex_edges=cut_stats["complex_edges"])
     out, face_map, vertex_target, stats = mc_utils.decimate_mesh(mesh, target, max_cost=args.max_cost,
                                                                  max_rounds=args.max_rounds, return_stats=True,
                                                                  device=args.device, boundary=args.boundary,
@@ -48,8 +59,10 @@ def main(argv=None):
     folder = os.path.dirname(os.path.abspath(args.mesh_out))
     np.save(os.path.join(folder, "face_map.npy"), face_map)
     np.save(os.path.join(folder, "vertex_target.npy"), vertex_target)
-    print(json.dumps(dict(stats, boundary=args.boundary, boundary_weight=args.boundary_weight, faces_in=n_f, vertices_in=int(mesh.vertices.shape[0]), target_faces=target,
-                          faces_out=int(out.faces.shape[0]), vertices_out=int(out.vertices.shape[0]))))
+    if args.make_manifold:
+        np.save(os.path.join(folder, "cut_vertex_map.npy"), cut_vertex_map)
+    print(json.dumps(dict(stats, boundary=args.boundary, boundary_weight=args.boundary_weight, faces_in=n_f, vertices_in=n_v, target_faces=target,
+                          faces_out=int(out.faces.shape[0]), vertices_out=int(out.vertices.shape[0]), **cut)))
 
 
 if __name__ == "__main__":

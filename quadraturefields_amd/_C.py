@@ -318,6 +318,16 @@ _MESH_DECIMATE_OPEN_SIGNATURES = {
                                             _P]),
 }
 
+# include/qf_mesh_manifold.h: the cut along complex edges and the split of every vertex into one copy per fan (DESIGN.md
+# section 3.9e), additive in the same way
+MESH_MANIFOLD_COUNTS = ("vertices", "split_vertices", "complex_edges", "complex_faces", "boundary_edges",
+                        "same_direction_edges", "degenerate_faces", "invalid_faces")
+_MESH_MANIFOLD_SIGNATURES = {
+    "qf_mesh_manifold_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64]),
+    "qf_mesh_manifold_count": (c_int, [_P, c_int64, c_int64, _P, c_int64, _P, c_int64, _P, _P]),
+    "qf_mesh_manifold_emit": (c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, c_int64, _P, _P, _P]),
+}
+
 
 def vertex_row_stride(n_lobes: int) -> int:
     """Floats per row of a vertex table: the width 3 + 7L + 1 rounded up to a 64-byte line (16 / 32 / 48 / 64 for
@@ -341,7 +351,8 @@ def lib() -> ctypes.CDLL:
                                           + list(_MESH_COMPACT_SIGNATURES.items())
                                           + list(_MESH_SUBDIVIDE_SIGNATURES.items())
                                           + list(_MESH_DECIMATE_SIGNATURES.items())
-                                          + list(_MESH_DECIMATE_OPEN_SIGNATURES.items())):
+                                          + list(_MESH_DECIMATE_OPEN_SIGNATURES.items())
+                                          + list(_MESH_MANIFOLD_SIGNATURES.items())):
             fn = getattr(handle, name)   # AttributeError if the symbol is not exported
             fn.restype = restype
             fn.argtypes = argtypes

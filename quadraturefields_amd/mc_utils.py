@@ -831,6 +831,82 @@ def decimate_mesh(mesh: TriMesh, target_faces: int, *, max_cost=None, vertex_loc
     return res + (out.stats,) if return_stats else res
 
 
+# ---- manifold repair (include/qf_mesh_manifold.h) --------------------------------------------------
+
+ManifoldMesh = namedtuple("ManifoldMesh", ["vertices", "faces", "vertex_map", "stats"])
+
+
+def make_manifold_device(vertices: torch.Tensor, faces: torch.Tensor, *, return_stats: bool = False) -> ManifoldMesh:
+    """Make a mesh a manifold with boundary on the device, losslessly, under the rule of DESIGN.md section 3.9e (this
+    project's own; it is not open3d's ``remove_non_manifold_edges``, which drops faces): the mesh is cut along every edge
+    with three or more faces and every vertex is split into one copy per fan of faces.  No face is dropped, none moves
+    and no coordinate changes: ``out.vertices[out.faces]`` equals ``vertices[faces]`` bit for bit, so every rendered frame
+    is unchanged, while every edge of the result has at most two faces and every vertex one fan -- the meshes
+    ``decimate_mesh_device(boundary="collapse")`` gets through.  ``vertices``: device float [V,3] (fp32 is widened
+    exactly), ``faces``: device int64 or int32 [F,3].  Returns ``ManifoldMesh(vertices fp64 [V',3], faces int64 [F,3],
+    vertex_map int64 [V'], stats)``: the first V rows are the input's, ``vertex_map`` names the source vertex of every
+    row (``baking.remap_vertex_features(table, vertex_map)`` carries a vertex-baked table along, with repeated rows; a
+    quantised table is refused there as ever).  With ``return_stats`` ``stats`` is a dict of the eight counts
+    (``_C.MESH_MANIFOLD_COUNTS``), else None.  A mesh that is already manifold comes back as itself.  Duplicate faces
+    put three or more faces on their edges and get cut apart from their neighbours: run ``compact_mesh_device`` with
+    ``remove_duplicates`` first.  Two host waits: the edge count of ``mesh_edges_device``, then V'.  Raises ValueError for
+    host tensors, bad shapes and, with their number, faces that index outside [0, V)."""
+    if not isinstance(vertices, torch.Tensor):
+        raise TypeError("vertices and faces must be torch.Tensors")
+    f = _device_faces(faces, "make_manifold_device")
+    if vertices.ndim != 2 or vertices.shape[1] != 3:
+        raise ValueError(f"vertices must be [V,3], got {tuple(vertices.shape)}")
+    if not vertices.is_floating_point():
+        raise TypeError(f"vertices must be floating point, got {vertices.dtype}")
+    if not vertices.is_cuda:
+        raise ValueError("make_manifold_device needs device tensors (quadraturefields_amd has no CPU fallback)")
+    if vertices.device != f.device:
+        raise ValueError(f"vertices on {vertices.device} and faces on {f.device}")
+    dev = vertices.device
+    n_v, n_f = vertices.shape[0], f.shape[0]
+    if n_v >= 2 ** 31 or 3 * n_f >= 2 ** 31:
+        raise ValueError(f"the mesh has {n_v} vertices and {n_f} faces; V and 3 F must be < 2^31")
+    v = vertices.to(torch.float64).contiguous()
+    if n_v == 0:
+        if n_f:
+            raise ValueError(f"{n_f} faces have an index outside [0, 0)")
+        stats = dict.fromkeys(_C.MESH_MANIFOLD_COUNTS, 0) if return_stats else None
+        return ManifoldMesh(v.clone(), f.clone(), torch.empty((0,), dtype=torch.int64, device=dev), stats)
+    numbered = mesh_edges_device(f, n_v)                                  # raises for faces out of range
+    face_edges, n_e = numbered.face_edges, numbered.stats["edges"]
+    lib = _C.lib()
+    with torch.cuda.device(dev):
+        ws_bytes = int(lib.qf_mesh_manifold_workspace_bytes(n_v, n_f, n_e))
+        if ws_bytes < 0:
+            raise RuntimeError(f"qf_mesh_manifold_workspace_bytes refused V={n_v}, F={n_f}, E={n_e}")
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+        counts = torch.empty((len(_C.MESH_MANIFOLD_COUNTS),), dtype=torch.int64, device=dev)
+        _C.check(lib.qf_mesh_manifold_count(_C.ptr(f), n_f, n_v, _C.ptr(face_edges), n_e, _C.ptr(ws), ws_bytes,
+                                            _C.ptr(counts), _C.stream()), "qf_mesh_manifold_count")
+        stats = dict(zip(_C.MESH_MANIFOLD_COUNTS, counts.tolist()))
+        if stats["invalid_faces"]:
+            raise ValueError(f"{stats['invalid_faces']} faces have an index outside [0, {n_v})")
+        out_v = torch.empty((stats["vertices"], 3), dtype=torch.float64, device=dev)
+        out_f = torch.empty((n_f, 3), dtype=torch.int64, device=dev)
+        vertex_map = torch.empty((stats["vertices"],), dtype=torch.int64, device=dev)
+        _C.check(lib.qf_mesh_manifold_emit(_C.ptr(v), _C.ptr(f), n_f, n_v, _C.ptr(ws), ws_bytes, _C.ptr(out_v),
+                                           out_v.shape[0], _C.ptr(out_f), _C.ptr(vertex_map), _C.stream()),
+                 "qf_mesh_manifold_emit")
+    return ManifoldMesh(out_v, out_f, vertex_map, stats if return_stats else None)
+
+
+def make_manifold(mesh: TriMesh, device="cuda", return_stats: bool = False):
+    """``make_manifold_device`` on a ``TriMesh``: ``(TriMesh, vertex_map)`` with a numpy int64 map (and the stats dict
+    third with ``return_stats``).  Per-vertex ``visual.uv`` is carried through ``vertex_map``."""
+    dev = _C.resolve_device(device)
+    out = make_manifold_device(torch.from_numpy(np.asarray(mesh.vertices, np.float64)).to(dev),
+                               torch.from_numpy(np.asarray(mesh.faces, np.int64)).to(dev), return_stats=True)
+    vertex_map = out.vertex_map.cpu().numpy()
+    uv = None if mesh.visual.uv is None else np.asarray(mesh.visual.uv)[vertex_map]
+    res = (TriMesh(out.vertices.cpu().numpy(), out.faces.cpu().numpy(), uv), vertex_map)
+    return res + (out.stats,) if return_stats else res
+
+
 def down_sample_quadraic(mesh: TriMesh, agg=None, verbose: bool = False, device="cuda", boundary: str = "lock") -> TriMesh:
     """The reference's ``down_sample_quadraic`` (examples/mc_utils.py:214-219) on the device: the mesh decimated to
     ``F // 10`` faces by ``decimate_mesh``.  The reference calls ``fast_simplification.simplify``; this is the project's
@@ -849,10 +925,13 @@ def clean_mesh(mesh: TriMesh, agg=None, remove_duplicate_faces: bool = False, re
     ``agg > 0`` (``agg=None`` skips it; the reference would raise) -- ``agg``'s value is otherwise unused, since
     fast_simplification's aggressiveness has no counterpart in DESIGN.md section 3.9d's rule, and parity with
     fast_simplification is unpinned.  ``remove_non_manifold_edges=True`` (open3d's removal) is not built and raises
-    NotImplementedError, before any work.  ``boundary`` is ``down_sample_quadraic``'s."""
+    NotImplementedError, before any work: open3d's rule drops faces; ``make_manifold`` is the
+    lossless repair this project has instead, a step of its own.  ``boundary`` is ``down_sample_quadraic``'s."""
     _boundary_options(boundary, 1.0)
     if remove_non_manifold_edges:
-        raise NotImplementedError("remove_non_manifold_edges (open3d's removal) is not built: DESIGN.md section 3.9d")
+        raise NotImplementedError("remove_non_manifold_edges (open3d's removal, which drops faces) is not built: DESIGN.md "
+                                  "section 3.9d; mc_utils.make_manifold cuts and splits instead and drops nothing "
+                                  "(section 3.9e)")
     if remove_duplicate_faces:
         mesh = compact_mesh(mesh, device=device, remove_duplicates=True, remove_unreferenced=False)[0]
         if verbose:
