@@ -3,6 +3,7 @@ rules are this project's own, parity with the reference's fast_simplification is
 
     python examples/decimate_mesh.py IN.ply OUT.ply (--target_faces N | --ratio R) [--max_cost C] [--max_rounds K]
                                                 [--boundary {lock,collapse}] [--boundary_weight W] [--make_manifold]
+                                                [--vertex_features IN.npy --out_vertex_features OUT.npy]
 
 Writes OUT.ply and, beside it, ``face_map.npy`` (the source face of every output face) and ``vertex_target.npy`` (the
 output vertex every input vertex ended in, -1 if it was dropped), and prints the stats as one JSON line.  With the default
@@ -12,7 +13,14 @@ border too, so an open mesh reaches its target.  Non-manifold edges are never co
 ``--make_manifold`` first cuts the mesh along its non-manifold edges and splits every vertex into one copy per fan
 (no face is dropped, no coordinate changes), decimates the cut mesh and also writes
 ``cut_vertex_map.npy`` (the input vertex of every vertex of the cut mesh); ``vertex_target.npy`` then refers to the cut
-mesh's vertices, and the JSON line gains ``cut_vertices_added``, ``cut_split_vertices`` and ``cut_complex_edges``."""
+mesh's vertices, and the JSON line gains ``cut_vertices_added``, ``cut_split_vertices`` and ``cut_complex_edges``.
+
+``--vertex_features IN.npy --out_vertex_features OUT.npy`` carries a vertex-baked table [V, W] of the input mesh to the
+output mesh (``baking.transfer_vertex_features``, DESIGN.md section 3.9f: every output vertex takes the input table
+blended at its closest point on the INPUT surface -- the uncut input, also with ``--make_manifold``, so no
+``cut_vertex_map`` is needed).  With these flags the JSON line gains the measured surface
+distances ``distance_out_to_in_mean`` / ``_max`` and ``distance_in_to_out_mean`` / ``_max`` (``mc_utils.mesh_distance``).
+Without them the files and the line are what they were."""
 import argparse
 import json
 import os
@@ -37,11 +45,16 @@ def main(argv=None):
                     help="weight of a boundary edge's plane in the quadrics of its ends (collapse mode)")
     ap.add_argument("--make_manifold", action="store_true",
                     help="cut non-manifold edges and split bow-tie vertices first (writes cut_vertex_map.npy)")
+    ap.add_argument("--vertex_features", default=None, help="vertex-baked table [V, W] (.npy) of the input mesh")
+    ap.add_argument("--out_vertex_features", default=None, help="where the table transferred to the output mesh goes")
     ap.add_argument("--device", default="cuda")
     args = ap.parse_args(argv)
     from quadraturefields_amd import mc_utils
     from quadraturefields_amd.mesh_io import load_mesh
+    if (args.vertex_features is None) != (args.out_vertex_features is None):
+        ap.error("--vertex_features and --out_vertex_features go together")
     mesh = load_mesh(args.mesh_in)
+    source = mesh
     n_f = mesh.faces.shape[0]
     if args.ratio is not None and not 0.0 <= args.ratio <= 1.0:
         ap.error("--ratio must lie in [0, 1]")
@@ -61,6 +74,18 @@ def main(argv=None):
     np.save(os.path.join(folder, "vertex_target.npy"), vertex_target)
     if args.make_manifold:
         np.save(os.path.join(folder, "cut_vertex_map.npy"), cut_vertex_map)
+    if args.vertex_features is not None:
+        import torch
+        from quadraturefields_amd import baking
+        from quadraturefields_amd.mesh_utils import RayIntersector
+        table = np.load(args.vertex_features)
+        inter = RayIntersector(source, device=args.device, builder="device")
+        moved = baking.transfer_vertex_features(inter, torch.from_numpy(np.ascontiguousarray(table, np.float32)).to(inter.device),
+                                                torch.from_numpy(np.asarray(out.vertices, np.float64)).to(inter.device))
+        np.save(args.out_vertex_features, moved.cpu().numpy())
+        d = mc_utils.mesh_distance(out, source, device=args.device)
+        cut = dict(cut, distance_out_to_in_mean=d.a_to_b_mean, distance_out_to_in_max=d.a_to_b_max,
+                   distance_in_to_out_mean=d.b_to_a_mean, distance_in_to_out_max=d.b_to_a_max)
     print(json.dumps(dict(stats, boundary=args.boundary, boundary_weight=args.boundary_weight, faces_in=n_f, vertices_in=n_v, target_faces=target,
                           faces_out=int(out.faces.shape[0]), vertices_out=int(out.vertices.shape[0]), **cut)))
 

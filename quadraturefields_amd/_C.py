@@ -328,6 +328,13 @@ _MESH_MANIFOLD_SIGNATURES = {
     "qf_mesh_manifold_emit": (c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, c_int64, _P, _P, _P]),
 }
 
+# include/qf_closest_point.h: the closest point on the mesh of a qf_bvh handle, additive in the
+# same way
+CLOSEST_POINT_COUNTS = ("nonfinite_queries", "no_triangle")
+_CLOSEST_POINT_SIGNATURES = {
+    "qf_bvh_closest_points": (c_int, [_P, _P, c_int64, c_double, _P, _P, _P, _P, _P]),
+}
+
 
 def vertex_row_stride(n_lobes: int) -> int:
     """Floats per row of a vertex table: the width 3 + 7L + 1 rounded up to a 64-byte line (16 / 32 / 48 / 64 for
@@ -352,7 +359,8 @@ def lib() -> ctypes.CDLL:
                                           + list(_MESH_SUBDIVIDE_SIGNATURES.items())
                                           + list(_MESH_DECIMATE_SIGNATURES.items())
                                           + list(_MESH_DECIMATE_OPEN_SIGNATURES.items())
-                                          + list(_MESH_MANIFOLD_SIGNATURES.items())):
+                                          + list(_MESH_MANIFOLD_SIGNATURES.items())
+                                          + list(_CLOSEST_POINT_SIGNATURES.items())):
             fn = getattr(handle, name)   # AttributeError if the symbol is not exported
             fn.restype = restype
             fn.argtypes = argtypes

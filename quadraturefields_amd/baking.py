@@ -491,6 +491,42 @@ def remap_vertex_features(vertex_features, vertex_map):
     return table[idx]
 
 
+@torch.no_grad()
+def transfer_vertex_features(src_mesh_intersect, vertex_features, dst_vertices, max_distance: float = math.inf):
+    """The per-vertex table of ANOTHER mesh of the same surface (a decimated, clustered or re-extracted one): row i is the
+    source table blended at the closest point of the source mesh to ``dst_vertices[i]``, ``b0 row[f0] + b1 row[f1] + b2
+    row[f2]`` over the closest source triangle f -- the function the vertex-baked renderer draws there.  The query is
+    ``closest_points`` of ``src_mesh_intersect`` (a ``MeshIntersection`` or ``RayIntersector`` of the source mesh; DESIGN.md
+    section 3.9f); the blend is fp32, left to right, from the barycentrics rounded once to fp32.  ``dst_vertices``: device
+    float [V',3].  A tensor [V, W] comes back as a tensor [V', W], a ``VertexBakedFeatures`` as a new module (same lobes,
+    same ``train_density``).  Destination vertices that are the source's own get their rows back bit for bit.  A
+    ``QuantisedVertexFeatures`` is refused with ``TypeError``: its records sit in a vertex texture laid out by V, so
+    transfer the fp32 table and quantise after.  Raises ValueError, with their number, for destination vertices that are
+    not finite or have no source triangle within ``max_distance`` (one host wait, for those counts)."""
+    if isinstance(vertex_features, QuantisedVertexFeatures):
+        raise TypeError("transfer_vertex_features: a QuantisedVertexFeatures cannot be transferred (its vertex texture is "
+                        "laid out by V); transfer the fp32 table and quantise after")
+    table = vertex_features.features() if isinstance(vertex_features, VertexBakedFeatures) else vertex_features
+    if not isinstance(table, torch.Tensor) or table.dim() != 2:
+        raise TypeError("vertex_features must be a [V, W] tensor or a VertexBakedFeatures")
+    inter = getattr(src_mesh_intersect, "rayintersector", src_mesh_intersect)
+    faces = np.asarray(inter.mesh.faces, dtype=np.int64)
+    if table.shape[0] != inter.mesh.vertices.shape[0]:
+        raise ValueError(f"vertex_features must have V = {inter.mesh.vertices.shape[0]} rows, got {tuple(table.shape)}")
+    found = inter.closest_points(dst_vertices, max_distance)
+    nonfinite, missed = found.counts.tolist()
+    if nonfinite or missed:
+        raise ValueError(f"transfer_vertex_features: {nonfinite} destination vertices are not finite and {missed} have no "
+                         f"source triangle within {max_distance}")
+    table = table.detach().to(device=inter.device, dtype=torch.float32)
+    corners = torch.from_numpy(faces).to(inter.device)[found.tri]
+    b = found.bary.to(torch.float32)
+    out = b[:, 0:1] * table[corners[:, 0]] + b[:, 1:2] * table[corners[:, 1]] + b[:, 2:3] * table[corners[:, 2]]
+    if isinstance(vertex_features, VertexBakedFeatures):
+        return VertexBakedFeatures(out, train_density=vertex_features.train_density)
+    return out
+
+
 # ---- refining the vertex-baked asset (DESIGN.md section 3.9c) -------------------------------------------------------------
 
 RefinedVertexBaked = namedtuple("RefinedVertexBaked", ["mesh", "table", "face_map", "vertex_parents", "levels"])

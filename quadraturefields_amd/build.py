@@ -22,7 +22,7 @@ ARCH = "gfx950"
 # and quadric rules), mesh_compact.hip (integer rules only; the flag keeps it with its neighbour), mesh_subdivide.hip (the
 # fp64 midpoint is one add and one multiply, never a fused one), mesh_decimate.hip (the fp64 quadric, point, cost and
 # side rules), uv_atlas.hip (the fp64 measure, class and corner rules) and bvh_build_device.hip (the fp32 Morton
-# keys of the device BVH build).  mesh_manifold.hip has no arithmetic at all and carries no flag.
+# keys of the device BVH build) and closest_point.hip (the fp64 region walk, point and distance rules).  mesh_manifold.hip has no arithmetic at all and carries no flag.
 SOURCES = [
     ("field_eval.hip", []),
     ("field_eval_bf16.hip", []),
@@ -56,6 +56,7 @@ SOURCES = [
     ("mesh_manifold.hip", []),     # no -ffp-contract flag: the file has no floating-point operation to contract
     ("uv_atlas.hip", ["-ffp-contract=off"]),
     ("bvh_build_device.hip", ["-ffp-contract=off"]),
+    ("closest_point.hip", ["-ffp-contract=off"]),
     ("bvh_build.cpp", ["-x", "hip"]),
     ("misc.cpp", ["-x", "hip"]),
     ("frame.cpp", ["-x", "hip"]),
@@ -77,6 +78,7 @@ def _deps(src: str):
             os.path.join(ROOT, "include", "qf_vertex_quant.h"), os.path.join(ROOT, "include", "qf_mesh_compact.h"),
             os.path.join(ROOT, "include", "qf_mesh_subdivide.h"), os.path.join(ROOT, "include", "qf_mesh_decimate.h"),
             os.path.join(ROOT, "include", "qf_mesh_decimate_open.h"), os.path.join(ROOT, "include", "qf_mesh_manifold.h"),
+            os.path.join(ROOT, "include", "qf_closest_point.h"),
             os.path.abspath(__file__)]
     deps += [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     return deps

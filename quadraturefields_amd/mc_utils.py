@@ -12,6 +12,7 @@ top of them.
 ``mesh_edges_device`` / ``subdivide_mesh_device`` / ``subdivide_mesh`` number a mesh's edges and split its faces at the
 midpoints of any marked subset of them, conformingly (``csrc/mesh_subdivide.hip``, rules in DESIGN.md section 3.9c).
 """
+import ctypes
 import math
 from collections import namedtuple
 
@@ -905,6 +906,87 @@ def make_manifold(mesh: TriMesh, device="cuda", return_stats: bool = False):
     uv = None if mesh.visual.uv is None else np.asarray(mesh.visual.uv)[vertex_map]
     res = (TriMesh(out.vertices.cpu().numpy(), out.faces.cpu().numpy(), uv), vertex_map)
     return res + (out.stats,) if return_stats else res
+
+
+# ---- mesh-to-mesh distance (include/qf_closest_point.h) ----------------------------------------------
+
+MeshDistance = namedtuple("MeshDistance", ["a_to_b_mean", "a_to_b_rms", "a_to_b_max", "b_to_a_mean", "b_to_a_rms",
+                                           "b_to_a_max", "symmetric_max"])
+
+
+def _distance_mesh(vertices, faces, what: str):
+    if not isinstance(vertices, torch.Tensor):
+        raise TypeError("vertices and faces must be torch.Tensors")
+    f = _device_faces(faces, "mesh_distance_device")
+    if vertices.ndim != 2 or vertices.shape[1] != 3:
+        raise ValueError(f"{what}: vertices must be [V,3], got {tuple(vertices.shape)}")
+    if not vertices.is_floating_point():
+        raise TypeError(f"{what}: vertices must be floating point, got {vertices.dtype}")
+    if not vertices.is_cuda:
+        raise ValueError("mesh_distance_device needs device tensors (quadraturefields_amd has no CPU fallback)")
+    if vertices.device != f.device:
+        raise ValueError(f"{what}: vertices on {vertices.device} and faces on {f.device}")
+    if f.shape[0] < 1 or vertices.shape[0] < 1:
+        raise ValueError(f"{what}: a mesh needs at least one vertex and one face")
+    if int(f.min()) < 0 or int(f.max()) >= vertices.shape[0]:
+        raise ValueError(f"{what}: faces index outside [0, {vertices.shape[0]})")
+    return vertices.to(torch.float64).contiguous(), f
+
+
+def _one_sided_distance(samples: torch.Tensor, vertices: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
+    """Distance fp64 [N] from every sample to the mesh, through a tree built on the device for this one query."""
+    lib, dev = _C.lib(), vertices.device
+    tri = vertices.to(torch.float32)[faces].reshape(-1, 9).contiguous()
+    n = samples.shape[0]
+    handle = ctypes.c_void_p()
+    with torch.cuda.device(dev):
+        _C.check(lib.qf_bvh_create_device(_C.ptr(tri, torch.float32), tri.shape[0], _C.stream(), ctypes.byref(handle)),
+                 "qf_bvh_create_device")
+        try:
+            out_tri = torch.empty((n,), dtype=torch.int32, device=dev)
+            bary = torch.empty((n, 3), dtype=torch.float64, device=dev)
+            dist2 = torch.empty((n,), dtype=torch.float64, device=dev)
+            counts = torch.empty((len(_C.CLOSEST_POINT_COUNTS),), dtype=torch.int64, device=dev)
+            _C.check(lib.qf_bvh_closest_points(handle, _C.ptr(samples), n, math.inf, _C.ptr(out_tri), _C.ptr(bary),
+                                               _C.ptr(dist2), _C.ptr(counts), _C.stream()), "qf_bvh_closest_points")
+            nonfinite, missed = counts.tolist()          # the host wait: the tree is no longer in use when it is destroyed
+        finally:
+            lib.qf_bvh_destroy(handle)
+    if nonfinite or missed:
+        raise ValueError(f"mesh_distance_device: {nonfinite} samples are not finite and {missed} found no triangle")
+    return dist2.sqrt()
+
+
+def mesh_distance_device(vertices_a: torch.Tensor, faces_a: torch.Tensor, vertices_b: torch.Tensor,
+                         faces_b: torch.Tensor) -> MeshDistance:
+    """The distance between two meshes, measured: each mesh is sampled at its vertices and its face centroids (fp64), and
+    every sample is taken to its closest point on the OTHER mesh (``qf_bvh_closest_points``, DESIGN.md section 3.9f, over
+    a tree built on the device from that mesh's vertices rounded to fp32).  Returns ``MeshDistance``: mean, root mean
+    square and maximum of the one-sided distances a -> b and b -> a, and ``symmetric_max``, the larger maximum (a sampled
+    Hausdorff distance: a lower bound of the true one).  Device tensors: vertices float [V,3], faces int64 or int32
+    [F,3], at least one face each; raises ValueError for host tensors, bad shapes, faces out of range and vertices that
+    are not finite.  Two device BVH builds and two queries; one host wait each."""
+    va, fa = _distance_mesh(vertices_a, faces_a, "mesh a")
+    vb, fb = _distance_mesh(vertices_b, faces_b, "mesh b")
+    if va.device != vb.device:
+        raise ValueError(f"mesh a on {va.device} and mesh b on {vb.device}")
+    stats = []
+    for (v, f), (ov, of) in (((va, fa), (vb, fb)), ((vb, fb), (va, fa))):
+        corners = v[f]
+        centroids = ((corners[:, 0] + corners[:, 1]) + corners[:, 2]) / 3.0
+        d = _one_sided_distance(torch.cat([v, centroids]).contiguous(), ov, of)
+        stats += [float(d.mean()), float((d * d).mean().sqrt()), float(d.max())]
+    return MeshDistance(*stats, max(stats[2], stats[5]))
+
+
+def mesh_distance(mesh_a: TriMesh, mesh_b: TriMesh, device="cuda") -> MeshDistance:
+    """``mesh_distance_device`` on two ``TriMesh``."""
+    dev = _C.resolve_device(device)
+    args = []
+    for m in (mesh_a, mesh_b):
+        args += [torch.from_numpy(np.asarray(m.vertices, np.float64)).to(dev),
+                 torch.from_numpy(np.asarray(m.faces, np.int64)).to(dev)]
+    return mesh_distance_device(*args)
 
 
 def down_sample_quadraic(mesh: TriMesh, agg=None, verbose: bool = False, device="cuda", boundary: str = "lock") -> TriMesh:

@@ -8,7 +8,9 @@ one traversal launch that emits every ray's hits already ordered front to back, 
 re-sort after deformation.
 """
 import ctypes
+import math
 import os
+from collections import namedtuple
 from types import SimpleNamespace
 from typing import Optional
 
@@ -81,6 +83,10 @@ def trimesh_ray_offset(vertices) -> float:
 
 
 _resolve_device = _C.resolve_device
+
+#: What ``RayIntersector.closest_points`` returns, all on the device: ``tri`` int64 [N] (-1: none), ``bary`` fp64 [N,3],
+#: ``dist2`` fp64 [N] (+inf: none), ``counts`` int64 [2] in the order of ``_C.CLOSEST_POINT_COUNTS``.
+ClosestPoints = namedtuple("ClosestPoints", ["tri", "bary", "dist2", "counts"])
 
 
 class _PermuteRowsFn(torch.autograd.Function):
@@ -334,6 +340,41 @@ class RayIntersector:
             tri = np.ascontiguousarray(v.reshape(-1, 3)[self.mesh.faces].reshape(-1, 9))
         with torch.cuda.device(self.device):
             _C.check(_C.lib().qf_bvh_refit(self._handle, tri.ctypes.data_as(ctypes.c_void_p), tri.shape[0]), "qf_bvh_refit")
+
+    def closest_points(self, points, max_distance: float = math.inf) -> ClosestPoints:
+        """The closest point of the mesh for every query point, under the rule of DESIGN.md section 3.9f
+        (include/qf_closest_point.h; this project's own, restated in numpy in tests/closest_point_reference.py): the
+        nearest triangle (ties to the lower face id), its barycentric coordinates there and the squared distance, fp64
+        arithmetic on the fp32 vertices the tree holds NOW -- after ``update_intersector`` or ``rebuild`` the answer is for
+        the new vertices.  ``points``: device float [N,3] (fp32 is widened exactly); ``max_distance`` >= 0: triangles
+        farther away do not count (``inf``: no limit).  Returns ``ClosestPoints(tri int64 [N], bary fp64 [N,3], dist2 fp64
+        [N], counts int64 [2])`` on the device: a query with a NaN or infinite coordinate, or with no triangle in reach,
+        gets ``tri`` -1, zero ``bary`` and ``dist2`` +inf, and ``counts`` holds the number of each (``_C.CLOSEST_POINT_COUNTS``).
+        One launch on the current stream, no host wait: ``counts`` stays on the device until the caller reads it.  Raises
+        TypeError / ValueError for host tensors, integer dtypes, bad shapes and a ``max_distance`` that is negative or NaN."""
+        if not isinstance(points, torch.Tensor):
+            raise TypeError("points must be a torch.Tensor")
+        if not points.is_floating_point():
+            raise TypeError(f"points must be floating point, got {points.dtype}")
+        if points.ndim != 2 or points.shape[1] != 3:
+            raise ValueError(f"points must be [N,3], got {tuple(points.shape)}")
+        if not points.is_cuda:
+            raise ValueError("closest_points needs device tensors (quadraturefields_amd has no CPU fallback)")
+        if points.device != self.device:
+            raise ValueError(f"points on {points.device} and the intersector on {self.device}")
+        reach = float(max_distance)
+        if not reach >= 0.0:
+            raise ValueError(f"max_distance must be >= 0, got {max_distance}")
+        pts = points.detach().to(torch.float64).contiguous()
+        n = pts.shape[0]
+        tri = torch.empty((n,), dtype=torch.int32, device=self.device)
+        bary = torch.empty((n, 3), dtype=torch.float64, device=self.device)
+        dist2 = torch.empty((n,), dtype=torch.float64, device=self.device)
+        counts = torch.empty((len(_C.CLOSEST_POINT_COUNTS),), dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            _C.check(_C.lib().qf_bvh_closest_points(self._handle, _C.ptr(pts), n, reach, _C.ptr(tri), _C.ptr(bary),
+                                                    _C.ptr(dist2), _C.ptr(counts), _C.stream()), "qf_bvh_closest_points")
+        return ClosestPoints(tri.to(torch.int64), bary, dist2, counts)
 
     #: After a frame on which some pixel collected more than K candidates (the camera-coherent pass is then wasted and
     #: the BVH answers) the next frames go straight to the BVH: 1 frame after an isolated overflow, doubling while the
@@ -1225,6 +1266,10 @@ class MeshIntersection:
         # bvh_builder: "host" (binned SAH) or "device" (linear BVH built on the GPU: far faster to build, slower to traverse)
         self.rayintersector = RayIntersector(self.mesh, max_hits=self.num_intersections, device=self.device,
                                              min_separation=min_hit_separation, builder=bvh_builder)
+
+    def closest_points(self, points, max_distance: float = math.inf) -> ClosestPoints:
+        """``RayIntersector.closest_points`` of this mesh's intersector."""
+        return self.rayintersector.closest_points(points, max_distance)
 
     def find_deltas(self, boundary, depth):
         """Constant step for every sample (mesh_utils.py:225-231; B-4)."""
