@@ -2,7 +2,7 @@
 rules are this project's own, parity with the reference's fast_simplification is unpinned).
 
     python examples/decimate_mesh.py IN.ply OUT.ply (--target_faces N | --ratio R) [--max_cost C] [--max_rounds K]
-                                                [--boundary {lock,collapse}] [--boundary_weight W] [--make_manifold]
+                                                [--boundary {lock,collapse}] [--boundary_weight W] [--make_manifold] [--weld H]
                                                 [--vertex_features IN.npy --out_vertex_features OUT.npy]
 
 Writes OUT.ply and, beside it, ``face_map.npy`` (the source face of every output face) and ``vertex_target.npy`` (the
@@ -20,7 +20,17 @@ output mesh (``baking.transfer_vertex_features``, DESIGN.md section 3.9f: every 
 blended at its closest point on the INPUT surface -- the uncut input, also with ``--make_manifold``, so no
 ``cut_vertex_map`` is needed).  With these flags the JSON line gains the measured surface
 distances ``distance_out_to_in_mean`` / ``_max`` and ``distance_in_to_out_mean`` / ``_max`` (``mc_utils.mesh_distance``).
-Without them the files and the line are what they were."""
+Without them the files and the line are what they were.
+
+``--weld H`` welds the decimated mesh last (vertices at the same place, or with ``H > 0`` within
+``H`` of one another, become the lowest of them; no face is dropped).  ``--weld 0`` re-joins exactly the copies
+``--make_manifold`` made that did not move apart since: all of them after ``--boundary lock``, while copies that
+``--boundary collapse`` moved stay apart unless ``H`` reaches them, at the cost of moving the surface by up to a class's
+diameter.  It also writes ``weld_vertex_map.npy`` (the vertex of the decimated mesh every output vertex is) and
+``weld_vertex_class.npy`` (the output vertex of every vertex of the decimated mesh; ``vertex_target.npy`` still refers to
+the decimated mesh before the weld), the JSON line gains ``weld_tolerance``, ``weld_vertices_removed``,
+``weld_merged_classes``, ``weld_largest_class`` and ``weld_collapsed_faces``, and a transferred table goes through
+``baking.weld_vertex_features(..., "first")``.  Without the flag nothing changes."""
 import argparse
 import json
 import os
@@ -45,6 +55,8 @@ def main(argv=None):
                     help="weight of a boundary edge's plane in the quadrics of its ends (collapse mode)")
     ap.add_argument("--make_manifold", action="store_true",
                     help="cut non-manifold edges and split bow-tie vertices first (writes cut_vertex_map.npy)")
+    ap.add_argument("--weld", type=float, default=None, metavar="H",
+                    help="weld the decimated mesh at this tolerance last (writes weld_vertex_map.npy, weld_vertex_class.npy)")
     ap.add_argument("--vertex_features", default=None, help="vertex-baked table [V, W] (.npy) of the input mesh")
     ap.add_argument("--out_vertex_features", default=None, help="where the table transferred to the output mesh goes")
     ap.add_argument("--device", default="cuda")
@@ -68,12 +80,22 @@ def main(argv=None):
                                                                  max_rounds=args.max_rounds, return_stats=True,
                                                                  device=args.device, boundary=args.boundary,
                                                                  boundary_weight=args.boundary_weight)
+    decimated = out
+    if args.weld is not None:
+        out, weld_vertex_map, weld_vertex_class, weld_stats = mc_utils.weld_vertices(out, args.weld, device=args.device,
+                                                                                     return_stats=True)
+        cut = dict(cut, weld_tolerance=args.weld, weld_vertices_removed=int(decimated.vertices.shape[0]) - weld_stats["vertices"],
+                   weld_merged_classes=weld_stats["merged_classes"], weld_largest_class=weld_stats["largest_class"],
+                   weld_collapsed_faces=weld_stats["collapsed_faces"])
     out.export(args.mesh_out)
     folder = os.path.dirname(os.path.abspath(args.mesh_out))
     np.save(os.path.join(folder, "face_map.npy"), face_map)
     np.save(os.path.join(folder, "vertex_target.npy"), vertex_target)
     if args.make_manifold:
         np.save(os.path.join(folder, "cut_vertex_map.npy"), cut_vertex_map)
+    if args.weld is not None:
+        np.save(os.path.join(folder, "weld_vertex_map.npy"), weld_vertex_map)
+        np.save(os.path.join(folder, "weld_vertex_class.npy"), weld_vertex_class)
     if args.vertex_features is not None:
         import torch
         from quadraturefields_amd import baking
@@ -81,7 +103,9 @@ def main(argv=None):
         table = np.load(args.vertex_features)
         inter = RayIntersector(source, device=args.device, builder="device")
         moved = baking.transfer_vertex_features(inter, torch.from_numpy(np.ascontiguousarray(table, np.float32)).to(inter.device),
-                                                torch.from_numpy(np.asarray(out.vertices, np.float64)).to(inter.device))
+                                                torch.from_numpy(np.asarray(decimated.vertices, np.float64)).to(inter.device))
+        if args.weld is not None:
+            moved = baking.weld_vertex_features(moved, weld_vertex_class, out.vertices.shape[0], "first")
         np.save(args.out_vertex_features, moved.cpu().numpy())
         d = mc_utils.mesh_distance(out, source, device=args.device)
         cut = dict(cut, distance_out_to_in_mean=d.a_to_b_mean, distance_out_to_in_max=d.a_to_b_max,

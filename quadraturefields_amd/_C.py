@@ -328,6 +328,15 @@ _MESH_MANIFOLD_SIGNATURES = {
     "qf_mesh_manifold_emit": (c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, c_int64, _P, _P, _P]),
 }
 
+# include/qf_mesh_weld.h: welding vertices by position, additive in the same way
+MESH_WELD_COUNTS = ("vertices", "merged_classes", "largest_class", "collapsed_faces", "largest_cell", "loose_vertices",
+                    "out_of_range_vertices", "invalid_faces")
+_MESH_WELD_SIGNATURES = {
+    "qf_mesh_weld_workspace_bytes": (c_int64, [c_int64, c_int64]),
+    "qf_mesh_weld_count": (c_int, [_P, c_int64, _P, c_int64, c_double, _P, c_int64, _P, _P]),
+    "qf_mesh_weld_emit": (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P, _P, _P, _P]),
+}
+
 # include/qf_closest_point.h: the closest point on the mesh of a qf_bvh handle, additive in the
 # same way
 CLOSEST_POINT_COUNTS = ("nonfinite_queries", "no_triangle")
@@ -360,7 +369,8 @@ def lib() -> ctypes.CDLL:
                                           + list(_MESH_DECIMATE_SIGNATURES.items())
                                           + list(_MESH_DECIMATE_OPEN_SIGNATURES.items())
                                           + list(_MESH_MANIFOLD_SIGNATURES.items())
-                                          + list(_CLOSEST_POINT_SIGNATURES.items())):
+                                          + list(_CLOSEST_POINT_SIGNATURES.items())
+                                          + list(_MESH_WELD_SIGNATURES.items())):
             fn = getattr(handle, name)   # AttributeError if the symbol is not exported
             fn.restype = restype
             fn.argtypes = argtypes

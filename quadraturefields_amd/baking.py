@@ -491,6 +491,53 @@ def remap_vertex_features(vertex_features, vertex_map):
     return table[idx]
 
 
+def weld_vertex_features(vertex_features, vertex_class, n_out: int, reduce: str = "first"):
+    """The per-vertex table of a welded mesh (``mc_utils.weld_vertices_device``):
+    ``vertex_class`` (int64 [V], array or tensor) is the output row of every input vertex, ``n_out`` the number of output
+    rows.  ``reduce="first"`` gives every class the row of its root, its lowest vertex, bit for bit -- the same rows as
+    ``remap_vertex_features(table, vertex_map)``.  ``reduce="mean"`` gives, per class, the fp64 sum of its members' rows
+    taken in increasing vertex index, divided by the member count and rounded once to fp32 (a stable sort by class and a
+    sequential segmented sum: the order is the stated one and two runs give the same bits).  A tensor [V, W] comes back
+    as a tensor [n_out, W], a ``VertexBakedFeatures`` as a new module (same lobes, same ``train_density``).  Every output
+    row needs at least one member, and every class must lie in [0, n_out).  A ``QuantisedVertexFeatures`` is refused with
+    ``TypeError``: its records sit in a vertex texture laid out by V, so weld the fp32 table and quantise after."""
+    if isinstance(vertex_features, QuantisedVertexFeatures):
+        raise TypeError("weld_vertex_features: a QuantisedVertexFeatures cannot be welded (its vertex texture is laid "
+                        "out by V); weld the fp32 table and quantise after")
+    if reduce not in ("first", "mean"):
+        raise ValueError(f"reduce must be 'first' or 'mean', got {reduce!r}")
+    baked = isinstance(vertex_features, VertexBakedFeatures)
+    table = (vertex_features.features() if baked else vertex_features)
+    if not isinstance(table, torch.Tensor) or table.dim() != 2:
+        raise TypeError("vertex_features must be a [V, W] tensor or a VertexBakedFeatures")
+    table = table.detach()
+    cls = torch.as_tensor(np.asarray(vertex_class) if not isinstance(vertex_class, torch.Tensor) else vertex_class)
+    if cls.dim() != 1 or cls.dtype not in (torch.int64, torch.int32) or cls.shape[0] != table.shape[0]:
+        raise ValueError(f"vertex_class must be an int64 vector of the table's {table.shape[0]} rows, got {cls.dtype} "
+                         f"{tuple(cls.shape)}")
+    n_out = int(n_out)
+    cls = cls.to(device=table.device, dtype=torch.int64)
+    if cls.numel() and (int(cls.min()) < 0 or int(cls.max()) >= n_out):
+        raise IndexError(f"vertex_class reaches outside the {n_out} output rows")
+    order = torch.sort(cls, stable=True).indices                  # by class, members in increasing vertex index
+    members = torch.bincount(cls, minlength=n_out)
+    if n_out and int(members.min()) == 0:
+        raise ValueError("vertex_class leaves an output row without a member")
+    start = torch.cumsum(members, 0) - members
+    if reduce == "first":
+        out = table[order[start]]
+    else:
+        rows = table[order].to(torch.float64)
+        total = rows[start]                                       # the sum starts as the root's row (a -0.0 stays one)
+        for k in range(1, int(members.max()) if n_out else 0):    # member k of every class that has one: a gather and an
+            has = members > k                                     # add on distinct rows, so the order is the stated one
+            total[has] = total[has] + rows[start[has] + k]
+        out = (total / members.to(torch.float64)[:, None]).to(table.dtype)
+    if baked:
+        return VertexBakedFeatures(out, train_density=vertex_features.train_density)
+    return out
+
+
 @torch.no_grad()
 def transfer_vertex_features(src_mesh_intersect, vertex_features, dst_vertices, max_distance: float = math.inf):
     """The per-vertex table of ANOTHER mesh of the same surface (a decimated, clustered or re-extracted one): row i is the

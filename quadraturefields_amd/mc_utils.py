@@ -221,14 +221,20 @@ def simplify_vertex_clustering(vertices: torch.Tensor, faces: torch.Tensor, voxe
     return out_v, out_f
 
 
-def downsample_mesh(mesh: TriMesh, vx=0, device="cuda") -> TriMesh:
+def downsample_mesh(mesh: TriMesh, vx=0, device="cuda", merge_tolerance=None) -> TriMesh:
     """The reference's ``mc_utils.downsample_mesh(mesh, vx)``: with ``vx > 0`` the mesh clustered with quadric
-    contraction at voxel size ``1 / vx`` (on the device), else ``mesh`` unchanged."""
+    contraction at voxel size ``1 / vx`` (on the device), else ``mesh`` unchanged.  With a ``merge_tolerance`` the
+    clustered mesh is then welded at that tolerance (``weld_vertices``): the stand-in for the
+    tolerance merge the reference gets from ``trimesh.Trimesh(..., process=True)``, under this project's own rule
+    (parity with trimesh is unpinned; degenerate faces stay).  ``None`` keeps the clustered mesh as it is."""
     if not vx > 0:
         return mesh
     dev = _C.resolve_device(device)
     v, f = simplify_vertex_clustering(torch.from_numpy(np.asarray(mesh.vertices, np.float64)).to(dev),
                                       torch.from_numpy(np.asarray(mesh.faces, np.int64)).to(dev), 1 / vx, "quadric")
+    if merge_tolerance is not None:
+        welded = weld_vertices_device(v, f, merge_tolerance)
+        v, f = welded.vertices, welded.faces
     return TriMesh(v.cpu().numpy(), f.cpu().numpy())
 
 
@@ -905,6 +911,104 @@ def make_manifold(mesh: TriMesh, device="cuda", return_stats: bool = False):
     vertex_map = out.vertex_map.cpu().numpy()
     uv = None if mesh.visual.uv is None else np.asarray(mesh.visual.uv)[vertex_map]
     res = (TriMesh(out.vertices.cpu().numpy(), out.faces.cpu().numpy(), uv), vertex_map)
+    return res + (out.stats,) if return_stats else res
+
+
+# ---- welding vertices by position (include/qf_mesh_weld.h) -----------------------------------------
+
+WeldedMesh = namedtuple("WeldedMesh", ["vertices", "faces", "vertex_map", "vertex_class", "stats"])
+
+
+def weld_vertices_device(vertices: torch.Tensor, faces: torch.Tensor = None, tolerance: float = 0.0, *,
+                         return_stats: bool = False) -> WeldedMesh:
+    """Weld the vertices of a mesh by position on the device, under the rule of DESIGN.md section 3.9g (this project's
+    own; parity with trimesh's ``merge_vertices`` is unpinned).  With ``tolerance == 0`` two finite vertices are one iff
+    their coordinates compare equal (-0.0 equals +0.0); with ``tolerance = h > 0`` iff ``((dx*dx + dy*dy) + dz*dz) <= h*h``
+    in fp64, a closed ball, and transitively: a chain of points each within ``h`` of the next is one vertex (single
+    linkage).  A class keeps the row of its lowest vertex, its root, bit for bit -- no coordinate is computed, so with
+    ``h > 0`` a vertex may move by up to its class's diameter.  Vertices with a non-finite coordinate merge with nothing.
+    No face is dropped: faces that become degenerate stay and are counted (``compact_mesh_device(remove_degenerate=True)``
+    drops them).  ``vertices``: device float [V,3] (fp32 is widened exactly), ``faces``: device int64 or int32 [F,3] or
+    None.  Returns ``WeldedMesh(vertices fp64 [V',3], faces int64 [F,3], vertex_map int64 [V'], vertex_class int64 [V],
+    stats)``: ``vertex_map`` names the root of every output row, ``vertex_class`` the output row of every input vertex
+    (``baking.weld_vertex_features(table, vertex_class, V')`` carries a vertex-baked table along).  With ``return_stats``
+    ``stats`` is a dict of the eight counts (``_C.MESH_WELD_COUNTS``), else None.  The link pass costs the square of a
+    search cell's population (``stats["largest_cell"]``, cells of edge ``2 h``).  One host wait, for V'.  Raises
+    ValueError for host tensors, bad shapes, a negative or non-finite tolerance and, with their number, faces that index
+    outside [0, V) and vertices whose search cell is out of range (``|x| / (2 h) >= 2^51``)."""
+    if not isinstance(vertices, torch.Tensor):
+        raise TypeError("vertices and faces must be torch.Tensors")
+    if vertices.ndim != 2 or vertices.shape[1] != 3:
+        raise ValueError(f"vertices must be [V,3], got {tuple(vertices.shape)}")
+    if not vertices.is_floating_point():
+        raise TypeError(f"vertices must be floating point, got {vertices.dtype}")
+    h = float(tolerance)
+    if not (h >= 0.0 and math.isfinite(h)):
+        raise ValueError(f"tolerance must be finite and >= 0, got {tolerance}")
+    if not vertices.is_cuda:
+        raise ValueError("weld_vertices_device needs device tensors (quadraturefields_amd has no CPU fallback)")
+    dev = vertices.device
+    f = torch.empty((0, 3), dtype=torch.int64, device=dev) if faces is None else _device_faces(faces, "weld_vertices_device")
+    if vertices.device != f.device:
+        raise ValueError(f"vertices on {vertices.device} and faces on {f.device}")
+    n_v, n_f = vertices.shape[0], f.shape[0]
+    if n_v >= 2 ** 31 or n_f >= 2 ** 31:
+        raise ValueError(f"the mesh has {n_v} vertices and {n_f} faces; both must be < 2^31")
+    v = vertices.to(torch.float64).contiguous()
+    if n_v == 0:
+        if n_f:
+            raise ValueError(f"{n_f} faces have an index outside [0, 0)")
+        empty = torch.empty((0,), dtype=torch.int64, device=dev)
+        stats = dict.fromkeys(_C.MESH_WELD_COUNTS, 0) if return_stats else None
+        return WeldedMesh(v.clone(), f.clone(), empty, empty.clone(), stats)
+    lib = _C.lib()
+    with torch.cuda.device(dev):
+        ws_bytes = int(lib.qf_mesh_weld_workspace_bytes(n_v, n_f))
+        if ws_bytes < 0:
+            raise RuntimeError(f"qf_mesh_weld_workspace_bytes refused V={n_v}, F={n_f}")
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+        counts = torch.empty((len(_C.MESH_WELD_COUNTS),), dtype=torch.int64, device=dev)
+        _C.check(lib.qf_mesh_weld_count(_C.ptr(v), n_v, _C.ptr(f) if n_f else None, n_f, h, _C.ptr(ws), ws_bytes,
+                                        _C.ptr(counts), _C.stream()), "qf_mesh_weld_count")
+        stats = dict(zip(_C.MESH_WELD_COUNTS, counts.tolist()))
+        if stats["invalid_faces"]:
+            raise ValueError(f"{stats['invalid_faces']} faces have an index outside [0, {n_v})")
+        if stats["out_of_range_vertices"]:
+            raise ValueError(f"{stats['out_of_range_vertices']} vertices have a search cell out of range at tolerance {h} "
+                             "(a coordinate over twice the tolerance must stay below 2^51)")
+        out_v = torch.empty((stats["vertices"], 3), dtype=torch.float64, device=dev)
+        out_f = torch.empty((n_f, 3), dtype=torch.int64, device=dev)
+        vertex_map = torch.empty((stats["vertices"],), dtype=torch.int64, device=dev)
+        vertex_class = torch.empty((n_v,), dtype=torch.int64, device=dev)
+        _C.check(lib.qf_mesh_weld_emit(_C.ptr(v), n_v, _C.ptr(f) if n_f else None, n_f, _C.ptr(ws), ws_bytes, _C.ptr(out_v),
+                                       out_v.shape[0], _C.ptr(out_f) if n_f else None, _C.ptr(vertex_map),
+                                       _C.ptr(vertex_class), _C.stream()), "qf_mesh_weld_emit")
+    return WeldedMesh(out_v, out_f, vertex_map, vertex_class, stats if return_stats else None)
+
+
+def weld_vertices(mesh: TriMesh, tolerance: float = 0.0, device="cuda", return_stats: bool = False, compact: bool = False):
+    """``weld_vertices_device`` on a ``TriMesh``: ``(TriMesh, vertex_map, vertex_class)`` with numpy int64 maps (and the
+    stats dict last with ``return_stats``).  Per-vertex ``visual.uv`` follows the root, so **welding an atlas mesh
+    discards the atlas**: the per-triangle atlas gives every corner its own uv, and of the corners welded into one
+    vertex only the root's survives.  With ``compact=True`` the welded mesh then goes through ``compact_mesh`` with
+    degenerate and duplicate faces and unreferenced vertices removed, and the result is ``(TriMesh, face_map, vertex_map,
+    vertex_class)``: ``face_map`` is that step's (the input face of every output face, since the weld moves none),
+    ``vertex_map`` the input root of every output vertex, and ``vertex_class`` the output vertex of every input vertex,
+    -1 for those whose class no surviving face uses."""
+    dev = _C.resolve_device(device)
+    out = weld_vertices_device(torch.from_numpy(np.asarray(mesh.vertices, np.float64)).to(dev),
+                               torch.from_numpy(np.asarray(mesh.faces, np.int64)).to(dev), tolerance, return_stats=True)
+    vertex_map, vertex_class = out.vertex_map.cpu().numpy(), out.vertex_class.cpu().numpy()
+    uv = None if mesh.visual.uv is None else np.asarray(mesh.visual.uv)[vertex_map]
+    welded = TriMesh(out.vertices.cpu().numpy(), out.faces.cpu().numpy(), uv)
+    if not compact:
+        res = (welded, vertex_map, vertex_class)
+        return res + (out.stats,) if return_stats else res
+    cleaned, face_map, kept = compact_mesh(welded, device=dev, remove_degenerate=True, remove_duplicates=True,
+                                           remove_unreferenced=True)
+    rank = np.full((vertex_map.shape[0],), -1, dtype=np.int64)
+    rank[kept] = np.arange(kept.shape[0], dtype=np.int64)
+    res = (cleaned, face_map, vertex_map[kept], rank[vertex_class])
     return res + (out.stats,) if return_stats else res
 
 
