@@ -790,8 +790,11 @@ __global__ void scatter_max_kernel(const float *values, const int64_t *index, in
         if (j < 0 || j >= n_out) continue;
         const float v = values[i];
         if (v != v) continue;
-        if (v >= 0.0f) atomicMax(reinterpret_cast<int *>(out + j), __float_as_int(v));
-        else atomicMin(reinterpret_cast<unsigned int *>(out + j), __float_as_uint(v));
+        // by the sign BIT, not by v >= 0: -0.0 is 0x80000000, INT_MIN as a signed pattern (an atomicMax of it never
+        // changes anything) but the smallest of the sign-bit-set unsigned patterns, i.e. the largest non-positive value
+        const unsigned int bits = __float_as_uint(v);
+        if (bits >> 31) atomicMin(reinterpret_cast<unsigned int *>(out + j), bits);
+        else atomicMax(reinterpret_cast<int *>(out + j), (int)bits);
     }
 }
 
