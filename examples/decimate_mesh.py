@@ -4,6 +4,7 @@ rules are this project's own, parity with the reference's fast_simplification is
     python examples/decimate_mesh.py IN.ply OUT.ply (--target_faces N | --ratio R) [--max_cost C] [--max_rounds K]
                                                 [--boundary {lock,collapse}] [--boundary_weight W] [--make_manifold] [--weld H]
                                                 [--vertex_features IN.npy --out_vertex_features OUT.npy]
+                                                [--distance_samples N]
 
 Writes OUT.ply and, beside it, ``face_map.npy`` (the source face of every output face) and ``vertex_target.npy`` (the
 output vertex every input vertex ended in, -1 if it was dropped), and prints the stats as one JSON line.  With the default
@@ -30,7 +31,12 @@ diameter.  It also writes ``weld_vertex_map.npy`` (the vertex of the decimated m
 ``weld_vertex_class.npy`` (the output vertex of every vertex of the decimated mesh; ``vertex_target.npy`` still refers to
 the decimated mesh before the weld), the JSON line gains ``weld_tolerance``, ``weld_vertices_removed``,
 ``weld_merged_classes``, ``weld_largest_class`` and ``weld_collapsed_faces``, and a transferred table goes through
-``baking.weld_vertex_features(..., "first")``.  Without the flag nothing changes."""
+``baking.weld_vertex_features(..., "first")``.  Without the flag nothing changes.
+
+``--distance_samples N`` measures the distance between the output and the input mesh at ``N`` points drawn uniformly by
+area from each (``mc_utils.mesh_distance(..., samples=N)``, DESIGN.md section 3.9h: mean and RMS over the surface, not
+over the tessellation) and adds ``distance_samples``, ``distance_sampled_out_to_in_mean`` / ``_rms`` / ``_max`` and
+``distance_sampled_in_to_out_mean`` / ``_rms`` / ``_max`` to the JSON line.  Without the flag nothing changes."""
 import argparse
 import json
 import os
@@ -59,6 +65,8 @@ def main(argv=None):
                     help="weld the decimated mesh at this tolerance last (writes weld_vertex_map.npy, weld_vertex_class.npy)")
     ap.add_argument("--vertex_features", default=None, help="vertex-baked table [V, W] (.npy) of the input mesh")
     ap.add_argument("--out_vertex_features", default=None, help="where the table transferred to the output mesh goes")
+    ap.add_argument("--distance_samples", type=int, default=None, metavar="N",
+                    help="also measure the output-to-input distance at N area-weighted surface samples per mesh")
     ap.add_argument("--device", default="cuda")
     args = ap.parse_args(argv)
     from quadraturefields_amd import mc_utils
@@ -110,6 +118,12 @@ def main(argv=None):
         d = mc_utils.mesh_distance(out, source, device=args.device)
         cut = dict(cut, distance_out_to_in_mean=d.a_to_b_mean, distance_out_to_in_max=d.a_to_b_max,
                    distance_in_to_out_mean=d.b_to_a_mean, distance_in_to_out_max=d.b_to_a_max)
+    if args.distance_samples is not None:
+        d = mc_utils.mesh_distance(out, source, device=args.device, samples=args.distance_samples)
+        cut = dict(cut, distance_samples=args.distance_samples, distance_sampled_out_to_in_mean=d.a_to_b_mean,
+                   distance_sampled_out_to_in_rms=d.a_to_b_rms, distance_sampled_out_to_in_max=d.a_to_b_max,
+                   distance_sampled_in_to_out_mean=d.b_to_a_mean, distance_sampled_in_to_out_rms=d.b_to_a_rms,
+                   distance_sampled_in_to_out_max=d.b_to_a_max)
     print(json.dumps(dict(stats, boundary=args.boundary, boundary_weight=args.boundary_weight, faces_in=n_f, vertices_in=n_v, target_faces=target,
                           faces_out=int(out.faces.shape[0]), vertices_out=int(out.vertices.shape[0]), **cut)))
 

@@ -5,7 +5,7 @@ used for device memory and streams; every tensor crosses the boundary as a raw d
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint8, c_uint32, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint8, c_uint32, c_uint64, c_void_p
 
 import torch
 
@@ -337,6 +337,15 @@ _MESH_WELD_SIGNATURES = {
     "qf_mesh_weld_emit": (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P, _P, _P, _P]),
 }
 
+# include/qf_mesh_sample.h: points drawn by area from a mesh's surface, additive in the same way
+MESH_SAMPLE_COUNTS = ("nonfinite_vertices", "invalid_faces", "bad_weights", "nonfinite_measures", "unsampled_faces",
+                      "no_measure")
+_MESH_SAMPLE_SIGNATURES = {
+    "qf_mesh_sample_workspace_bytes": (c_int64, [c_int64, c_int64]),
+    "qf_mesh_sample_prepare": (c_int, [_P, c_int64, _P, c_int64, _P, _P, c_int64, _P, _P]),
+    "qf_mesh_sample_emit": (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, c_int64, c_uint64, _P, _P, _P, _P]),
+}
+
 # include/qf_closest_point.h: the closest point on the mesh of a qf_bvh handle, additive in the
 # same way
 CLOSEST_POINT_COUNTS = ("nonfinite_queries", "no_triangle")
@@ -370,7 +379,8 @@ def lib() -> ctypes.CDLL:
                                           + list(_MESH_DECIMATE_OPEN_SIGNATURES.items())
                                           + list(_MESH_MANIFOLD_SIGNATURES.items())
                                           + list(_CLOSEST_POINT_SIGNATURES.items())
-                                          + list(_MESH_WELD_SIGNATURES.items())):
+                                          + list(_MESH_WELD_SIGNATURES.items())
+                                          + list(_MESH_SAMPLE_SIGNATURES.items())):
             fn = getattr(handle, name)   # AttributeError if the symbol is not exported
             fn.restype = restype
             fn.argtypes = argtypes

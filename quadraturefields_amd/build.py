@@ -23,7 +23,8 @@ ARCH = "gfx950"
 # fp64 midpoint is one add and one multiply, never a fused one), mesh_decimate.hip (the fp64 quadric, point, cost and
 # side rules), uv_atlas.hip (the fp64 measure, class and corner rules) and bvh_build_device.hip (the fp32 Morton
 # keys of the device BVH build) and closest_point.hip (the fp64 region walk, point and distance rules).  mesh_manifold.hip has no arithmetic at all and carries no flag;
-# mesh_weld.hip carries it for the fp64 cell quotient and distance test of the weld.
+# mesh_weld.hip carries it for the fp64 cell quotient and distance test of the weld, mesh_sample.hip for the fp64 measure,
+# quotient, position and point rules of surface sampling.
 SOURCES = [
     ("field_eval.hip", []),
     ("field_eval_bf16.hip", []),
@@ -56,6 +57,7 @@ SOURCES = [
     ("mesh_decimate.hip", ["-ffp-contract=off"]),
     ("mesh_manifold.hip", []),     # no -ffp-contract flag: the file has no floating-point operation to contract
     ("mesh_weld.hip", ["-ffp-contract=off"]),      # the fp64 cell quotient and distance test of the weld
+    ("mesh_sample.hip", ["-ffp-contract=off"]),    # the fp64 measure, position, barycentric and point rules
     ("uv_atlas.hip", ["-ffp-contract=off"]),
     ("bvh_build_device.hip", ["-ffp-contract=off"]),
     ("closest_point.hip", ["-ffp-contract=off"]),
@@ -81,6 +83,7 @@ def _deps(src: str):
             os.path.join(ROOT, "include", "qf_mesh_subdivide.h"), os.path.join(ROOT, "include", "qf_mesh_decimate.h"),
             os.path.join(ROOT, "include", "qf_mesh_decimate_open.h"), os.path.join(ROOT, "include", "qf_mesh_manifold.h"),
             os.path.join(ROOT, "include", "qf_closest_point.h"), os.path.join(ROOT, "include", "qf_mesh_weld.h"),
+            os.path.join(ROOT, "include", "qf_mesh_sample.h"),
             os.path.abspath(__file__)]
     deps += [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     return deps

@@ -1012,6 +1012,90 @@ def weld_vertices(mesh: TriMesh, tolerance: float = 0.0, device="cuda", return_s
     return res + (out.stats,) if return_stats else res
 
 
+# ---- points drawn by area from a mesh's surface (include/qf_mesh_sample.h) ------------------------
+
+SurfaceSamples = namedtuple("SurfaceSamples", ["points", "face", "bary"])
+
+
+def sample_surface_device(vertices: torch.Tensor, faces: torch.Tensor, n_samples: int, seed: int = 0,
+                          face_weight: torch.Tensor = None, return_stats: bool = False):
+    """``n_samples`` points drawn from the surface of a mesh on the device, uniformly by area, under the rule of DESIGN.md
+    section 3.9h (this project's own).  The faces are laid end to end by measure -- area, times ``face_weight[f]`` when
+    weights are given, quantised to 2^-32 of the largest face -- and sample ``i`` falls in the ``i``-th of ``n_samples``
+    equal strata of that line, so the number of samples on a face is within 2 of its share, and face ids come out
+    non-decreasing; inside its face a sample is uniform.  The same ``seed`` gives the same bytes, from run to run and
+    whatever the launch shape.  ``vertices``: device float [V,3] (fp32 is widened exactly), ``faces``: device int64 or
+    int32 [F,3], ``face_weight``: device float [F], non-negative and finite, or None; ``seed`` in [0, 2^64).  Faces below
+    2^-32 of the largest measure (degenerate ones, zero weights) are never sampled.  Returns ``SurfaceSamples(points fp64
+    [N,3], face int64 [N], bary fp64 [N,3])``, and with ``return_stats`` a dict of the six counts
+    (``_C.MESH_SAMPLE_COUNTS``) second.  One host wait, for the counts, after both calls are enqueued.  Raises ValueError
+    for host tensors, bad shapes and, naming the counts, a mesh with non-finite vertices, faces that index outside
+    [0, V), bad weights, non-finite measures, or no measure at all."""
+    if not isinstance(vertices, torch.Tensor):
+        raise TypeError("vertices and faces must be torch.Tensors")
+    if vertices.ndim != 2 or vertices.shape[1] != 3:
+        raise ValueError(f"vertices must be [V,3], got {tuple(vertices.shape)}")
+    if not vertices.is_floating_point():
+        raise TypeError(f"vertices must be floating point, got {vertices.dtype}")
+    n, seed = int(n_samples), int(seed)
+    if not 0 <= n < 2 ** 31:
+        raise ValueError(f"n_samples must be in [0, 2^31), got {n_samples}")
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError(f"seed must be in [0, 2^64), got {seed}")
+    if not vertices.is_cuda:
+        raise ValueError("sample_surface_device needs device tensors (quadraturefields_amd has no CPU fallback)")
+    dev = vertices.device
+    f = _device_faces(faces, "sample_surface_device")
+    if f.device != dev:
+        raise ValueError(f"vertices on {dev} and faces on {f.device}")
+    n_v, n_f = vertices.shape[0], f.shape[0]
+    if not (1 <= n_v < 2 ** 31 and 1 <= n_f and 3 * n_f < 2 ** 31):
+        raise ValueError(f"the mesh has {n_v} vertices and {n_f} faces; it needs 1 <= V < 2^31 and 1 <= F < 2^31 / 3")
+    w = None
+    if face_weight is not None:
+        if not isinstance(face_weight, torch.Tensor) or not face_weight.is_floating_point():
+            raise TypeError("face_weight must be a floating-point torch.Tensor")
+        if face_weight.shape != (n_f,):
+            raise ValueError(f"face_weight must be [{n_f}], got {tuple(face_weight.shape)}")
+        if face_weight.device != dev:
+            raise ValueError(f"vertices on {dev} and face_weight on {face_weight.device}")
+        w = face_weight.to(torch.float64).contiguous()
+    v = vertices.to(torch.float64).contiguous()
+    lib = _C.lib()
+    with torch.cuda.device(dev):
+        ws_bytes = int(lib.qf_mesh_sample_workspace_bytes(n_v, n_f))
+        if ws_bytes < 0:
+            raise RuntimeError(f"qf_mesh_sample_workspace_bytes refused V={n_v}, F={n_f}")
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+        counts = torch.empty((len(_C.MESH_SAMPLE_COUNTS),), dtype=torch.int64, device=dev)
+        points = torch.empty((n, 3), dtype=torch.float64, device=dev)
+        face = torch.empty((n,), dtype=torch.int64, device=dev)
+        bary = torch.empty((n, 3), dtype=torch.float64, device=dev)
+        _C.check(lib.qf_mesh_sample_prepare(_C.ptr(v), n_v, _C.ptr(f), n_f, None if w is None else _C.ptr(w), _C.ptr(ws),
+                                            ws_bytes, _C.ptr(counts), _C.stream()), "qf_mesh_sample_prepare")
+        _C.check(lib.qf_mesh_sample_emit(_C.ptr(v), n_v, _C.ptr(f), n_f, _C.ptr(ws), ws_bytes, n, seed,
+                                         _C.ptr(points) if n else None, _C.ptr(face) if n else None,
+                                         _C.ptr(bary) if n else None, _C.stream()), "qf_mesh_sample_emit")
+        stats = dict(zip(_C.MESH_SAMPLE_COUNTS, counts.tolist()))        # the host wait
+    if any(stats[k] for k in _C.MESH_SAMPLE_COUNTS[:4]) or stats["no_measure"]:
+        raise ValueError("sample_surface_device: the mesh cannot be sampled: "
+                         + ", ".join(f"{k}={stats[k]}" for k in _C.MESH_SAMPLE_COUNTS))
+    out = SurfaceSamples(points, face, bary)
+    return (out, stats) if return_stats else out
+
+
+def sample_surface(mesh: TriMesh, n_samples: int, seed: int = 0, face_weight=None, device="cuda", return_stats: bool = False):
+    """``sample_surface_device`` on a ``TriMesh``: ``SurfaceSamples`` of numpy arrays (and the stats dict second with
+    ``return_stats``).  ``face_weight``: array-like [F] or None."""
+    dev = _C.resolve_device(device)
+    w = None if face_weight is None else torch.from_numpy(np.ascontiguousarray(face_weight, dtype=np.float64)).to(dev)
+    out, stats = sample_surface_device(torch.from_numpy(np.asarray(mesh.vertices, np.float64)).to(dev),
+                                       torch.from_numpy(np.asarray(mesh.faces, np.int64)).to(dev), n_samples, seed,
+                                       face_weight=w, return_stats=True)
+    res = SurfaceSamples(out.points.cpu().numpy(), out.face.cpu().numpy(), out.bary.cpu().numpy())
+    return (res, stats) if return_stats else res
+
+
 # ---- mesh-to-mesh distance (DESIGN.md section 3.9f, include/qf_closest_point.h) ----------------------------------------------
 
 MeshDistance = namedtuple("MeshDistance", ["a_to_b_mean", "a_to_b_rms", "a_to_b_max", "b_to_a_mean", "b_to_a_rms",
@@ -1062,35 +1146,48 @@ def _one_sided_distance(samples: torch.Tensor, vertices: torch.Tensor, faces: to
 
 
 def mesh_distance_device(vertices_a: torch.Tensor, faces_a: torch.Tensor, vertices_b: torch.Tensor,
-                         faces_b: torch.Tensor) -> MeshDistance:
+                         faces_b: torch.Tensor, samples: int = None, seed: int = 0) -> MeshDistance:
     """The distance between two meshes, measured: each mesh is sampled at its vertices and its face centroids (fp64), and
     every sample is taken to its closest point on the OTHER mesh (``qf_bvh_closest_points``, DESIGN.md section 3.9f, over
     a tree built on the device from that mesh's vertices rounded to fp32).  Returns ``MeshDistance``: mean, root mean
     square and maximum of the one-sided distances a -> b and b -> a, and ``symmetric_max``, the larger maximum (a sampled
     Hausdorff distance: a lower bound of the true one).  Device tensors: vertices float [V,3], faces int64 or int32
     [F,3], at least one face each; raises ValueError for host tensors, bad shapes, faces out of range and vertices that
-    are not finite.  Two device BVH builds and two queries; one host wait each."""
+    are not finite.  Two device BVH builds and two queries; one host wait each.
+
+    The default samples follow the tessellation, so its mean and RMS are averages over vertices and centroids, not over
+    the surface: they move when a mesh is re-tessellated without moving.  With ``samples=N`` each mesh is sampled instead
+    at ``N`` points drawn uniformly by area (``sample_surface_device`` with ``seed``): mean and
+    RMS then estimate the surface integrals, whatever the tessellation, and the maximum is taken over those points.  The
+    Hausdorff figure is still a lower bound of the true one: a finite sample can miss the farthest point (and unlike
+    the default it need not contain the vertices).  ``samples=None`` is bit for bit the function without the argument."""
     va, fa = _distance_mesh(vertices_a, faces_a, "mesh a")
     vb, fb = _distance_mesh(vertices_b, faces_b, "mesh b")
     if va.device != vb.device:
         raise ValueError(f"mesh a on {va.device} and mesh b on {vb.device}")
+    if samples is not None and int(samples) < 1:
+        raise ValueError(f"samples must be None or at least 1, got {samples}")
     stats = []
     for (v, f), (ov, of) in (((va, fa), (vb, fb)), ((vb, fb), (va, fa))):
-        corners = v[f]
-        centroids = ((corners[:, 0] + corners[:, 1]) + corners[:, 2]) / 3.0
-        d = _one_sided_distance(torch.cat([v, centroids]).contiguous(), ov, of)
+        if samples is None:
+            corners = v[f]
+            centroids = ((corners[:, 0] + corners[:, 1]) + corners[:, 2]) / 3.0
+            queries = torch.cat([v, centroids]).contiguous()
+        else:
+            queries = sample_surface_device(v, f, int(samples), seed).points
+        d = _one_sided_distance(queries, ov, of)
         stats += [float(d.mean()), float((d * d).mean().sqrt()), float(d.max())]
     return MeshDistance(*stats, max(stats[2], stats[5]))
 
 
-def mesh_distance(mesh_a: TriMesh, mesh_b: TriMesh, device="cuda") -> MeshDistance:
+def mesh_distance(mesh_a: TriMesh, mesh_b: TriMesh, device="cuda", samples: int = None, seed: int = 0) -> MeshDistance:
     """``mesh_distance_device`` on two ``TriMesh``."""
     dev = _C.resolve_device(device)
     args = []
     for m in (mesh_a, mesh_b):
         args += [torch.from_numpy(np.asarray(m.vertices, np.float64)).to(dev),
                  torch.from_numpy(np.asarray(m.faces, np.int64)).to(dev)]
-    return mesh_distance_device(*args)
+    return mesh_distance_device(*args, samples=samples, seed=seed)
 
 
 def down_sample_quadraic(mesh: TriMesh, agg=None, verbose: bool = False, device="cuda", boundary: str = "lock") -> TriMesh:
