@@ -48,8 +48,6 @@ constexpr int kAxisBits = 21;
 constexpr float kAxisCells = 2097152.f;  // 2^21
 constexpr uint32_t kAxisMax = (1u << kAxisBits) - 1u;
 
-inline int64_t align_up(int64_t x) { return (x + 255) & ~int64_t(255); }
-
 // Bounds of the finite triangles' vertices and centroids, their area, the count of the others.
 struct Info {
     float vlo[3], vhi[3], clo[3], chi[3];
@@ -387,7 +385,7 @@ int build_device(const float *d_tri_verts, int64_t n_tri, hipStream_t st, float 
     const size_t temp_bytes = rocprim_temp_bytes((size_t)n_tri, (size_t)capacity, st);
     if (temp_bytes == 0) return QF_ERR_HIP;
     int64_t off = 0;
-    auto take = [&](int64_t bytes) { const int64_t at = off; off += align_up(bytes); return at; };
+    auto take = [&](int64_t bytes) { const int64_t at = off; off += qf_align_up(bytes); return at; };
     const int64_t o_info = take(sizeof(Info)), o_partial = take((int64_t)sizeof(Info) * kRedBlocks);
     const int64_t o_key_a = take(8 * n_tri), o_key_b = take(8 * n_tri), o_id_a = take(4 * n_tri), o_id_b = take(4 * n_tri);
     const int64_t o_rg_a = take(8 * capacity), o_rg_b = take(8 * capacity), o_cnt = take(4 * capacity), o_off = take(4 * capacity);

@@ -39,8 +39,6 @@ constexpr int64_t kTile = (int64_t)kBlock * kItems;          // grid points per 
 constexpr int64_t kMaxDim = int64_t(1) << 24;                // grid coordinates exact in fp32
 constexpr int64_t kMaxPoints = int64_t(1) << 31;
 
-inline int64_t align_up(int64_t x) { return (x + 255) & ~int64_t(255); }
-
 struct Workspace {
     int32_t *local;       // [N] vertex offset of each grid point within its workgroup's tile
     int64_t *block_v;     // [nb] vertices per tile, then (scan) the tile's first vertex
@@ -53,13 +51,12 @@ Workspace carve(void *base, int64_t n)
 {
     const int64_t nb = (n + kTile - 1) / kTile;
     Workspace w;
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) { char *p = static_cast<char *>(base) + off; off += align_up(bytes); return p; };
-    w.local = reinterpret_cast<int32_t *>(take(4 * n));
-    w.block_v = reinterpret_cast<int64_t *>(take(8 * nb));
-    w.block_f = reinterpret_cast<int64_t *>(take(8 * nb));
-    w.block_bad = reinterpret_cast<int64_t *>(take(8 * nb));
-    w.bytes = off;
+    QfCarver c{base};
+    w.local = c.take<int32_t>(n);
+    w.block_v = c.take<int64_t>(nb);
+    w.block_f = c.take<int64_t>(nb);
+    w.block_bad = c.take<int64_t>(nb);
+    w.bytes = c.off;
     return w;
 }
 

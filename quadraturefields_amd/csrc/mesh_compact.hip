@@ -5,35 +5,28 @@
 // Passes of qf_mesh_compact_count (one stream, no host wait):
 //   init      parent[v] = v, csize[v] = 0, used[v] = (vertices are all kept);
 //   classify  per face: validity, mask, degenerate -> state[f]; the sorted index triple -> tri[3f..] (int32);
-//   dup       an open-addressing hash table of face ids keyed by the sorted triple, at least 2 F slots: a surviving
-//             face claims the first empty slot of its probe sequence with compare-and-swap, or lowers the id of the slot
-//             that already holds its triple with an integer atomicMin; afterwards a face is a duplicate iff its slot
-//             holds another id.  The lowest index wins whatever the arrival order, and faces already dropped are never
-//             entered, so they are nobody's "earlier copy".  (No library sort: rocPRIM's onesweep kernels use scratch
-//             and a look-back spin.);
-//   union     lock-free union-find over vertices: the larger root is hooked under the smaller with compare-and-swap, so
-//             a tree's root is its smallest vertex whatever the arrival order; a failed swap continues from the value
-//             it read (another thread made progress), nothing waits;
+//   dup       an open-addressing hash table of face ids keyed by the sorted triple, at least 2 F slots, filled with
+//             mesh_device.h's claim-or-lower insert; afterwards a face is a duplicate iff its slot holds another id.
+//             The lowest index wins whatever the arrival order, and faces already dropped are never entered, so they
+//             are nobody's "earlier copy".  (No library sort: rocPRIM's onesweep kernels use scratch and a look-back
+//             spin.);
+//   union     mesh_device.h's lock-free union-find over vertices: a tree's root is its smallest vertex whatever the
+//             arrival order;
 //   flatten   parent[v] = root(v);  size: one integer atomic per surviving face on csize[root];
 //   island    faces of components below M dropped, the vertices of the final faces marked;
-//   scans     output positions of faces and vertices: three launches each, block scans in the style of scan.hip;
+//   scans     output positions of faces and vertices: mesh_device.h's three-launch scan, once each;
 //   finalize  counts[8].
 // Every tally is an integer sum, so no result depends on the launch shape or the arrival order.
-#include "qf_common.h"
+#include "mesh_device.h"
 #include "qf_mesh_compact.h"
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kScanItems = 1024;                // items per workgroup in the scans
 constexpr int64_t kMaxCount = int64_t(1) << 31;
 constexpr uint32_t kDropped = 0x7fffffffu;      // above every vertex index (V < 2^31, so an index is <= 2^31 - 2)
-constexpr uint32_t kEmpty = 0xffffffffu;        // an unclaimed slot of the duplicate table (a face id is < 2^31)
 constexpr int kAllFlags = QF_MESH_REMOVE_DEGENERATE | QF_MESH_REMOVE_DUPLICATES | QF_MESH_REMOVE_UNREFERENCED;
 
 enum : uint8_t { kAlive = 0, kByMask = 1, kDegenerate = 2, kDuplicate = 3, kIsland = 4, kInvalid = 5 };
-
-inline int64_t align_up(int64_t x) { return (x + 255) & ~int64_t(255); }
 
 struct Info {
     unsigned long long n_invalid, n_mask, n_degenerate, n_duplicate, n_island, n_components;
@@ -56,32 +49,24 @@ struct Workspace {
     int64_t bytes;
 };
 
-int64_t table_slots(int64_t F)
-{
-    int64_t t = 64;
-    while (t < 2 * F) t <<= 1;
-    return t;
-}
-
 Workspace carve(void *base, int64_t V, int64_t F)
 {
     Workspace w;
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) { char *p = static_cast<char *>(base) + off; off += align_up(bytes); return p; };
-    w.info = reinterpret_cast<Info *>(take(sizeof(Info)));
-    w.parent = reinterpret_cast<int32_t *>(take(4 * V));
-    w.csize = reinterpret_cast<int32_t *>(take(4 * V));
-    w.used = reinterpret_cast<uint8_t *>(take(V));
-    w.vpos = reinterpret_cast<int32_t *>(take(4 * V));
-    w.state = reinterpret_cast<uint8_t *>(take(F));
-    w.tri = reinterpret_cast<int32_t *>(take(12 * F));
-    w.fpos = reinterpret_cast<int32_t *>(take(4 * F));
+    QfCarver c{base};
+    w.info = c.take<Info>(1);
+    w.parent = c.take<int32_t>(V);
+    w.csize = c.take<int32_t>(V);
+    w.used = c.take<uint8_t>(V);
+    w.vpos = c.take<int32_t>(V);
+    w.state = c.take<uint8_t>(F);
+    w.tri = c.take<int32_t>(3 * F);
+    w.fpos = c.take<int32_t>(F);
     w.slots = table_slots(F);
-    w.table = reinterpret_cast<uint32_t *>(take(4 * w.slots));
-    w.slot = reinterpret_cast<uint32_t *>(take(4 * F));
-    w.vpart = reinterpret_cast<int32_t *>(take(4 * qf_div_up(V, kScanItems)));
-    w.fpart = reinterpret_cast<int32_t *>(take(4 * qf_div_up(F, kScanItems)));
-    w.bytes = off;
+    w.table = c.take<uint32_t>(w.slots);
+    w.slot = c.take<uint32_t>(F);
+    w.vpart = c.take<int32_t>(qf_div_up(V, kScanItems));
+    w.fpart = c.take<int32_t>(qf_div_up(F, kScanItems));
+    w.bytes = c.off;
     return w;
 }
 
@@ -93,49 +78,6 @@ struct Job {
     int32_t flags;
     int32_t M;
 };
-
-__device__ __forceinline__ int64_t gtid() { return (int64_t)blockIdx.x * blockDim.x + threadIdx.x; }
-
-// Sum of `v` over the wave, added to *dst by one lane.  Every lane of the wave must call it.
-__device__ __forceinline__ void tally(unsigned long long *dst, int v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    if ((threadIdx.x & 63) == 0 && v) atomicAdd(dst, (unsigned long long)v);
-}
-
-__device__ __forceinline__ int32_t load_parent(const int32_t *parent, int32_t x)
-{
-    return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// Root of x, halving the path on the way: a parent only ever moves to a smaller vertex of the same tree, so the
-// atomicMin keeps every concurrent reader on a valid path.
-__device__ __forceinline__ int32_t uf_find(int32_t *parent, int32_t x)
-{
-    int32_t p = load_parent(parent, x);
-    while (p != x) {
-        const int32_t gp = load_parent(parent, p);
-        if (gp != p) atomicMin(parent + x, gp);
-        x = p;
-        p = gp;
-    }
-    return x;
-}
-
-__device__ __forceinline__ void uf_union(int32_t *parent, int32_t a, int32_t b)
-{
-    while (true) {
-        a = uf_find(parent, a);
-        b = uf_find(parent, b);
-        if (a == b) return;
-        const int32_t hi = a > b ? a : b, lo = a > b ? b : a;
-        const int32_t old = atomicCAS(parent + hi, hi, lo);
-        if (old == hi) return;
-        a = old;            // hi was hooked under `old` by another thread meanwhile: go on from there
-        b = lo;
-    }
-}
 
 __global__ __launch_bounds__(kBlock) void init_kernel(int64_t V, Workspace ws, int all_used)
 {
@@ -190,31 +132,17 @@ __device__ __forceinline__ uint64_t triple_hash(uint32_t lo, uint32_t mid, uint3
     return h ^ (h >> 31);
 }
 
-// A surviving face walks its probe sequence to the first slot that is empty (claimed with compare-and-swap) or holds a
-// face with the same sorted triple (whose id it lowers to its own if smaller).  A slot's triple never changes once it is
-// claimed, and a failed swap goes on with the id it read: nothing waits.  At most F of the >= 2 F slots are ever claimed,
-// so the walk ends.
+// A surviving face enters the table under its sorted triple (claim_or_lower of mesh_device.h).
 __global__ __launch_bounds__(kBlock) void duplicate_insert_kernel(int64_t F, Workspace ws)
 {
     const int64_t f = gtid();
     if (f >= F || ws.info->n_invalid != 0 || ws.state[f] != kAlive) return;
     const int32_t lo = ws.tri[3 * f], mid = ws.tri[3 * f + 1], hi = ws.tri[3 * f + 2];
-    const uint64_t wrap = (uint64_t)ws.slots - 1;
-    uint64_t s = triple_hash((uint32_t)lo, (uint32_t)mid, (uint32_t)hi) & wrap;
-    while (true) {
-        uint32_t g = __hip_atomic_load(ws.table + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (g == kEmpty) {
-            g = atomicCAS(ws.table + s, kEmpty, (uint32_t)f);
-            if (g == kEmpty) break;
-        }
+    const uint64_t hash = triple_hash((uint32_t)lo, (uint32_t)mid, (uint32_t)hi);
+    ws.slot[f] = (uint32_t)claim_or_lower(ws.table, (uint64_t)ws.slots - 1, hash, (uint32_t)f, [&](uint32_t g) {
         const int32_t *t = ws.tri + 3 * (int64_t)g;
-        if (t[0] == lo && t[1] == mid && t[2] == hi) {
-            if ((uint32_t)f < g) atomicMin(ws.table + s, (uint32_t)f);
-            break;
-        }
-        s = (s + 1) & wrap;
-    }
-    ws.slot[f] = (uint32_t)s;
+        return t[0] == lo && t[1] == mid && t[2] == hi;
+    });
 }
 
 __global__ __launch_bounds__(kBlock) void duplicate_mark_kernel(int64_t F, Workspace ws)
@@ -241,12 +169,7 @@ __global__ __launch_bounds__(kBlock) void flatten_kernel(int64_t V, Workspace ws
 {
     const int64_t v = gtid();
     if (v >= V || ws.info->n_invalid != 0) return;
-    int32_t x = (int32_t)v, p = load_parent(ws.parent, x);
-    while (p != x) {
-        x = p;
-        p = load_parent(ws.parent, x);
-    }
-    __hip_atomic_store(ws.parent + v, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(ws.parent + v, uf_root(ws.parent, (int32_t)v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 __global__ __launch_bounds__(kBlock) void component_size_kernel(int64_t F, Workspace ws)
@@ -279,80 +202,6 @@ __global__ __launch_bounds__(kBlock) void island_kernel(int64_t F, Workspace ws,
         }
     }
     tally(&ws.info->n_island, island);
-}
-
-// ---- exclusive scan of the flags (src[i] == match) over n items: per-workgroup sums, one workgroup scans those, every
-// workgroup scans its own items from its base (scan.hip's three launches)
-__device__ __forceinline__ int32_t block_inclusive_scan(int32_t v, int32_t *s_wave, int32_t *total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int32_t o = __shfl_up(v, off, 64);
-        if (lane >= off) v += o;
-    }
-    if (lane == 63) s_wave[wave] = v;
-    __syncthreads();
-    int32_t base = 0, sum = 0;
-    for (int w = 0; w < kBlock / 64; ++w) {
-        if (w < wave) base += s_wave[w];
-        sum += s_wave[w];
-    }
-    __syncthreads();
-    *total = sum;
-    return v + base;
-}
-
-__global__ __launch_bounds__(kBlock) void scan_partials_kernel(const uint8_t *__restrict__ src, int64_t n, uint8_t match,
-                                                               int32_t *__restrict__ partial)
-{
-    __shared__ int32_t s_wave[kBlock / 64];
-    const int64_t i0 = (int64_t)blockIdx.x * kScanItems + (int64_t)threadIdx.x * (kScanItems / kBlock);
-    int32_t v = 0;
-#pragma unroll
-    for (int k = 0; k < kScanItems / kBlock; ++k) v += (i0 + k < n && src[i0 + k] == match) ? 1 : 0;
-    int32_t total;
-    block_inclusive_scan(v, s_wave, &total);
-    if (threadIdx.x == 0) partial[blockIdx.x] = total;
-}
-
-// one workgroup; every thread owns a contiguous run of the partial sums
-__global__ __launch_bounds__(kBlock) void scan_bases_kernel(int32_t *partial, int64_t n_blocks, int32_t *total_out)
-{
-    __shared__ int32_t s_wave[kBlock / 64];
-    const int64_t per = (n_blocks + kBlock - 1) / kBlock;
-    const int64_t i0 = (int64_t)threadIdx.x * per, i1 = i0 + per < n_blocks ? i0 + per : n_blocks;
-    int32_t sum = 0;
-    for (int64_t i = i0; i < i1; ++i) sum += partial[i];
-    int32_t total;
-    int32_t run = block_inclusive_scan(sum, s_wave, &total) - sum;
-    for (int64_t i = i0; i < i1; ++i) {
-        const int32_t v = partial[i];
-        partial[i] = run;
-        run += v;
-    }
-    if (threadIdx.x == 0) *total_out = total;
-}
-
-__global__ __launch_bounds__(kBlock) void scan_positions_kernel(const uint8_t *__restrict__ src, int64_t n, uint8_t match,
-                                                                const int32_t *__restrict__ partial,
-                                                                int32_t *__restrict__ pos)
-{
-    __shared__ int32_t s_wave[kBlock / 64];
-    const int64_t i0 = (int64_t)blockIdx.x * kScanItems + (int64_t)threadIdx.x * (kScanItems / kBlock);
-    int32_t c[kScanItems / kBlock], v = 0;
-#pragma unroll
-    for (int k = 0; k < kScanItems / kBlock; ++k) {
-        c[k] = (i0 + k < n && src[i0 + k] == match) ? 1 : 0;
-        v += c[k];
-    }
-    int32_t total;
-    int32_t run = partial[blockIdx.x] + block_inclusive_scan(v, s_wave, &total) - v;
-#pragma unroll
-    for (int k = 0; k < kScanItems / kBlock; ++k) {
-        if (i0 + k < n) pos[i0 + k] = run;
-        run += c[k];
-    }
 }
 
 __global__ void finalize_kernel(Workspace ws, int64_t *counts)
@@ -428,8 +277,6 @@ __global__ __launch_bounds__(kBlock) void mark_hit_faces_kernel(const int32_t *_
     if (out_of_range) tally(out_of_range, bad);
 }
 
-unsigned blocks(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
-
 bool sizes_ok(int64_t V, int64_t F) { return V >= 1 && V < kMaxCount && F >= 0 && F < kMaxCount; }
 
 bool make_job(const double *v, int64_t V, const int64_t *f, int64_t F, const uint8_t *keep, int32_t flags, int64_t M,
@@ -444,19 +291,6 @@ bool make_job(const double *v, int64_t V, const int64_t *f, int64_t F, const uin
     J->flags = flags;
     J->M = (int32_t)M;
     return true;
-}
-
-int scan_flags(const uint8_t *src, int64_t n, uint8_t match, int32_t *partial, int32_t *pos, int32_t *total, hipStream_t s)
-{
-    if (n == 0) return QF_OK;           // the total stays at the zero the workspace's info block starts with
-    const int64_t n_blocks = qf_div_up(n, kScanItems);
-    hipLaunchKernelGGL(scan_partials_kernel, dim3((unsigned)n_blocks), dim3(kBlock), 0, s, src, n, match, partial);
-    QF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(scan_bases_kernel, dim3(1), dim3(kBlock), 0, s, partial, n_blocks, total);
-    QF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(scan_positions_kernel, dim3((unsigned)n_blocks), dim3(kBlock), 0, s, src, n, match, partial, pos);
-    QF_LAUNCH_CHECK();
-    return QF_OK;
 }
 
 }  // namespace
@@ -504,9 +338,9 @@ extern "C" int qf_mesh_compact_count(const double *vertices, int64_t n_vertices,
         hipLaunchKernelGGL(island_kernel, dim3(blocks(F)), dim3(kBlock), 0, s, F, ws, J.M, unref);
         QF_LAUNCH_CHECK();
     }
-    int st = scan_flags(ws.state, F, kAlive, ws.fpart, ws.fpos, &ws.info->face_total, s);
+    int st = scan_bytes(ws.state, F, ItemEquals{kAlive}, ws.fpart, ws.fpos, &ws.info->face_total, s);
     if (st != QF_OK) return st;
-    st = scan_flags(ws.used, V, 1, ws.vpart, ws.vpos, &ws.info->vertex_total, s);
+    st = scan_bytes(ws.used, V, ItemEquals{1}, ws.vpart, ws.vpos, &ws.info->vertex_total, s);
     if (st != QF_OK) return st;
     hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(1), 0, s, ws, counts);
     QF_LAUNCH_CHECK();

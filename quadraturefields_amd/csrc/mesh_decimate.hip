@@ -19,19 +19,15 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
-#include "qf_common.h"
+#include "mesh_device.h"
 #include "qf_mesh_decimate.h"
 #include "qf_mesh_decimate_open.h"
 
 namespace {
 
-constexpr int kBlock = 256;
 constexpr int64_t kMaxCount = int64_t(1) << 31;
 constexpr uint64_t kNone = ~uint64_t(0);        // above every key: keys fit 63 bits
 constexpr double kTau = 1e-6;
-
-inline int64_t align_up(int64_t x) { return (x + 255) & ~int64_t(255); }
-inline int blocks(int64_t n) { return (int)((n + kBlock - 1) / kBlock); }
 
 struct Info {
     unsigned long long candidates, legal, selected, locked, invalid, nonfinite;
@@ -83,31 +79,30 @@ size_t temp_bytes_for(int64_t F, int64_t E, hipStream_t s)
 Workspace carve(void *base, int64_t V, int64_t F, int64_t E, size_t temp)
 {
     Workspace w;
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) { char *p = static_cast<char *>(base) + off; off += align_up(bytes); return p; };
-    w.info = reinterpret_cast<Info *>(take(sizeof(Info)));
-    w.fstart = reinterpret_cast<int64_t *>(take(8 * V));
-    w.fend = reinterpret_cast<int64_t *>(take(8 * V));
-    w.nstart = reinterpret_cast<int64_t *>(take(8 * V));
-    w.nend = reinterpret_cast<int64_t *>(take(8 * V));
-    w.m1 = reinterpret_cast<uint64_t *>(take(8 * V));
-    w.m2 = reinterpret_cast<uint64_t *>(take(8 * V));
-    w.remap = reinterpret_cast<int32_t *>(take(4 * V));
-    w.locked = reinterpret_cast<uint8_t *>(take(V));
-    w.fkey_a = reinterpret_cast<uint64_t *>(take(24 * F));
-    w.fkey_b = reinterpret_cast<uint64_t *>(take(24 * F));
-    w.plane = reinterpret_cast<double *>(take(32 * F));
-    w.nkey_a = reinterpret_cast<uint64_t *>(take(16 * E));
-    w.nkey_b = reinterpret_cast<uint64_t *>(take(16 * E));
-    w.uses = reinterpret_cast<int32_t *>(take(4 * E));
-    w.key = reinterpret_cast<uint64_t *>(take(8 * E));
-    w.skey_a = reinterpret_cast<uint64_t *>(take(8 * E));
-    w.skey_b = reinterpret_cast<uint64_t *>(take(8 * E));
-    w.sval_a = reinterpret_cast<int32_t *>(take(4 * E));
-    w.sval_b = reinterpret_cast<int32_t *>(take(4 * E));
-    w.temp = take((int64_t)temp);
+    QfCarver c{base};
+    w.info = c.take<Info>(1);
+    w.fstart = c.take<int64_t>(V);
+    w.fend = c.take<int64_t>(V);
+    w.nstart = c.take<int64_t>(V);
+    w.nend = c.take<int64_t>(V);
+    w.m1 = c.take<uint64_t>(V);
+    w.m2 = c.take<uint64_t>(V);
+    w.remap = c.take<int32_t>(V);
+    w.locked = c.take<uint8_t>(V);
+    w.fkey_a = c.take<uint64_t>(3 * F);
+    w.fkey_b = c.take<uint64_t>(3 * F);
+    w.plane = c.take<double>(4 * F);
+    w.nkey_a = c.take<uint64_t>(2 * E);
+    w.nkey_b = c.take<uint64_t>(2 * E);
+    w.uses = c.take<int32_t>(E);
+    w.key = c.take<uint64_t>(E);
+    w.skey_a = c.take<uint64_t>(E);
+    w.skey_b = c.take<uint64_t>(E);
+    w.sval_a = c.take<int32_t>(E);
+    w.sval_b = c.take<int32_t>(E);
+    w.temp = c.take<char>((int64_t)temp);
     w.temp_bytes = temp;
-    w.bytes = off;
+    w.bytes = c.off;
     return w;
 }
 
@@ -119,8 +114,6 @@ struct Mesh {
     const double *Q;
     int64_t V, F, E;
 };
-
-__device__ __forceinline__ int64_t gtid() { return (int64_t)blockIdx.x * blockDim.x + threadIdx.x; }
 
 __device__ __forceinline__ bool face_ok(const int64_t *t, int64_t V)
 {
@@ -546,19 +539,18 @@ size_t scan_bytes_for(int64_t E, hipStream_t s)
 Open carve_open(void *base, int64_t first, int64_t V, int64_t E, size_t temp)
 {
     Open o;
-    int64_t off = align_up(first);
-    auto take = [&](int64_t bytes) { char *p = static_cast<char *>(base) + off; off += align_up(bytes); return p; };
-    o.info = reinterpret_cast<OpenInfo *>(take(sizeof(OpenInfo)));
-    o.nb = reinterpret_cast<int32_t *>(take(4 * V));
-    o.bad = reinterpret_cast<uint8_t *>(take(V));
-    o.cls = reinterpret_cast<uint8_t *>(take(V));
-    o.iso = reinterpret_cast<uint8_t *>(take(E));
-    o.weight = reinterpret_cast<int32_t *>(take(4 * E));
-    o.before = reinterpret_cast<int32_t *>(take(4 * E));
-    o.eplane = reinterpret_cast<double *>(take(32 * E));
-    o.temp = take((int64_t)temp);
+    QfCarver c{base, qf_align_up(first)};
+    o.info = c.take<OpenInfo>(1);
+    o.nb = c.take<int32_t>(V);
+    o.bad = c.take<uint8_t>(V);
+    o.cls = c.take<uint8_t>(V);
+    o.iso = c.take<uint8_t>(E);
+    o.weight = c.take<int32_t>(E);
+    o.before = c.take<int32_t>(E);
+    o.eplane = c.take<double>(4 * E);
+    o.temp = c.take<char>((int64_t)temp);
     o.temp_bytes = temp;
-    o.bytes = off;
+    o.bytes = c.off;
     return o;
 }
 

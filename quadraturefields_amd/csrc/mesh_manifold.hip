@@ -7,30 +7,25 @@
 //   classify  per face: validity and degeneracy -> state[f]; parent[c] = c for its three corners;
 //   uses      per half-edge of a proper face: an integer atomicAdd on uses[e], atomicMin / atomicMax of the half-edge id
 //             into lo[e] / hi[e]; for uses == 2 these two are the pair;
-//   link      per edge: the tallies of uses; for uses == 2 the two corner pairs with equal vertex indices are united in a
-//             lock-free union-find over the 3 F corners (mesh_compact.hip's discipline: the larger root is hooked under
-//             the smaller with compare-and-swap, paths are halved with atomicMin, a failed swap goes on from the value
-//             it read, nothing waits), so a class's root is its lowest corner whatever the arrival order;
+//   link      per edge: the tallies of uses; for uses == 2 the two corner pairs with equal vertex indices are united in
+//             mesh_device.h's lock-free union-find over the 3 F corners, so a class's root is its lowest corner whatever
+//             the arrival order;
 //   flatten   per face: parent[c] = root(c) for its corners, a root lowers vmin[vertex] to itself (integer atomicMin: the
 //             lowest class of every vertex), and the faces with a complex edge are tallied;
 //   extras    per corner: flag[c] = 1 iff c is the root of a class that is not vmin of its vertex; split[v] marks the
 //             vertices that have one;
-//   scan      output rank of every extra class: three launches, block scans in the style of scan.hip;
+//   scan      output rank of every extra class: mesh_device.h's three-launch scan;
 //   finalize  the split vertices tallied, then counts[8].
 // Every tally is an integer sum (a wave sum and one atomic per wave), so no result depends on the launch shape or the
 // arrival order.
-#include "qf_common.h"
+#include "mesh_device.h"
 #include "qf_mesh_manifold.h"
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kScanItems = 1024;                // items per workgroup in the scan
 constexpr int64_t kMaxCount = int64_t(1) << 31;
 
 enum : uint8_t { kProper = 0, kDegenerate = 1, kInvalid = 2 };
-
-inline int64_t align_up(int64_t x) { return (x + 255) & ~int64_t(255); }
 
 struct Info {
     unsigned long long n_invalid, n_degenerate, n_split, n_complex_edges, n_complex_faces, n_boundary, n_same_direction;
@@ -58,22 +53,21 @@ struct Workspace {
 Workspace carve(void *base, int64_t V, int64_t F, int64_t E)
 {
     Workspace w;
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) { char *p = static_cast<char *>(base) + off; off += align_up(bytes); return p; };
-    w.info = reinterpret_cast<Info *>(take(sizeof(Info)));
-    w.vmin = reinterpret_cast<uint32_t *>(take(4 * V));
-    w.state = reinterpret_cast<uint8_t *>(take(F));
-    w.parent = reinterpret_cast<int32_t *>(take(12 * F));
-    w.flag = reinterpret_cast<uint8_t *>(take(3 * F));
-    w.pos = reinterpret_cast<int32_t *>(take(12 * F));
-    w.part = reinterpret_cast<int32_t *>(take(4 * qf_div_up(3 * F, kScanItems)));
-    w.emit_bytes = off;
-    w.split = reinterpret_cast<uint8_t *>(take(V));
-    w.uses = reinterpret_cast<int32_t *>(take(4 * E));
-    w.hi = reinterpret_cast<uint32_t *>(take(4 * E));
-    w.zero_bytes = off - w.emit_bytes;
-    w.lo = reinterpret_cast<uint32_t *>(take(4 * E));
-    w.bytes = off;
+    QfCarver c{base};
+    w.info = c.take<Info>(1);
+    w.vmin = c.take<uint32_t>(V);
+    w.state = c.take<uint8_t>(F);
+    w.parent = c.take<int32_t>(3 * F);
+    w.flag = c.take<uint8_t>(3 * F);
+    w.pos = c.take<int32_t>(3 * F);
+    w.part = c.take<int32_t>(qf_div_up(3 * F, kScanItems));
+    w.emit_bytes = c.off;
+    w.split = c.take<uint8_t>(V);
+    w.uses = c.take<int32_t>(E);
+    w.hi = c.take<uint32_t>(E);
+    w.zero_bytes = c.off - w.emit_bytes;
+    w.lo = c.take<uint32_t>(E);
+    w.bytes = c.off;
     return w;
 }
 
@@ -82,49 +76,6 @@ struct Job {
     const int64_t *fe;
     int64_t V, F, E;
 };
-
-__device__ __forceinline__ int64_t gtid() { return (int64_t)blockIdx.x * blockDim.x + threadIdx.x; }
-
-// Sum of `v` over the wave, added to *dst by one lane.  Every lane of the wave must call it.
-__device__ __forceinline__ void tally(unsigned long long *dst, int v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    if ((threadIdx.x & 63) == 0 && v) atomicAdd(dst, (unsigned long long)v);
-}
-
-__device__ __forceinline__ int32_t load_parent(const int32_t *parent, int32_t x)
-{
-    return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// Root of x, halving the path on the way: a parent only ever moves to a smaller corner of the same tree, so the
-// atomicMin keeps every concurrent reader on a valid path.
-__device__ __forceinline__ int32_t uf_find(int32_t *parent, int32_t x)
-{
-    int32_t p = load_parent(parent, x);
-    while (p != x) {
-        const int32_t gp = load_parent(parent, p);
-        if (gp != p) atomicMin(parent + x, gp);
-        x = p;
-        p = gp;
-    }
-    return x;
-}
-
-__device__ __forceinline__ void uf_union(int32_t *parent, int32_t a, int32_t b)
-{
-    while (true) {
-        a = uf_find(parent, a);
-        b = uf_find(parent, b);
-        if (a == b) return;
-        const int32_t hi = a > b ? a : b, lo = a > b ? b : a;
-        const int32_t old = atomicCAS(parent + hi, hi, lo);
-        if (old == hi) return;
-        a = old;            // hi was hooked under `old` by another thread meanwhile: go on from there
-        b = lo;
-    }
-}
 
 __global__ __launch_bounds__(kBlock) void classify_kernel(Job J, Workspace ws)
 {
@@ -201,11 +152,7 @@ __global__ __launch_bounds__(kBlock) void flatten_kernel(Job J, Workspace ws)
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             const int32_t c = (int32_t)(3 * f + k);
-            int32_t x = c, p = load_parent(ws.parent, x);
-            while (p != x) {
-                x = p;
-                p = load_parent(ws.parent, x);
-            }
+            const int32_t x = uf_root(ws.parent, c);
             __hip_atomic_store(ws.parent + c, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (x == c) atomicMin(ws.vmin + J.f[c], (uint32_t)c);
             complex_face |= ws.uses[J.fe[c]] > 2;
@@ -233,80 +180,6 @@ __global__ __launch_bounds__(kBlock) void split_count_kernel(int64_t V, Workspac
 {
     const int64_t v = gtid();
     tally(&ws.info->n_split, v < V && ws.split[v] != 0);
-}
-
-// ---- exclusive scan of the flags over n items: per-workgroup sums, one workgroup scans those, every workgroup scans its
-// own items from its base (scan.hip's three launches)
-__device__ __forceinline__ int32_t block_inclusive_scan(int32_t v, int32_t *s_wave, int32_t *total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int32_t o = __shfl_up(v, off, 64);
-        if (lane >= off) v += o;
-    }
-    if (lane == 63) s_wave[wave] = v;
-    __syncthreads();
-    int32_t base = 0, sum = 0;
-    for (int w = 0; w < kBlock / 64; ++w) {
-        if (w < wave) base += s_wave[w];
-        sum += s_wave[w];
-    }
-    __syncthreads();
-    *total = sum;
-    return v + base;
-}
-
-__global__ __launch_bounds__(kBlock) void scan_partials_kernel(const uint8_t *__restrict__ src, int64_t n,
-                                                               int32_t *__restrict__ partial)
-{
-    __shared__ int32_t s_wave[kBlock / 64];
-    const int64_t i0 = (int64_t)blockIdx.x * kScanItems + (int64_t)threadIdx.x * (kScanItems / kBlock);
-    int32_t v = 0;
-#pragma unroll
-    for (int k = 0; k < kScanItems / kBlock; ++k) v += (i0 + k < n && src[i0 + k]) ? 1 : 0;
-    int32_t total;
-    block_inclusive_scan(v, s_wave, &total);
-    if (threadIdx.x == 0) partial[blockIdx.x] = total;
-}
-
-// one workgroup; every thread owns a contiguous run of the partial sums
-__global__ __launch_bounds__(kBlock) void scan_bases_kernel(int32_t *partial, int64_t n_blocks, int32_t *total_out)
-{
-    __shared__ int32_t s_wave[kBlock / 64];
-    const int64_t per = (n_blocks + kBlock - 1) / kBlock;
-    const int64_t i0 = (int64_t)threadIdx.x * per, i1 = i0 + per < n_blocks ? i0 + per : n_blocks;
-    int32_t sum = 0;
-    for (int64_t i = i0; i < i1; ++i) sum += partial[i];
-    int32_t total;
-    int32_t run = block_inclusive_scan(sum, s_wave, &total) - sum;
-    for (int64_t i = i0; i < i1; ++i) {
-        const int32_t v = partial[i];
-        partial[i] = run;
-        run += v;
-    }
-    if (threadIdx.x == 0) *total_out = total;
-}
-
-__global__ __launch_bounds__(kBlock) void scan_positions_kernel(const uint8_t *__restrict__ src, int64_t n,
-                                                                const int32_t *__restrict__ partial,
-                                                                int32_t *__restrict__ pos)
-{
-    __shared__ int32_t s_wave[kBlock / 64];
-    const int64_t i0 = (int64_t)blockIdx.x * kScanItems + (int64_t)threadIdx.x * (kScanItems / kBlock);
-    int32_t c[kScanItems / kBlock], v = 0;
-#pragma unroll
-    for (int k = 0; k < kScanItems / kBlock; ++k) {
-        c[k] = (i0 + k < n && src[i0 + k]) ? 1 : 0;
-        v += c[k];
-    }
-    int32_t total;
-    int32_t run = partial[blockIdx.x] + block_inclusive_scan(v, s_wave, &total) - v;
-#pragma unroll
-    for (int k = 0; k < kScanItems / kBlock; ++k) {
-        if (i0 + k < n) pos[i0 + k] = run;
-        run += c[k];
-    }
 }
 
 __global__ void finalize_kernel(int64_t V, Workspace ws, int64_t *counts)
@@ -366,24 +239,9 @@ __global__ __launch_bounds__(kBlock) void corner_emit_kernel(const uint64_t *__r
     out_faces[c] = index;
 }
 
-unsigned blocks(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
-
 bool sizes_ok(int64_t V, int64_t F, int64_t E)
 {
     return V >= 1 && V < kMaxCount && F >= 0 && F < kMaxCount && 3 * F < kMaxCount && E >= 0 && E < kMaxCount;
-}
-
-int scan_flags(const uint8_t *src, int64_t n, int32_t *partial, int32_t *pos, int32_t *total, hipStream_t s)
-{
-    if (n == 0) return QF_OK;           // the total stays at the zero the workspace's info block starts with
-    const int64_t n_blocks = qf_div_up(n, kScanItems);
-    hipLaunchKernelGGL(scan_partials_kernel, dim3((unsigned)n_blocks), dim3(kBlock), 0, s, src, n, partial);
-    QF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(scan_bases_kernel, dim3(1), dim3(kBlock), 0, s, partial, n_blocks, total);
-    QF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(scan_positions_kernel, dim3((unsigned)n_blocks), dim3(kBlock), 0, s, src, n, partial, pos);
-    QF_LAUNCH_CHECK();
-    return QF_OK;
 }
 
 }  // namespace
@@ -423,7 +281,7 @@ extern "C" int qf_mesh_manifold_count(const int64_t *faces, int64_t n_faces, int
         QF_LAUNCH_CHECK();
         hipLaunchKernelGGL(extras_kernel, dim3(blocks(3 * F)), dim3(kBlock), 0, s, J, ws);
         QF_LAUNCH_CHECK();
-        const int st = scan_flags(ws.flag, 3 * F, ws.part, ws.pos, &ws.info->extra_total, s);
+        const int st = scan_bytes(ws.flag, 3 * F, ItemNonZero{}, ws.part, ws.pos, &ws.info->extra_total, s);
         if (st != QF_OK) return st;
         hipLaunchKernelGGL(split_count_kernel, dim3(blocks(V)), dim3(kBlock), 0, s, V, ws);
         QF_LAUNCH_CHECK();

@@ -14,7 +14,7 @@
 // non-decreasing in i, so neighbouring lanes walk the same top of the search and end in neighbouring places), three
 // vertex gathers, rules 7 and 8.  The [N,3] rows go through LDS so that every store instruction of a wave writes 512
 // contiguous bytes.  Every tally is an integer sum (a wave reduction and one atomic per wave).
-#include "qf_common.h"
+#include "mesh_device.h"
 #include "qf_mesh_sample.h"
 
 #include <rocprim/device/device_scan.hpp>
@@ -23,10 +23,7 @@
 
 namespace {
 
-constexpr int kBlock = 256;
 constexpr int64_t kMaxCount = int64_t(1) << 31;
-
-inline int64_t align_up(int64_t x) { return (x + 255) & ~int64_t(255); }
 
 struct Info {
     unsigned long long n_nonfinite_vertices, n_invalid_faces, n_bad_weights, n_nonfinite_measures, n_zero;
@@ -53,15 +50,14 @@ size_t temp_bytes_for(int64_t F) { return (size_t)F + 65536; }
 Workspace carve(void *base, int64_t F, size_t temp)
 {
     Workspace w;
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) { char *p = static_cast<char *>(base) + off; off += align_up(bytes); return p; };
-    w.info = reinterpret_cast<Info *>(take(sizeof(Info)));
-    w.measure = reinterpret_cast<double *>(take(8 * F));
-    w.q = reinterpret_cast<uint64_t *>(take(8 * F));
-    w.cum = reinterpret_cast<uint64_t *>(take(8 * F));
-    w.temp = take((int64_t)temp);
+    QfCarver c{base};
+    w.info = c.take<Info>(1);
+    w.measure = c.take<double>(F);
+    w.q = c.take<uint64_t>(F);
+    w.cum = c.take<uint64_t>(F);
+    w.temp = c.take<char>((int64_t)temp);
     w.temp_bytes = temp;
-    w.bytes = off;
+    w.bytes = c.off;
     return w;
 }
 
@@ -71,27 +67,6 @@ struct Job {
     const double *weight;   // NULL: every weight is 1
     int64_t V, F;
 };
-
-__device__ __forceinline__ int64_t gtid() { return (int64_t)blockIdx.x * blockDim.x + threadIdx.x; }
-
-// Sum of `v` over the wave, added to *dst by one lane.  Every lane of the wave must call it.
-__device__ __forceinline__ void tally(unsigned long long *dst, int v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    if ((threadIdx.x & 63) == 0 && v) atomicAdd(dst, (unsigned long long)v);
-}
-
-// Maximum of `v` over the wave, raised into *dst by one lane.  Every lane of the wave must call it.
-__device__ __forceinline__ void tally_max(unsigned long long *dst, unsigned long long v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_xor(v, off, 64);
-        v = o > v ? o : v;
-    }
-    if ((threadIdx.x & 63) == 0 && v) atomicMax(dst, v);
-}
 
 __device__ __forceinline__ bool finite_bits(uint64_t w) { return (w & 0x7ff0000000000000ull) != 0x7ff0000000000000ull; }
 
@@ -241,8 +216,6 @@ __global__ __launch_bounds__(kBlock) void emit_kernel(Job J, Workspace ws, int64
         }
     }
 }
-
-unsigned blocks(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
 bool sizes_ok(int64_t V, int64_t F) { return V >= 1 && V < kMaxCount && F >= 1 && 3 * F < kMaxCount; }
 

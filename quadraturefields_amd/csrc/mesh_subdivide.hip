@@ -5,140 +5,25 @@
 //
 // Passes of qf_mesh_edges_count (one stream, no host wait):
 //   classify  per face: validity, degenerate -> state[f];
-//   insert    an open-addressing hash table of half-edge ids keyed by the pair (min, max), at least 6 F slots: a half-edge
-//             claims the first empty slot of its probe sequence with compare-and-swap, or lowers the id of the slot that
-//             already holds its pair with an integer atomicMin, and adds one to the slot's use count.  A slot's pair never
-//             changes once it is claimed and a failed swap goes on with the id it read, so nothing waits (the design of
-//             mesh_compact.hip's duplicate pass);
+//   insert    an open-addressing hash table of half-edge ids keyed by the pair (min, max), at least 6 F slots, filled
+//             with mesh_device.h's claim-or-lower insert; a half-edge also adds one to its slot's use count;
 //   flag      first[h] = the slot of h holds h: the lowest half-edge of every pair, whatever the arrival order; the
 //             boundary edges are those whose use count is one;
-//   scan      exclusive scan of first[] over the half-edges, three launches in the style of scan.hip: the edge ids;
+//   scan      exclusive scan of first[] over the half-edges, mesh_device.h's three launches: the edge ids;
 //   finalize  counts[4].
 // qf_mesh_subdivide_count: classify (validity, marked edges per face -> children per face; the lowest half-edge of every
 // marked edge with an integer atomicMin, which is the one thread that writes the new vertex), the scans of the children and
 // of the marks, finalize.  Every tally is an integer sum, so no result depends on the launch shape or the arrival order.
-#include "qf_common.h"
+#include "mesh_device.h"
 #include "qf_mesh_subdivide.h"
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kScanItems = 1024;                // items per workgroup in the scans
-constexpr int kPer = kScanItems / kBlock;
 constexpr int64_t kMaxCount = int64_t(1) << 31;
 constexpr int64_t kMaxEdgeFaces = (kMaxCount - 1) / 3;      // 3 F < 2^31: a half-edge id fits 31 bits
 constexpr int64_t kMaxSplitFaces = int64_t(1) << 29;        // 4 F < 2^31
-constexpr uint32_t kEmpty = 0xffffffffu;        // an unclaimed slot of the edge table
 
 enum : uint8_t { kValid = 0, kDegenerate = 1, kInvalid = 2 };
-
-inline int64_t align_up(int64_t x) { return (x + 255) & ~int64_t(255); }
-
-__device__ __forceinline__ int64_t gtid() { return (int64_t)blockIdx.x * blockDim.x + threadIdx.x; }
-
-// Sum of `v` over the wave, added to *dst by one lane.  Every lane of the wave must call it.
-__device__ __forceinline__ void tally(unsigned long long *dst, int v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    if ((threadIdx.x & 63) == 0 && v) atomicAdd(dst, (unsigned long long)v);
-}
-
-// ---- exclusive scan of uint8 items (their values, or with `flags` whether they are not zero) over n items:
-// per-workgroup sums, one workgroup scans those, every workgroup scans its own items from its base
-__device__ __forceinline__ int32_t block_inclusive_scan(int32_t v, int32_t *s_wave, int32_t *total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int32_t o = __shfl_up(v, off, 64);
-        if (lane >= off) v += o;
-    }
-    if (lane == 63) s_wave[wave] = v;
-    __syncthreads();
-    int32_t base = 0, sum = 0;
-    for (int w = 0; w < kBlock / 64; ++w) {
-        if (w < wave) base += s_wave[w];
-        sum += s_wave[w];
-    }
-    __syncthreads();
-    *total = sum;
-    return v + base;
-}
-
-__device__ __forceinline__ int32_t scan_item(const uint8_t *src, int64_t i, int64_t n, int flags)
-{
-    if (i >= n) return 0;
-    const int32_t v = src[i];
-    return flags ? (v != 0) : v;
-}
-
-__global__ __launch_bounds__(kBlock) void scan_partials_kernel(const uint8_t *__restrict__ src, int64_t n, int flags,
-                                                               int32_t *__restrict__ partial)
-{
-    __shared__ int32_t s_wave[kBlock / 64];
-    const int64_t i0 = (int64_t)blockIdx.x * kScanItems + (int64_t)threadIdx.x * kPer;
-    int32_t v = 0;
-#pragma unroll
-    for (int k = 0; k < kPer; ++k) v += scan_item(src, i0 + k, n, flags);
-    int32_t total;
-    block_inclusive_scan(v, s_wave, &total);
-    if (threadIdx.x == 0) partial[blockIdx.x] = total;
-}
-
-// one workgroup; every thread owns a contiguous run of the partial sums
-__global__ __launch_bounds__(kBlock) void scan_bases_kernel(int32_t *partial, int64_t n_blocks, int32_t *total_out)
-{
-    __shared__ int32_t s_wave[kBlock / 64];
-    const int64_t per = (n_blocks + kBlock - 1) / kBlock;
-    const int64_t i0 = (int64_t)threadIdx.x * per, i1 = i0 + per < n_blocks ? i0 + per : n_blocks;
-    int32_t sum = 0;
-    for (int64_t i = i0; i < i1; ++i) sum += partial[i];
-    int32_t total;
-    int32_t run = block_inclusive_scan(sum, s_wave, &total) - sum;
-    for (int64_t i = i0; i < i1; ++i) {
-        const int32_t v = partial[i];
-        partial[i] = run;
-        run += v;
-    }
-    if (threadIdx.x == 0) *total_out = total;
-}
-
-__global__ __launch_bounds__(kBlock) void scan_positions_kernel(const uint8_t *__restrict__ src, int64_t n, int flags,
-                                                                const int32_t *__restrict__ partial,
-                                                                int32_t *__restrict__ pos)
-{
-    __shared__ int32_t s_wave[kBlock / 64];
-    const int64_t i0 = (int64_t)blockIdx.x * kScanItems + (int64_t)threadIdx.x * kPer;
-    int32_t c[kPer], v = 0;
-#pragma unroll
-    for (int k = 0; k < kPer; ++k) {
-        c[k] = scan_item(src, i0 + k, n, flags);
-        v += c[k];
-    }
-    int32_t total;
-    int32_t run = partial[blockIdx.x] + block_inclusive_scan(v, s_wave, &total) - v;
-#pragma unroll
-    for (int k = 0; k < kPer; ++k) {
-        if (i0 + k < n) pos[i0 + k] = run;
-        run += c[k];
-    }
-}
-
-unsigned blocks(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
-
-int scan_bytes(const uint8_t *src, int64_t n, int flags, int32_t *partial, int32_t *pos, int32_t *total, hipStream_t s)
-{
-    if (n == 0) return QF_OK;           // the total stays at the zero the workspace's info block starts with
-    const int64_t n_blocks = qf_div_up(n, kScanItems);
-    hipLaunchKernelGGL(scan_partials_kernel, dim3((unsigned)n_blocks), dim3(kBlock), 0, s, src, n, flags, partial);
-    QF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(scan_bases_kernel, dim3(1), dim3(kBlock), 0, s, partial, n_blocks, total);
-    QF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(scan_positions_kernel, dim3((unsigned)n_blocks), dim3(kBlock), 0, s, src, n, flags, partial, pos);
-    QF_LAUNCH_CHECK();
-    return QF_OK;
-}
 
 // validity and degeneracy of face f; the three indices as 32-bit values when valid
 __device__ __forceinline__ uint8_t load_face(const int64_t *faces, int64_t f, int64_t V, int32_t v[3])
@@ -175,19 +60,17 @@ EdgeWorkspace carve_edges(void *base, int64_t F)
 {
     EdgeWorkspace w;
     const int64_t H = 3 * F;
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) { char *p = static_cast<char *>(base) + off; off += align_up(bytes); return p; };
-    w.info = reinterpret_cast<EdgeInfo *>(take(sizeof(EdgeInfo)));
-    w.state = reinterpret_cast<uint8_t *>(take(F));
-    w.slots = 64;
-    while (w.slots < 2 * H) w.slots <<= 1;
-    w.table = reinterpret_cast<uint32_t *>(take(4 * w.slots));
-    w.uses = reinterpret_cast<uint32_t *>(take(4 * w.slots));
-    w.slot = reinterpret_cast<uint32_t *>(take(4 * H));
-    w.first = reinterpret_cast<uint8_t *>(take(H));
-    w.pos = reinterpret_cast<int32_t *>(take(4 * H));
-    w.part = reinterpret_cast<int32_t *>(take(4 * qf_div_up(H, kScanItems)));
-    w.bytes = off;
+    QfCarver c{base};
+    w.info = c.take<EdgeInfo>(1);
+    w.state = c.take<uint8_t>(F);
+    w.slots = table_slots(H);
+    w.table = c.take<uint32_t>(w.slots);
+    w.uses = c.take<uint32_t>(w.slots);
+    w.slot = c.take<uint32_t>(H);
+    w.first = c.take<uint8_t>(H);
+    w.pos = c.take<int32_t>(H);
+    w.part = c.take<int32_t>(qf_div_up(H, kScanItems));
+    w.bytes = c.off;
     return w;
 }
 
@@ -221,26 +104,15 @@ __global__ __launch_bounds__(kBlock) void edge_classify_kernel(const int64_t *fa
     tally(&ws.info->n_degenerate, degenerate);
 }
 
-// At most 3 F of the >= 6 F slots are ever claimed, so the walk ends.
+// A half-edge of a valid face enters the table under its pair (claim_or_lower of mesh_device.h: at most 3 F of the
+// >= 6 F slots are ever claimed).
 __global__ __launch_bounds__(kBlock) void edge_insert_kernel(const int64_t *faces, int64_t H, EdgeWorkspace ws)
 {
     const int64_t h = gtid();
     if (h >= H || ws.info->n_invalid != 0 || ws.state[h / 3] != kValid) return;
     const uint64_t key = pair_key(faces, (uint32_t)h);
-    const uint64_t wrap = (uint64_t)ws.slots - 1;
-    uint64_t s = pair_hash(key) & wrap;
-    while (true) {
-        uint32_t g = __hip_atomic_load(ws.table + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (g == kEmpty) {
-            g = atomicCAS(ws.table + s, kEmpty, (uint32_t)h);
-            if (g == kEmpty) break;
-        }
-        if (pair_key(faces, g) == key) {
-            if ((uint32_t)h < g) atomicMin(ws.table + s, (uint32_t)h);
-            break;
-        }
-        s = (s + 1) & wrap;
-    }
+    const uint64_t s = claim_or_lower(ws.table, (uint64_t)ws.slots - 1, pair_hash(key), (uint32_t)h,
+                                      [&](uint32_t g) { return pair_key(faces, g) == key; });
     atomicAdd(ws.uses + s, 1u);
     ws.slot[h] = (uint32_t)s;
 }
@@ -313,16 +185,15 @@ struct SplitWorkspace {
 SplitWorkspace carve_split(void *base, int64_t F, int64_t E)
 {
     SplitWorkspace w;
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) { char *p = static_cast<char *>(base) + off; off += align_up(bytes); return p; };
-    w.info = reinterpret_cast<SplitInfo *>(take(sizeof(SplitInfo)));
-    w.children = reinterpret_cast<uint8_t *>(take(F));
-    w.fpos = reinterpret_cast<int32_t *>(take(4 * F));
-    w.epos = reinterpret_cast<int32_t *>(take(4 * E));
-    w.owner = reinterpret_cast<int32_t *>(take(4 * E));
-    w.fpart = reinterpret_cast<int32_t *>(take(4 * qf_div_up(F, kScanItems)));
-    w.epart = reinterpret_cast<int32_t *>(take(4 * qf_div_up(E, kScanItems)));
-    w.bytes = off;
+    QfCarver c{base};
+    w.info = c.take<SplitInfo>(1);
+    w.children = c.take<uint8_t>(F);
+    w.fpos = c.take<int32_t>(F);
+    w.epos = c.take<int32_t>(E);
+    w.owner = c.take<int32_t>(E);
+    w.fpart = c.take<int32_t>(qf_div_up(F, kScanItems));
+    w.epart = c.take<int32_t>(qf_div_up(E, kScanItems));
+    w.bytes = c.off;
     return w;
 }
 
@@ -539,7 +410,7 @@ extern "C" int qf_mesh_edges_count(const int64_t *faces, int64_t n_faces, int64_
         hipLaunchKernelGGL(edge_flag_kernel, dim3(blocks(H)), dim3(kBlock), 0, s, H, ws);
         QF_LAUNCH_CHECK();
     }
-    const int st = scan_bytes(ws.first, H, 1, ws.part, ws.pos, &ws.info->edge_total, s);
+    const int st = scan_bytes(ws.first, H, ItemNonZero{}, ws.part, ws.pos, &ws.info->edge_total, s);
     if (st != QF_OK) return st;
     hipLaunchKernelGGL(edge_finalize_kernel, dim3(1), dim3(1), 0, s, ws, counts);
     QF_LAUNCH_CHECK();
@@ -587,9 +458,9 @@ extern "C" int qf_mesh_subdivide_count(const int64_t *faces, int64_t n_faces, in
         hipLaunchKernelGGL(split_classify_kernel, dim3(blocks(J.F)), dim3(kBlock), 0, s, J, ws);
         QF_LAUNCH_CHECK();
     }
-    int st = scan_bytes(ws.children, J.F, 0, ws.fpart, ws.fpos, &ws.info->face_total, s);
+    int st = scan_bytes(ws.children, J.F, ItemValue{}, ws.fpart, ws.fpos, &ws.info->face_total, s);
     if (st != QF_OK) return st;
-    st = scan_bytes(edge_mark, J.E, 1, ws.epart, ws.epos, &ws.info->mark_total, s);
+    st = scan_bytes(edge_mark, J.E, ItemNonZero{}, ws.epart, ws.epos, &ws.info->mark_total, s);
     if (st != QF_OK) return st;
     hipLaunchKernelGGL(split_finalize_kernel, dim3(1), dim3(1), 0, s, ws, J.V, J.F, counts);
     QF_LAUNCH_CHECK();

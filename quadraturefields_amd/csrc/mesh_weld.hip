@@ -6,24 +6,22 @@
 //   cells     per vertex: finite test; the key (h > 0: the integer cell floor(x / s) per axis; h == 0: the three
 //             coordinates' bits with -0.0 made +0.0), the loose and out-of-range tallies, parent[v] = v;
 //   faces     per face: the invalid tally;
-//   insert    per finite vertex: an open-addressing table of >= 2 V slots keyed by the key, under the discipline of
-//             mesh_compact.hip's duplicate table: a slot is claimed with compare-and-swap and its key never changes, its
-//             vertex id is lowered with an integer atomicMin; with h > 0 the vertex is also pushed on the slot's list
-//             with one atomicExch (the list is read only in the next launch);
+//   insert    per finite vertex: an open-addressing table of >= 2 V slots keyed by the key, filled with mesh_device.h's
+//             claim-or-lower insert, so a slot ends with the lowest vertex id of its key; with h > 0 the vertex is also
+//             pushed on the slot's list with one atomicExch (the list is read only in the next launch);
 //   link      h > 0 only, per finite vertex: the members with a lower index of the 27 cells around its own are tested
-//             under rule 2 and united in a lock-free union-find (the larger root is hooked under the smaller with
-//             compare-and-swap, paths are halved with atomicMin, a failed swap goes on from the value it read, nothing
-//             waits), so a class's root is its lowest index whatever the arrival order; the arithmetic is skipped when
-//             both already share a root.  Quadratic in a cell's population, which counts[4] reports;
+//             under rule 2 and united in mesh_device.h's lock-free union-find, so a class's root is its lowest index
+//             whatever the arrival order; the arithmetic is skipped when both already share a root.  Quadratic in a
+//             cell's population, which counts[4] reports;
 //   flatten   per vertex: parent[v] = root (h == 0: the lowest id of its slot, whose members are equal by construction,
 //             so the pass is linear whatever the input), and the class sizes (integer atomicAdd);
 //   roots     per vertex: flag[v] = 1 iff v is a root; the classes of two or more and the largest class;
-//   scan      output row of every root: three launches, block scans in the style of scan.hip;
+//   scan      output row of every root: mesh_device.h's three-launch scan;
 //   tally     per face: faces that were not degenerate and now are;
 //   finalize  counts[8].
 // Every tally is an integer sum or maximum (a wave reduction and one atomic per wave), so no result depends on the
 // launch shape or the arrival order.
-#include "qf_common.h"
+#include "mesh_device.h"
 #include "qf_mesh_weld.h"
 
 #include <cfloat>
@@ -31,15 +29,10 @@
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kScanItems = 1024;                // items per workgroup in the scan
 constexpr int64_t kMaxCount = int64_t(1) << 31;
-constexpr uint32_t kEmpty = 0xffffffffu;        // an unclaimed slot, and the end of a slot's list (a vertex id is < 2^31)
 constexpr double kCellLimit = 2251799813685248.0;   // 2^51
 
 enum : uint8_t { kFinite = 0, kLoose = 1, kOutOfRange = 2 };
-
-inline int64_t align_up(int64_t x) { return (x + 255) & ~int64_t(255); }
 
 struct Info {
     unsigned long long n_invalid, n_out_of_range, n_loose, n_multi, n_collapsed;
@@ -64,32 +57,24 @@ struct Workspace {
     int64_t bytes;
 };
 
-int64_t table_slots(int64_t V)
-{
-    int64_t n = 64;
-    while (n < 2 * V) n <<= 1;
-    return n;
-}
-
 Workspace carve(void *base, int64_t V)
 {
     Workspace w;
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) { char *p = static_cast<char *>(base) + off; off += align_up(bytes); return p; };
-    w.info = reinterpret_cast<Info *>(take(sizeof(Info)));
-    w.parent = reinterpret_cast<int32_t *>(take(4 * V));
-    w.flag = reinterpret_cast<uint8_t *>(take(V));
-    w.pos = reinterpret_cast<int32_t *>(take(4 * V));
-    w.part = reinterpret_cast<int32_t *>(take(4 * qf_div_up(V, kScanItems)));
-    w.state = reinterpret_cast<uint8_t *>(take(V));
-    w.key = reinterpret_cast<int64_t *>(take(24 * V));
-    w.slot = reinterpret_cast<uint32_t *>(take(4 * V));
-    w.next = reinterpret_cast<uint32_t *>(take(4 * V));
-    w.size = reinterpret_cast<int32_t *>(take(4 * V));
+    QfCarver c{base};
+    w.info = c.take<Info>(1);
+    w.parent = c.take<int32_t>(V);
+    w.flag = c.take<uint8_t>(V);
+    w.pos = c.take<int32_t>(V);
+    w.part = c.take<int32_t>(qf_div_up(V, kScanItems));
+    w.state = c.take<uint8_t>(V);
+    w.key = c.take<int64_t>(3 * V);
+    w.slot = c.take<uint32_t>(V);
+    w.next = c.take<uint32_t>(V);
+    w.size = c.take<int32_t>(V);
     w.slots = table_slots(V);
-    w.table = reinterpret_cast<uint32_t *>(take(4 * w.slots));      // 4 * slots is a multiple of 256: head follows at once
-    w.head = reinterpret_cast<uint32_t *>(take(4 * w.slots));
-    w.bytes = off;
+    w.table = c.take<uint32_t>(w.slots);        // 4 * slots is a multiple of 256: head follows at once
+    w.head = c.take<uint32_t>(w.slots);
+    w.bytes = c.off;
     return w;
 }
 
@@ -101,61 +86,9 @@ struct Job {
     double h2;              // h * h
 };
 
-__device__ __forceinline__ int64_t gtid() { return (int64_t)blockIdx.x * blockDim.x + threadIdx.x; }
-
-// Sum of `v` over the wave, added to *dst by one lane.  Every lane of the wave must call it.
-__device__ __forceinline__ void tally(unsigned long long *dst, int v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    if ((threadIdx.x & 63) == 0 && v) atomicAdd(dst, (unsigned long long)v);
-}
-
-// Maximum of `v` (>= 0) over the wave, raised into *dst by one lane.  Every lane of the wave must call it.
-__device__ __forceinline__ void tally_max(unsigned int *dst, int v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const int o = __shfl_xor(v, off, 64);
-        v = o > v ? o : v;
-    }
-    if ((threadIdx.x & 63) == 0 && v) atomicMax(dst, (unsigned int)v);
-}
-
 __device__ __forceinline__ bool refused(const Workspace &ws)
 {
     return ws.info->n_invalid != 0 || ws.info->n_out_of_range != 0;
-}
-
-__device__ __forceinline__ int32_t load_parent(const int32_t *parent, int32_t x)
-{
-    return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// Root of x, halving the path on the way: a parent only ever moves to a smaller vertex of the same tree, so the
-// atomicMin keeps every concurrent reader on a valid path.
-__device__ __forceinline__ int32_t uf_find(int32_t *parent, int32_t x)
-{
-    int32_t p = load_parent(parent, x);
-    while (p != x) {
-        const int32_t gp = load_parent(parent, p);
-        if (gp != p) atomicMin(parent + x, gp);
-        x = p;
-        p = gp;
-    }
-    return x;
-}
-
-// a and b are roots as far as the caller saw
-__device__ __forceinline__ void uf_union(int32_t *parent, int32_t a, int32_t b)
-{
-    while (a != b) {
-        const int32_t hi = a > b ? a : b, lo = a > b ? b : a;
-        const int32_t old = atomicCAS(parent + hi, hi, lo);
-        if (old == hi) return;
-        a = uf_find(parent, old);      // hi was hooked under `old` by another thread meanwhile: go on from there
-        b = uf_find(parent, lo);
-    }
 }
 
 __device__ __forceinline__ uint64_t key_hash(int64_t a, int64_t b, int64_t c)
@@ -222,46 +155,33 @@ __global__ __launch_bounds__(kBlock) void faces_kernel(Job J, Workspace ws)
     tally(&ws.info->n_invalid, invalid);
 }
 
-// A finite vertex walks its probe sequence to the first slot that is empty (claimed with compare-and-swap) or holds a
-// vertex with the same key (whose id it lowers to its own if smaller).  A slot's key never changes once it is claimed,
-// and a failed swap goes on with the id it read: nothing waits.  At most V of the >= 2 V slots are ever claimed, so the
-// walk ends.
+// whether vertex g has the key (kx, ky, kz)
+struct SameKey {
+    const int64_t *key;
+    int64_t kx, ky, kz;
+    __device__ __forceinline__ bool operator()(uint32_t g) const
+    {
+        const int64_t *k = key + 3 * (int64_t)g;
+        return k[0] == kx && k[1] == ky && k[2] == kz;
+    }
+};
+
+// A finite vertex enters the table under its key (claim_or_lower of mesh_device.h).
 __global__ __launch_bounds__(kBlock) void insert_kernel(Job J, Workspace ws)
 {
     const int64_t v = gtid();
     if (v >= J.V || refused(ws) || ws.state[v] != kFinite) return;
     const int64_t kx = ws.key[3 * v], ky = ws.key[3 * v + 1], kz = ws.key[3 * v + 2];
-    const uint64_t wrap = (uint64_t)ws.slots - 1;
-    uint64_t s = key_hash(kx, ky, kz) & wrap;
-    while (true) {
-        uint32_t g = __hip_atomic_load(ws.table + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (g == kEmpty) {
-            g = atomicCAS(ws.table + s, kEmpty, (uint32_t)v);
-            if (g == kEmpty) break;
-        }
-        const int64_t *k = ws.key + 3 * (int64_t)g;
-        if (k[0] == kx && k[1] == ky && k[2] == kz) {
-            if ((uint32_t)v < g) atomicMin(ws.table + s, (uint32_t)v);
-            break;
-        }
-        s = (s + 1) & wrap;
-    }
+    const uint64_t s = claim_or_lower(ws.table, (uint64_t)ws.slots - 1, key_hash(kx, ky, kz), (uint32_t)v,
+                                      SameKey{ws.key, kx, ky, kz});
     ws.slot[v] = (uint32_t)s;
     if (J.cell > 0.0) ws.next[v] = atomicExch(ws.head + s, (uint32_t)v);
 }
 
-// The slot that holds the key, or kEmpty: the probe sequence of an absent key ends at an unclaimed slot.
-__device__ __forceinline__ uint32_t find_slot(const Workspace &ws, int64_t kx, int64_t ky, int64_t kz)
+// The slot that holds the key, or kEmpty.
+__device__ __forceinline__ uint32_t key_slot(const Workspace &ws, int64_t kx, int64_t ky, int64_t kz)
 {
-    const uint64_t wrap = (uint64_t)ws.slots - 1;
-    uint64_t s = key_hash(kx, ky, kz) & wrap;
-    while (true) {
-        const uint32_t g = ws.table[s];
-        if (g == kEmpty) return kEmpty;
-        const int64_t *k = ws.key + 3 * (int64_t)g;
-        if (k[0] == kx && k[1] == ky && k[2] == kz) return (uint32_t)s;
-        s = (s + 1) & wrap;
-    }
+    return find_slot(ws.table, (uint64_t)ws.slots - 1, key_hash(kx, ky, kz), SameKey{ws.key, kx, ky, kz});
 }
 
 __global__ __launch_bounds__(kBlock) void link_kernel(Job J, Workspace ws)
@@ -275,7 +195,7 @@ __global__ __launch_bounds__(kBlock) void link_kernel(Job J, Workspace ws)
         const bool lowest = ws.table[own] == (uint32_t)v;          // the cell's lowest member counts its population
         for (int n = 0; n < 27; ++n) {
             const int ox = n % 3 - 1, oy = (n / 3) % 3 - 1, oz = n / 9 - 1;
-            const uint32_t s = n == 13 ? own : find_slot(ws, kx + ox, ky + oy, kz + oz);
+            const uint32_t s = n == 13 ? own : key_slot(ws, kx + ox, ky + oy, kz + oz);
             if (s == kEmpty) continue;
             for (uint32_t u = ws.head[s]; u != kEmpty; u = ws.next[u]) {
                 if (n == 13 && lowest) ++population;
@@ -283,7 +203,7 @@ __global__ __launch_bounds__(kBlock) void link_kernel(Job J, Workspace ws)
                 const int32_t ru = uf_find(ws.parent, (int32_t)u), rv = uf_find(ws.parent, (int32_t)v);
                 if (ru == rv) continue;
                 const double dx = x - J.v[3 * (int64_t)u], dy = y - J.v[3 * (int64_t)u + 1], dz = z - J.v[3 * (int64_t)u + 2];
-                if (((dx * dx + dy * dy) + dz * dz) <= J.h2) uf_union(ws.parent, ru, rv);
+                if (((dx * dx + dy * dy) + dz * dz) <= J.h2) uf_union_roots(ws.parent, ru, rv);
             }
         }
     }
@@ -296,15 +216,10 @@ __global__ __launch_bounds__(kBlock) void flatten_kernel(Job J, Workspace ws)
     if (v >= J.V || refused(ws)) return;
     int32_t x = (int32_t)v;
     if (ws.state[v] == kFinite) {
-        if (J.cell > 0.0) {
-            int32_t p = load_parent(ws.parent, x);
-            while (p != x) {
-                x = p;
-                p = load_parent(ws.parent, x);
-            }
-        } else {
+        if (J.cell > 0.0)
+            x = uf_root(ws.parent, x);
+        else
             x = (int32_t)ws.table[ws.slot[v]];
-        }
     }
     __hip_atomic_store(ws.parent + v, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     atomicAdd(ws.size + x, 1);
@@ -338,80 +253,6 @@ __global__ __launch_bounds__(kBlock) void face_tally_kernel(Job J, Workspace ws)
         }
     }
     tally(&ws.info->n_collapsed, collapsed);
-}
-
-// ---- exclusive scan of the flags over n items: per-workgroup sums, one workgroup scans those, every workgroup scans its
-// own items from its base (scan.hip's three launches)
-__device__ __forceinline__ int32_t block_inclusive_scan(int32_t v, int32_t *s_wave, int32_t *total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int32_t o = __shfl_up(v, off, 64);
-        if (lane >= off) v += o;
-    }
-    if (lane == 63) s_wave[wave] = v;
-    __syncthreads();
-    int32_t base = 0, sum = 0;
-    for (int w = 0; w < kBlock / 64; ++w) {
-        if (w < wave) base += s_wave[w];
-        sum += s_wave[w];
-    }
-    __syncthreads();
-    *total = sum;
-    return v + base;
-}
-
-__global__ __launch_bounds__(kBlock) void scan_partials_kernel(const uint8_t *__restrict__ src, int64_t n,
-                                                               int32_t *__restrict__ partial)
-{
-    __shared__ int32_t s_wave[kBlock / 64];
-    const int64_t i0 = (int64_t)blockIdx.x * kScanItems + (int64_t)threadIdx.x * (kScanItems / kBlock);
-    int32_t v = 0;
-#pragma unroll
-    for (int k = 0; k < kScanItems / kBlock; ++k) v += (i0 + k < n && src[i0 + k]) ? 1 : 0;
-    int32_t total;
-    block_inclusive_scan(v, s_wave, &total);
-    if (threadIdx.x == 0) partial[blockIdx.x] = total;
-}
-
-// one workgroup; every thread owns a contiguous run of the partial sums
-__global__ __launch_bounds__(kBlock) void scan_bases_kernel(int32_t *partial, int64_t n_blocks, int32_t *total_out)
-{
-    __shared__ int32_t s_wave[kBlock / 64];
-    const int64_t per = (n_blocks + kBlock - 1) / kBlock;
-    const int64_t i0 = (int64_t)threadIdx.x * per, i1 = i0 + per < n_blocks ? i0 + per : n_blocks;
-    int32_t sum = 0;
-    for (int64_t i = i0; i < i1; ++i) sum += partial[i];
-    int32_t total;
-    int32_t run = block_inclusive_scan(sum, s_wave, &total) - sum;
-    for (int64_t i = i0; i < i1; ++i) {
-        const int32_t v = partial[i];
-        partial[i] = run;
-        run += v;
-    }
-    if (threadIdx.x == 0) *total_out = total;
-}
-
-__global__ __launch_bounds__(kBlock) void scan_positions_kernel(const uint8_t *__restrict__ src, int64_t n,
-                                                                const int32_t *__restrict__ partial,
-                                                                int32_t *__restrict__ pos)
-{
-    __shared__ int32_t s_wave[kBlock / 64];
-    const int64_t i0 = (int64_t)blockIdx.x * kScanItems + (int64_t)threadIdx.x * (kScanItems / kBlock);
-    int32_t c[kScanItems / kBlock], v = 0;
-#pragma unroll
-    for (int k = 0; k < kScanItems / kBlock; ++k) {
-        c[k] = (i0 + k < n && src[i0 + k]) ? 1 : 0;
-        v += c[k];
-    }
-    int32_t total;
-    int32_t run = partial[blockIdx.x] + block_inclusive_scan(v, s_wave, &total) - v;
-#pragma unroll
-    for (int k = 0; k < kScanItems / kBlock; ++k) {
-        if (i0 + k < n) pos[i0 + k] = run;
-        run += c[k];
-    }
 }
 
 __global__ void finalize_kernel(Job J, Workspace ws, int64_t *counts)
@@ -459,21 +300,7 @@ __global__ __launch_bounds__(kBlock) void face_emit_kernel(const int64_t *__rest
     out_faces[c] = ws.pos[ws.parent[faces[c]]];
 }
 
-unsigned blocks(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
-
 bool sizes_ok(int64_t V, int64_t F) { return V >= 1 && V < kMaxCount && F >= 0 && F < kMaxCount; }
-
-int scan_flags(const uint8_t *src, int64_t n, int32_t *partial, int32_t *pos, int32_t *total, hipStream_t s)
-{
-    const int64_t n_blocks = qf_div_up(n, kScanItems);
-    hipLaunchKernelGGL(scan_partials_kernel, dim3((unsigned)n_blocks), dim3(kBlock), 0, s, src, n, partial);
-    QF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(scan_bases_kernel, dim3(1), dim3(kBlock), 0, s, partial, n_blocks, total);
-    QF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(scan_positions_kernel, dim3((unsigned)n_blocks), dim3(kBlock), 0, s, src, n, partial, pos);
-    QF_LAUNCH_CHECK();
-    return QF_OK;
-}
 
 }  // namespace
 
@@ -518,7 +345,7 @@ extern "C" int qf_mesh_weld_count(const double *vertices, int64_t n_vertices, co
     QF_LAUNCH_CHECK();
     hipLaunchKernelGGL(roots_kernel, dim3(blocks(V)), dim3(kBlock), 0, s, J, ws);
     QF_LAUNCH_CHECK();
-    const int st = scan_flags(ws.flag, V, ws.part, ws.pos, &ws.info->root_total, s);
+    const int st = scan_bytes(ws.flag, V, ItemNonZero{}, ws.part, ws.pos, &ws.info->root_total, s);
     if (st != QF_OK) return st;
     if (F > 0) {
         hipLaunchKernelGGL(face_tally_kernel, dim3(blocks(F)), dim3(kBlock), 0, s, J, ws);

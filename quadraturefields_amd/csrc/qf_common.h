@@ -34,6 +34,24 @@ int qf_cu_count_cached();
 
 static inline int64_t qf_div_up(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// Every array of a workspace starts on a multiple of 256 bytes.
+static inline int64_t qf_align_up(int64_t x) { return (x + 255) & ~int64_t(255); }
+
+// Carves one workspace allocation into its arrays: take<T>(count) returns the next array and advances `off` by its
+// byte size rounded up with qf_align_up.  A null base is fine when only the sizes matter (the *_workspace_bytes entry
+// points): `off` is the bytes taken so far and may be read between two takes.
+struct QfCarver {
+    void *base;
+    int64_t off = 0;
+    template <typename T>
+    T *take(int64_t count)
+    {
+        char *p = static_cast<char *>(base) + off;
+        off += qf_align_up((int64_t)sizeof(T) * count);
+        return reinterpret_cast<T *>(p);
+    }
+};
+
 // Grid size for a grid-stride elementwise kernel: enough blocks to fill the chip, capped.
 static inline int qf_grid_1d(int64_t n, int block, int blocks_per_cu = 8)
 {

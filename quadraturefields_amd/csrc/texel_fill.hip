@@ -30,8 +30,6 @@ constexpr int kScanItems = 4;                        // elements per thread of t
 constexpr int kScanTile = kBlock * kScanItems;
 constexpr int kResolveTexels = 4;                    // texels per lane of the resolve pass (12 floats = 3 x 16 B)
 
-inline int64_t align_up(int64_t x) { return (x + 255) & ~int64_t(255); }
-
 struct Workspace {
     int32_t *owner, *line_owner;
     int4 *qrec;          // [F][2]: (q0r, q0c, q1r, q1c), (q2r, q2c, bbox row min, bbox col min)
@@ -46,16 +44,15 @@ Workspace carve(void *base, int64_t hw, int64_t F)
 {
     Workspace w;
     const int64_t nb = qf_div_up(F, kScanTile);
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) { char *p = static_cast<char *>(base) + off; off += align_up(bytes); return p; };
-    w.owner = reinterpret_cast<int32_t *>(take(4 * hw));
-    w.line_owner = reinterpret_cast<int32_t *>(take(4 * hw));
-    w.qrec = reinterpret_cast<int4 *>(take(32 * F));
-    w.cum = reinterpret_cast<int64_t *>(take(8 * F));
-    w.block_sum = reinterpret_cast<int64_t *>(take(8 * nb));
-    w.inv_den = reinterpret_cast<double *>(take(8 * F));
-    w.centroid = reinterpret_cast<float4 *>(take(16 * F));
-    w.bytes = off;
+    QfCarver c{base};
+    w.owner = c.take<int32_t>(hw);
+    w.line_owner = c.take<int32_t>(hw);
+    w.qrec = c.take<int4>(2 * F);
+    w.cum = c.take<int64_t>(F);
+    w.block_sum = c.take<int64_t>(nb);
+    w.inv_den = c.take<double>(F);
+    w.centroid = c.take<float4>(F);
+    w.bytes = c.off;
     return w;
 }
 

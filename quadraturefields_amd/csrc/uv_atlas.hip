@@ -29,19 +29,16 @@
 
 #include <rocprim/device/device_radix_sort.hpp>
 
-#include "qf_common.h"
+#include "mesh_device.h"
 
 namespace {
 
-constexpr int kBlock = 256;
 constexpr int kRedBlocks = 512;
 constexpr int kClasses = 64;                    // max_leg <= 63
 constexpr int kKeyBits = 36;                    // 6 bits of class above 30 bits of Morton code
 constexpr int64_t kMaxCount = int64_t(1) << 31;
 constexpr int32_t kMaxSide = 16384;
 constexpr double kDelta = 0.0625;
-
-inline int64_t align_up(int64_t x) { return (x + 255) & ~int64_t(255); }
 
 struct Info {
     double lo[3], hi[3];
@@ -79,25 +76,24 @@ size_t temp_bytes_for(int64_t F, hipStream_t s)
 Workspace carve(void *base, int64_t F, size_t temp)
 {
     Workspace w;
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) { char *p = static_cast<char *>(base) + off; off += align_up(bytes); return p; };
-    w.info = reinterpret_cast<Info *>(take(sizeof(Info)));
-    w.red = reinterpret_cast<double *>(take(8 * 6 * kRedBlocks));
-    w.red_bad = reinterpret_cast<int64_t *>(take(8 * 2 * kRedBlocks));
-    w.ell = reinterpret_cast<double *>(take(8 * F));
-    w.morton = reinterpret_cast<uint32_t *>(take(4 * F));
-    w.apex = reinterpret_cast<uint8_t *>(take(F));
-    w.hist = reinterpret_cast<uint32_t *>(take(4 * kClasses));
-    w.first_row = reinterpret_cast<int64_t *>(take(8 * kClasses));
-    w.start = reinterpret_cast<int32_t *>(take(4 * kClasses));
-    w.key_a = reinterpret_cast<uint64_t *>(take(8 * F));
-    w.key_b = reinterpret_cast<uint64_t *>(take(8 * F));
-    w.fid_a = reinterpret_cast<int32_t *>(take(4 * F));
-    w.fid_b = reinterpret_cast<int32_t *>(take(4 * F));
-    w.rank = reinterpret_cast<int32_t *>(take(4 * F));
-    w.temp = take((int64_t)temp);
+    QfCarver c{base};
+    w.info = c.take<Info>(1);
+    w.red = c.take<double>(6 * kRedBlocks);
+    w.red_bad = c.take<int64_t>(2 * kRedBlocks);
+    w.ell = c.take<double>(F);
+    w.morton = c.take<uint32_t>(F);
+    w.apex = c.take<uint8_t>(F);
+    w.hist = c.take<uint32_t>(kClasses);
+    w.first_row = c.take<int64_t>(kClasses);
+    w.start = c.take<int32_t>(kClasses);
+    w.key_a = c.take<uint64_t>(F);
+    w.key_b = c.take<uint64_t>(F);
+    w.fid_a = c.take<int32_t>(F);
+    w.fid_b = c.take<int32_t>(F);
+    w.rank = c.take<int32_t>(F);
+    w.temp = c.take<char>((int64_t)temp);
     w.temp_bytes = temp;
-    w.bytes = off;
+    w.bytes = c.off;
     return w;
 }
 
@@ -106,8 +102,6 @@ struct Mesh {
     const int64_t *f;
     int64_t V, F;
 };
-
-__device__ __forceinline__ int64_t gtid() { return (int64_t)blockIdx.x * blockDim.x + threadIdx.x; }
 
 // Per block: min / max of the finite vertices, the count of non-finite vertices and of faces with an index outside
 // [0, V).  Min and max do not depend on order; the counts are integers.
@@ -381,8 +375,6 @@ __global__ __launch_bounds__(kBlock) void emit_kernel(Mesh M, double rho, int N,
         out.uv[6 * base + i] = x / side;
     }
 }
-
-unsigned blocks(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
 bool faces_ok(int64_t F) { return F >= 1 && 3 * F < kMaxCount; }
 

@@ -30,18 +30,15 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
-#include "qf_common.h"
+#include "mesh_device.h"
 
 namespace {
 
-constexpr int kBlock = 256;
 constexpr int kRedBlocks = 512;
 constexpr int64_t kMaxCount = int64_t(1) << 31;
 constexpr int64_t kAxisCells = int64_t(1) << 21;
 constexpr uint32_t kDropped = 0x7fffffffu;      // above every cell id and vertex id (both < 2^31 - 1)
 constexpr double kTau = 1e-6;
-
-inline int64_t align_up(int64_t x) { return (x + 255) & ~int64_t(255); }
 
 struct Info {
     double lo[3];
@@ -112,42 +109,41 @@ size_t temp_bytes_for(int64_t V, int64_t F, hipStream_t s)
 Workspace carve(void *base, int64_t V, int64_t F, size_t temp)
 {
     Workspace w;
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) { char *p = static_cast<char *>(base) + off; off += align_up(bytes); return p; };
-    w.info = reinterpret_cast<Info *>(take(sizeof(Info)));
-    w.red = reinterpret_cast<double *>(take(8 * 6 * kRedBlocks));
-    w.red_bad = reinterpret_cast<int64_t *>(take(8 * 2 * kRedBlocks));
-    w.key_a = reinterpret_cast<uint64_t *>(take(8 * V));
-    w.key_b = reinterpret_cast<uint64_t *>(take(8 * V));
-    w.vid_a = reinterpret_cast<int32_t *>(take(4 * V));
-    w.vid_b = reinterpret_cast<int32_t *>(take(4 * V));
-    w.head = reinterpret_cast<int32_t *>(take(4 * V));
-    w.seg = reinterpret_cast<int32_t *>(take(4 * V));
-    w.first = reinterpret_cast<int32_t *>(take(4 * V));
-    w.rank = reinterpret_cast<int32_t *>(take(4 * V));
-    w.seg_vid = reinterpret_cast<int32_t *>(take(4 * V));
-    w.seg_start = reinterpret_cast<int32_t *>(take(4 * (V + 1)));
-    w.cell_seg = reinterpret_cast<int32_t *>(take(4 * V));
-    w.vcell = reinterpret_cast<int32_t *>(take(4 * V));
-    w.tri = reinterpret_cast<int32_t *>(take(12 * F));
-    w.fk_a = reinterpret_cast<uint64_t *>(take(8 * F));
-    w.fk_b = reinterpret_cast<uint64_t *>(take(8 * F));
-    w.fk0_a = reinterpret_cast<uint32_t *>(take(4 * F));
-    w.fk0_b = reinterpret_cast<uint32_t *>(take(4 * F));
-    w.fid_a = reinterpret_cast<int32_t *>(take(4 * F));
-    w.fid_b = reinterpret_cast<int32_t *>(take(4 * F));
-    w.keep = reinterpret_cast<int32_t *>(take(4 * F));
-    w.fpos = reinterpret_cast<int32_t *>(take(4 * F));
-    w.ik_a = reinterpret_cast<uint32_t *>(take(12 * F));
-    w.ik_b = reinterpret_cast<uint32_t *>(take(12 * F));
-    w.if_a = reinterpret_cast<int32_t *>(take(12 * F));
-    w.if_b = reinterpret_cast<int32_t *>(take(12 * F));
-    w.inc_start = reinterpret_cast<int64_t *>(take(8 * V));
-    w.inc_end = reinterpret_cast<int64_t *>(take(8 * V));
-    w.plane = reinterpret_cast<double *>(take(32 * F));
-    w.temp = take((int64_t)temp);
+    QfCarver c{base};
+    w.info = c.take<Info>(1);
+    w.red = c.take<double>(6 * kRedBlocks);
+    w.red_bad = c.take<int64_t>(2 * kRedBlocks);
+    w.key_a = c.take<uint64_t>(V);
+    w.key_b = c.take<uint64_t>(V);
+    w.vid_a = c.take<int32_t>(V);
+    w.vid_b = c.take<int32_t>(V);
+    w.head = c.take<int32_t>(V);
+    w.seg = c.take<int32_t>(V);
+    w.first = c.take<int32_t>(V);
+    w.rank = c.take<int32_t>(V);
+    w.seg_vid = c.take<int32_t>(V);
+    w.seg_start = c.take<int32_t>(V + 1);
+    w.cell_seg = c.take<int32_t>(V);
+    w.vcell = c.take<int32_t>(V);
+    w.tri = c.take<int32_t>(3 * F);
+    w.fk_a = c.take<uint64_t>(F);
+    w.fk_b = c.take<uint64_t>(F);
+    w.fk0_a = c.take<uint32_t>(F);
+    w.fk0_b = c.take<uint32_t>(F);
+    w.fid_a = c.take<int32_t>(F);
+    w.fid_b = c.take<int32_t>(F);
+    w.keep = c.take<int32_t>(F);
+    w.fpos = c.take<int32_t>(F);
+    w.ik_a = c.take<uint32_t>(3 * F);
+    w.ik_b = c.take<uint32_t>(3 * F);
+    w.if_a = c.take<int32_t>(3 * F);
+    w.if_b = c.take<int32_t>(3 * F);
+    w.inc_start = c.take<int64_t>(V);
+    w.inc_end = c.take<int64_t>(V);
+    w.plane = c.take<double>(4 * F);
+    w.temp = c.take<char>((int64_t)temp);
     w.temp_bytes = temp;
-    w.bytes = off;
+    w.bytes = c.off;
     return w;
 }
 
@@ -157,8 +153,6 @@ struct Mesh {
     int64_t V, F;
     double s;
 };
-
-__device__ __forceinline__ int64_t gtid() { return (int64_t)blockIdx.x * blockDim.x + threadIdx.x; }
 
 // Per block: min / max of the finite vertices, the count of non-finite vertices and of faces with an index outside
 // [0, V).  Min and max do not depend on order; the counts are integers.
@@ -509,8 +503,6 @@ __global__ __launch_bounds__(kBlock) void face_emit_kernel(int64_t F, Workspace 
     out[3 * o + 1] = ws.tri[3 * f + 1];
     out[3 * o + 2] = ws.tri[3 * f + 2];
 }
-
-unsigned blocks(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
 bool sizes_ok(int64_t V, int64_t F) { return V >= 1 && V < kMaxCount && F >= 0 && F < kMaxCount; }
 

@@ -121,6 +121,21 @@ def test_seeded_marks_on_a_larger_mesh(device, share):
         assert got.stats["faces"] == 36000 and got.stats["faces_3_marked"] == 9000
 
 
+def test_grid_past_the_scan_bases_threshold(device):
+    """A 363 x 363 quad grid, F = 263 538: the scan of the children (a byte's value, 1 to 4, not a flag) runs over more
+    than 262 144 items, from where a thread of the scan's middle launch owns more than one per-workgroup sum; the scans
+    of the 790 614 half-edges and of the 396 033 marks are past it too.  A seeded 10 % of the edges is marked."""
+    n = 363
+    i, j = np.meshgrid(np.arange(n + 1), np.arange(n + 1), indexing="ij")
+    v = np.stack([i.ravel(), j.ravel(), np.zeros(i.size)], 1) + np.random.default_rng(5).normal(scale=0.1, size=(i.size, 3))
+    a = (i[:-1, :-1] * (n + 1) + j[:-1, :-1]).ravel()
+    f = np.concatenate([np.stack([a, a + n + 1, a + n + 2], 1), np.stack([a, a + n + 2, a + 1], 1)])
+    n_e = 3 * n * n + 2 * n
+    assert len(f) == 263538 > 262144 and n_e == 396033
+    got, want = _assert_matches(v, f, _marks(n_e, 0.1, 17))
+    assert got.stats["faces"] == want[4][0] > len(f) and got.stats["faces_3_marked"] > 0
+
+
 def test_marks_may_be_bool_or_integer_and_edges_are_optional(device):
     v, f, e, fe = _mesh_3000()
     m = _marks(len(e), 0.5, 17)
