@@ -5,7 +5,7 @@
                                              --ckpt_path ROOT/fit_sg.pth [--early_stop_eps E] [--mesh_path MESH]
                                              [--size 200] [--views 4] [--up_sample 1] [--shells 2] [--subdivisions 3]
                                              [--features PATH] [--quantise {linear,sigma}] [--save_quantised PREFIX]
-                                             [--load_quantised PREFIX]
+                                             [--load_quantised PREFIX] [--fit_samples_per_face N]
 
 The mesh is ``--mesh_path`` or, without it, the shell mesh ``examples/fit_sg_synthetic.py`` fits on (``--shells``,
 ``--subdivisions``); the field is ``--ckpt_path``'s ``radiance_field`` (what ``fit_sg_synthetic.py --out`` wrote) or, if
@@ -20,7 +20,10 @@ one; nothing is written then.  ``--quantise {linear,sigma}`` quantises the baked
 with that colour codec (``baking.quantise_vertex_features``, DESIGN.md section 3.5f) and renders from the records;
 ``--save_quantised PREFIX`` writes its uint8 PNG set (``PREFIX + alpha.png`` ...), ``--load_quantised PREFIX`` reads one
 (written with the codec ``--quantise`` names, default linear) instead of quantising.  The PSNR against the fp32 vertex
-frame is then printed too.
+frame is then printed too.  ``--fit_samples_per_face N`` also fits the fp32 table to the field over the surface
+(``baking.fit_vertex_features`` with the baked or loaded table as the prior), renders the same
+views from the fitted table and prints its PSNR / SSIM and both tables' ``baking.vertex_surface_error`` beside the
+others; without the flag nothing else changes.
 """
 import argparse
 import json
@@ -56,6 +59,8 @@ def parse(argv):
                     help="quantise the vertex table to uint8 records with this colour codec before rendering")
     ap.add_argument("--save_quantised", type=str, default="", help="write the quantised table's PNG set under this prefix")
     ap.add_argument("--load_quantised", type=str, default="", help="read the quantised table's PNG set from this prefix")
+    ap.add_argument("--fit_samples_per_face", type=int, default=0,
+                    help="also score the table fitted to the field over the surface, with this many samples per face")
     return ap.parse_args(argv)
 
 
@@ -115,6 +120,10 @@ def main(argv=None):
         focal = synthetic.lego_focal(size)
         scorer = FrameScorer(size, size, up_sample=factor, capacity=max(args.views, 1), device=device)
         shaded = samples = 0
+        fitted = fit_scorer = None
+        if args.fit_samples_per_face > 0:
+            fitted = baking.fit_vertex_features(sg, mesh, args.fit_samples_per_face, prior=features, device=device)
+            fit_scorer = FrameScorer(size, size, up_sample=factor, capacity=max(args.views, 1), device=device)
         for c2w in synthetic.orbit_cameras(args.views):
             o, d = synthetic.camera_rays(c2w, focal, size, size, device=device)
             pixels = renderer.render(o, d, camera=make_camera(c2w, focal, size, size))[0]        # the field's own frame
@@ -130,6 +139,9 @@ def main(argv=None):
                 sq_err += ((rgb.double() - rgb32.double()) ** 2).sum()
                 n_px += rgb.numel()
             scorer.score(rgb, pixels)
+            if fitted is not None:
+                fit_scorer.score(renderer.render_vertex_baked(o, d, fitted, camera=camera,
+                                                              early_stop_eps=args.early_stop_eps)[0], pixels)
         res = scorer.results()
     out = {"psnr": res["psnr_avg"], "ssim": res["ssim_avg"], "psnrs": res["psnr"].tolist(), "ssims": res["ssim"].tolist(),
            "vertices": int(features.shape[0]), "columns": int(features.shape[1])}
@@ -142,6 +154,16 @@ def main(argv=None):
         mse = float(sq_err) / max(n_px, 1)
         out["psnr_vs_fp32_vertex"] = -10.0 * float(np.log10(mse)) if mse > 0 else float("inf")
         print("psnr vs fp32 vertex frame: ", out["psnr_vs_fp32_vertex"])
+    if fitted is not None:
+        fit_res = fit_scorer.results()
+        n_fresh = args.fit_samples_per_face * int(mesh.faces.shape[0])
+        errors = {k: baking.vertex_surface_error(sg, mesh, t, n_fresh, seed=1) for k, t in (("", features), ("fit_", fitted))}
+        out.update({"fit_samples_per_face": args.fit_samples_per_face, "fit_psnr": fit_res["psnr_avg"],
+                    "fit_ssim": fit_res["ssim_avg"], "surface_error_rms": errors[""]["rms"],
+                    "fit_surface_error_rms": errors["fit_"]["rms"]})
+        print(f"fitted table ({args.fit_samples_per_face} samples per face): psnr {out['fit_psnr']}  ssim {out['fit_ssim']}")
+        print(f"surface error (rms, pixel units, fresh samples): {out['surface_error_rms']:.3e} as loaded or baked, "
+              f"{out['fit_surface_error_rms']:.3e} fitted")
     print(json.dumps(out))
     return out
 

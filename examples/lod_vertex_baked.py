@@ -5,6 +5,7 @@ held-out views with both assets.
     python examples/lod_vertex_baked.py --synthetic --root ROOT --num_lobes 6 --log2_hashmap_size 19
                                         --ckpt_path ROOT/fit_sg.pth --ratio 0.25 [--mesh_path MESH] [--features PATH]
                                         [--size 200] [--views 4] [--shells 2] [--subdivisions 3] [--boundary {lock,collapse}]
+                                        [--fit_samples_per_face N]
 
 The mesh is ``--mesh_path`` or the shell mesh ``examples/fit_sg_synthetic.py`` fits on; the field is ``--ckpt_path``'s
 ``radiance_field`` or, if the file does not exist, the seeded SG state.  The table is ``--features PATH`` (what
@@ -15,7 +16,11 @@ away) or ``baking.bake_vertex_features`` of the field.  The mesh is decimated to
 mesh with a table baked again from the field at its vertices.  Each is scored by ``metrics.FrameScorer`` against the SG
 field's own render of the view on the full mesh.  Prints faces, vertices, table bytes and PSNR / SSIM of each, the
 measured surface distance between the two meshes, and one JSON line; writes ``ROOT/lod_mesh.ply`` and
-``ROOT/lod_vertex_features.npy``."""
+``ROOT/lod_vertex_features.npy``.
+
+With ``--fit_samples_per_face N`` two more assets are rendered and scored beside those three: the full and the decimated
+mesh, each with a table fitted to the field over its surface (``baking.fit_vertex_features`` with N samples per face,
+DESIGN.md section 3.9i) in place of the point bake.  Without the flag nothing else changes."""
 import argparse
 import json
 import os
@@ -44,6 +49,8 @@ def parse(argv):
     ap.add_argument("--shells", type=int, default=2)
     ap.add_argument("--subdivisions", type=int, default=3)
     ap.add_argument("--features", type=str, default="", help="load this vertex table (.npy) instead of baking one")
+    ap.add_argument("--fit_samples_per_face", type=int, default=0,
+                    help="also score tables fitted to the field over the surface, with this many samples per face")
     return ap.parse_args(argv)
 
 
@@ -94,6 +101,10 @@ def main(argv=None):
         np.save(os.path.join(args.root, "lod_vertex_features.npy"), moved.cpu().numpy())
 
         assets = {"full": (full, table), "transferred": (small, moved), "rebaked": (small, rebaked)}
+        if args.fit_samples_per_face > 0:
+            assets["fitted"] = (full, baking.fit_vertex_features(sg, mesh, args.fit_samples_per_face, device=device))
+            assets["fitted_decimated"] = (small, baking.fit_vertex_features(sg, small_mesh, args.fit_samples_per_face,
+                                                                            device=device))
         size, focal = args.size, synthetic.lego_focal(args.size)
         scorers = {k: FrameScorer(size, size, up_sample=1, capacity=max(args.views, 1), device=device) for k in assets}
         renderers = {k: FrameRenderer(mi, sg, render_step_size=5e-3) for k, (mi, _) in assets.items()}
@@ -109,7 +120,7 @@ def main(argv=None):
         res = scorers[k].results()
         out[k] = {"faces": int(mi.mesh.faces.shape[0]), "vertices": int(feats.shape[0]), "table_bytes": int(feats.numel() * 4),
                   "psnr": res["psnr_avg"], "ssim": res["ssim_avg"]}
-        print(f"{k:12s} {out[k]['faces']:8d} faces {out[k]['vertices']:8d} vertices {out[k]['table_bytes'] / 1e6:8.2f} MB   "
+        print(f"{k:{max(12, *map(len, assets))}s} {out[k]['faces']:8d} faces {out[k]['vertices']:8d} vertices {out[k]['table_bytes'] / 1e6:8.2f} MB   "
               f"psnr {out[k]['psnr']:.2f}  ssim {out[k]['ssim']:.4f}")
     print(f"surface distance: decimated -> full mean {distance.a_to_b_mean:.3e} max {distance.a_to_b_max:.3e}, "
           f"full -> decimated mean {distance.b_to_a_mean:.3e} max {distance.b_to_a_max:.3e}")

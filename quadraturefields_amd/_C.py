@@ -346,6 +346,19 @@ _MESH_SAMPLE_SIGNATURES = {
     "qf_mesh_sample_emit": (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, c_int64, c_uint64, _P, _P, _P, _P]),
 }
 
+# include/qf_vertex_fit.h: the vertex table fitted to a field over the surface, additive in the
+# same way
+VERTEX_FIT_COUNTS = ("bad_sample_faces", "unsorted_samples", "nonfinite_entries", "skipped_faces", "skipped_samples",
+                     "inactive_vertices", "clamped_entries", "refused")
+VERTEX_FIT_MAX_COLUMNS = 64
+_VERTEX_FIT_SIGNATURES = {
+    "qf_vertex_fit_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64, c_int64]),
+    "qf_vertex_fit_assemble": (c_int, [_P, c_int64, c_int64, _P, _P, c_int64, _P, c_int64, _P, c_int64, c_int64, c_double,
+                                       _P, _P, _P, _P, c_int64, _P, _P]),
+    "qf_vertex_fit_solve": (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, _P, _P, _P, c_int64, c_uint64, _P, c_int64,
+                                    _P, c_int64, _P, _P, _P]),
+}
+
 # include/qf_closest_point.h: the closest point on the mesh of a qf_bvh handle, additive in the
 # same way
 CLOSEST_POINT_COUNTS = ("nonfinite_queries", "no_triangle")
@@ -380,7 +393,8 @@ def lib() -> ctypes.CDLL:
                                           + list(_MESH_MANIFOLD_SIGNATURES.items())
                                           + list(_CLOSEST_POINT_SIGNATURES.items())
                                           + list(_MESH_WELD_SIGNATURES.items())
-                                          + list(_MESH_SAMPLE_SIGNATURES.items())):
+                                          + list(_MESH_SAMPLE_SIGNATURES.items())
+                                          + list(_VERTEX_FIT_SIGNATURES.items())):
             fn = getattr(handle, name)   # AttributeError if the symbol is not exported
             fn.restype = restype
             fn.argtypes = argtypes

@@ -24,7 +24,8 @@ ARCH = "gfx950"
 # side rules), uv_atlas.hip (the fp64 measure, class and corner rules) and bvh_build_device.hip (the fp32 Morton
 # keys of the device BVH build) and closest_point.hip (the fp64 region walk, point and distance rules).  mesh_manifold.hip has no arithmetic at all and carries no flag;
 # mesh_weld.hip carries it for the fp64 cell quotient and distance test of the weld, mesh_sample.hip for the fp64 measure,
-# quotient, position and point rules of surface sampling.
+# quotient, position and point rules of surface sampling, vertex_fit.hip for the fp64 sums, products and quotients of the
+# surface fit of the vertex table, each rounded on its own.
 SOURCES = [
     ("field_eval.hip", []),
     ("field_eval_bf16.hip", []),
@@ -58,6 +59,7 @@ SOURCES = [
     ("mesh_manifold.hip", []),     # no -ffp-contract flag: the file has no floating-point operation to contract
     ("mesh_weld.hip", ["-ffp-contract=off"]),      # the fp64 cell quotient and distance test of the weld
     ("mesh_sample.hip", ["-ffp-contract=off"]),    # the fp64 measure, position, barycentric and point rules
+    ("vertex_fit.hip", ["-ffp-contract=off"]),     # the fp64 gram, right-hand side, operator, dot and update rules
     ("uv_atlas.hip", ["-ffp-contract=off"]),
     ("bvh_build_device.hip", ["-ffp-contract=off"]),
     ("closest_point.hip", ["-ffp-contract=off"]),
@@ -83,7 +85,7 @@ def _deps(src: str):
             os.path.join(ROOT, "include", "qf_mesh_subdivide.h"), os.path.join(ROOT, "include", "qf_mesh_decimate.h"),
             os.path.join(ROOT, "include", "qf_mesh_decimate_open.h"), os.path.join(ROOT, "include", "qf_mesh_manifold.h"),
             os.path.join(ROOT, "include", "qf_closest_point.h"), os.path.join(ROOT, "include", "qf_mesh_weld.h"),
-            os.path.join(ROOT, "include", "qf_mesh_sample.h"),
+            os.path.join(ROOT, "include", "qf_mesh_sample.h"), os.path.join(ROOT, "include", "qf_vertex_fit.h"),
             os.path.abspath(__file__)]
     deps += [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     return deps
