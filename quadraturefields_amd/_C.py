@@ -372,6 +372,12 @@ def vertex_row_stride(n_lobes: int) -> int:
     1 / 2 / 6 / 8 lobes)."""
     return 16 * ((3 + 7 * int(n_lobes) + 1 + 15) // 16)
 
+# every table lib() registers: a new stage adds its own here
+_SIGNATURE_TABLES = (_SIGNATURES, _VERTEX_BAKED_SIGNATURES, _VERTEX_TRAIN_SIGNATURES, _VERTEX_QUANT_SIGNATURES,
+                     _MESH_COMPACT_SIGNATURES, _MESH_SUBDIVIDE_SIGNATURES, _MESH_DECIMATE_SIGNATURES,
+                     _MESH_DECIMATE_OPEN_SIGNATURES, _MESH_MANIFOLD_SIGNATURES, _CLOSEST_POINT_SIGNATURES,
+                     _MESH_WELD_SIGNATURES, _MESH_SAMPLE_SIGNATURES, _VERTEX_FIT_SIGNATURES)
+
 _lib = None
 
 
@@ -384,20 +390,11 @@ def lib() -> ctypes.CDLL:
                 f"{LIB_PATH} is missing: build it with `python -m quadraturefields_amd.build` "
                 "(hipcc --offload-arch=gfx950).  quadraturefields_amd has no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in (list(_SIGNATURES.items()) + list(_VERTEX_BAKED_SIGNATURES.items())
-                                          + list(_VERTEX_TRAIN_SIGNATURES.items()) + list(_VERTEX_QUANT_SIGNATURES.items())
-                                          + list(_MESH_COMPACT_SIGNATURES.items())
-                                          + list(_MESH_SUBDIVIDE_SIGNATURES.items())
-                                          + list(_MESH_DECIMATE_SIGNATURES.items())
-                                          + list(_MESH_DECIMATE_OPEN_SIGNATURES.items())
-                                          + list(_MESH_MANIFOLD_SIGNATURES.items())
-                                          + list(_CLOSEST_POINT_SIGNATURES.items())
-                                          + list(_MESH_WELD_SIGNATURES.items())
-                                          + list(_MESH_SAMPLE_SIGNATURES.items())
-                                          + list(_VERTEX_FIT_SIGNATURES.items())):
-            fn = getattr(handle, name)   # AttributeError if the symbol is not exported
-            fn.restype = restype
-            fn.argtypes = argtypes
+        for table in _SIGNATURE_TABLES:
+            for name, (restype, argtypes) in table.items():
+                fn = getattr(handle, name)   # AttributeError if the symbol is not exported
+                fn.restype = restype
+                fn.argtypes = argtypes
         version = handle.qf_abi_version()
         experiment = os.environ.get("QF_HIP_LIBRARY_EXPERIMENT") == "1" and version == ABI_VERSION + 1000
         if version != ABI_VERSION and not experiment:

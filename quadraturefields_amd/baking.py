@@ -29,6 +29,7 @@ import numpy as np
 import torch
 
 from . import _C
+from ._mesh_args import counts_buffer, mesh_inputs, read_counts, to_numpy, trimesh_tensors, workspace
 from .mesh_io import TriMesh
 
 
@@ -640,11 +641,13 @@ def fit_vertex_table_device(faces, n_vertices: int, sample_face, sample_bary, ta
     column, ``rhs_norm`` and ``residual_norm`` (lists of C floats).  One host wait, for the counts.  Raises ValueError,
     naming the counts, when sample faces are out of range or decrease, or when a barycentric, target or prior entry is
     not finite; then nothing was solved."""
-    from . import mc_utils
     table, n_c = _fit_table_of(prior, "fit_vertex_table_device")
-    f = mc_utils._device_faces(faces, "fit_vertex_table_device")
-    dev = f.device
-    n_v, n_f = int(n_vertices), f.shape[0]
+    lam, steps = float(prior_weight), int(iterations)
+    if not (lam >= 0.0 and math.isfinite(lam)):
+        raise ValueError(f"prior_weight must be finite and >= 0, got {prior_weight!r}")
+    if steps < 0:
+        raise ValueError(f"iterations must be >= 0, got {iterations!r}")
+    _, f, dev, n_v, n_f = mesh_inputs(None, faces, "fit_vertex_table_device", limit="3F", n_vertices=n_vertices)
     for name, t in (("sample_face", sample_face), ("sample_bary", sample_bary), ("targets", targets), ("prior", table)):
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"{name} must be a torch.Tensor")
@@ -663,23 +666,15 @@ def fit_vertex_table_device(faces, n_vertices: int, sample_face, sample_bary, ta
         raise ValueError(f"the prior must have V = {n_v} >= 1 rows, got {tuple(table.shape)}")
     if table.stride(1) != 1 or table.stride(0) < n_c:
         table = table.contiguous()
-    lam, steps = float(prior_weight), int(iterations)
-    if not (lam >= 0.0 and math.isfinite(lam)):
-        raise ValueError(f"prior_weight must be finite and >= 0, got {prior_weight!r}")
-    if steps < 0:
-        raise ValueError(f"iterations must be >= 0, got {iterations!r}")
     mask = _clamp_mask(clamp_columns, n_c)
     sf, sb, y = sample_face.contiguous(), sample_bary.contiguous(), targets.contiguous()
     lib = _C.lib()
     with torch.cuda.device(dev):
-        ws_bytes = int(lib.qf_vertex_fit_workspace_bytes(n_v, n_f, n, n_c))
-        if ws_bytes < 0:
-            raise ValueError(f"qf_vertex_fit_workspace_bytes refused V={n_v}, F={n_f}, N={n}, C={n_c}")
-        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+        ws, ws_bytes = workspace("qf_vertex_fit_workspace_bytes", dev, ValueError, V=n_v, F=n_f, N=n, C=n_c)
         gram = torch.empty((n_f, 9), dtype=torch.float64, device=dev)
         mass = torch.empty((n_v,), dtype=torch.float64, device=dev)
         rhs = torch.empty((n_v, n_c), dtype=torch.float64, device=dev)
-        counts = torch.empty((len(_C.VERTEX_FIT_COUNTS),), dtype=torch.int64, device=dev)
+        counts = counts_buffer(_C.VERTEX_FIT_COUNTS, dev)
         norms = torch.empty((n_c, 2), dtype=torch.float64, device=dev)
         out = torch.empty((n_v, n_c), dtype=torch.float32, device=dev)
         x0 = ctypes.c_void_p(table.data_ptr())
@@ -691,7 +686,7 @@ def fit_vertex_table_device(faces, n_vertices: int, sample_face, sample_bary, ta
                                          _C.ptr(gram) if n_f else None, _C.ptr(mass), _C.ptr(rhs), steps, mask, _C.ptr(ws),
                                          ws_bytes, _C.ptr(out), n_c, _C.ptr(norms), _C.ptr(counts), _C.stream()),
                  "qf_vertex_fit_solve")
-        stats = dict(zip(_C.VERTEX_FIT_COUNTS, counts.tolist()))         # the host wait
+        stats = read_counts(_C.VERTEX_FIT_COUNTS, counts)                # the host wait
     if stats["refused"]:
         raise ValueError("fit_vertex_table_device: the input cannot be fitted: "
                          + ", ".join(f"{k}={stats[k]}" for k in _C.VERTEX_FIT_COUNTS[:3]))
@@ -706,11 +701,7 @@ def fit_vertex_table_device(faces, n_vertices: int, sample_face, sample_bary, ta
 
 def _mesh_tensors(mesh, device):
     """fp64 vertices and int64 faces of a ``TriMesh`` (or anything with ``vertices`` and ``faces``) on ``device``."""
-    mesh = getattr(mesh, "mesh", mesh)
-    v, f = mesh.vertices, mesh.faces
-    v = v if isinstance(v, torch.Tensor) else torch.from_numpy(np.asarray(v, dtype=np.float64))
-    f = f if isinstance(f, torch.Tensor) else torch.from_numpy(np.asarray(f, dtype=np.int64))
-    return v.to(device=device, dtype=torch.float64), f.to(device=device, dtype=torch.int64)
+    return trimesh_tensors(getattr(mesh, "mesh", mesh), device)
 
 
 @torch.no_grad()
@@ -920,8 +911,7 @@ def refine_vertex_baked(mesh: TriMesh, radiance_field, tol: float, max_levels: i
     tensors ``edges``, ``errors`` and ``marks``)."""
     from . import mc_utils
     dev = _C.resolve_device(device)
-    v = torch.from_numpy(np.asarray(mesh.vertices, np.float64)).to(dev)
-    f = torch.from_numpy(np.asarray(mesh.faces, np.int64)).to(dev)
+    v, f = trimesh_tensors(mesh, dev)
     if max_vertices is not None and int(max_vertices) < v.shape[0]:
         raise ValueError(f"max_vertices = {max_vertices} is below the mesh's {v.shape[0]} vertices")
     table = _field_features(radiance_field, v.to(torch.float32))
@@ -953,5 +943,4 @@ def refine_vertex_baked(mesh: TriMesh, radiance_field, tol: float, max_levels: i
         v, f = out.vertices, out.faces
         face_map = face_map[out.face_map]
         parents = mc_utils.chain_vertex_parents(parents, out.vertex_parents)
-    refined = TriMesh(v.cpu().numpy(), f.cpu().numpy(), None)
-    return RefinedVertexBaked(refined, table, face_map.cpu().numpy(), parents.cpu().numpy(), levels)
+    return RefinedVertexBaked(TriMesh(*to_numpy(v, f), None), table, *to_numpy(face_map, parents), levels)

@@ -315,28 +315,19 @@ extern "C" int qf_mesh_compact_count(const double *vertices, int64_t n_vertices,
     const int unref = (flags & QF_MESH_REMOVE_UNREFERENCED) ? 1 : 0;
 
     QF_HIP_TRY(hipMemsetAsync(ws.info, 0, sizeof(Info), s));
-    hipLaunchKernelGGL(init_kernel, dim3(blocks(V)), dim3(kBlock), 0, s, V, ws, unref ? 0 : 1);
-    QF_LAUNCH_CHECK();
+    QF_MESH_LAUNCH(init_kernel, V, V, ws, unref ? 0 : 1);
     if (F > 0) {
-        hipLaunchKernelGGL(classify_kernel, dim3(blocks(F)), dim3(kBlock), 0, s, J, ws);
-        QF_LAUNCH_CHECK();
+        QF_MESH_LAUNCH(classify_kernel, F, J, ws);
         if (flags & QF_MESH_REMOVE_DUPLICATES) {
             QF_HIP_TRY(hipMemsetAsync(ws.table, 0xff, 4 * (size_t)ws.slots, s));
-            hipLaunchKernelGGL(duplicate_insert_kernel, dim3(blocks(F)), dim3(kBlock), 0, s, F, ws);
-            QF_LAUNCH_CHECK();
-            hipLaunchKernelGGL(duplicate_mark_kernel, dim3(blocks(F)), dim3(kBlock), 0, s, F, ws);
-            QF_LAUNCH_CHECK();
+            QF_MESH_LAUNCH(duplicate_insert_kernel, F, F, ws);
+            QF_MESH_LAUNCH(duplicate_mark_kernel, F, F, ws);
         }
-        hipLaunchKernelGGL(union_kernel, dim3(blocks(F)), dim3(kBlock), 0, s, F, ws);
-        QF_LAUNCH_CHECK();
-        hipLaunchKernelGGL(flatten_kernel, dim3(blocks(V)), dim3(kBlock), 0, s, V, ws);
-        QF_LAUNCH_CHECK();
-        hipLaunchKernelGGL(component_size_kernel, dim3(blocks(F)), dim3(kBlock), 0, s, F, ws);
-        QF_LAUNCH_CHECK();
-        hipLaunchKernelGGL(component_count_kernel, dim3(blocks(V)), dim3(kBlock), 0, s, V, ws);
-        QF_LAUNCH_CHECK();
-        hipLaunchKernelGGL(island_kernel, dim3(blocks(F)), dim3(kBlock), 0, s, F, ws, J.M, unref);
-        QF_LAUNCH_CHECK();
+        QF_MESH_LAUNCH(union_kernel, F, F, ws);
+        QF_MESH_LAUNCH(flatten_kernel, V, V, ws);
+        QF_MESH_LAUNCH(component_size_kernel, F, F, ws);
+        QF_MESH_LAUNCH(component_count_kernel, V, V, ws);
+        QF_MESH_LAUNCH(island_kernel, F, F, ws, J.M, unref);
     }
     int st = scan_bytes(ws.state, F, ItemEquals{kAlive}, ws.fpart, ws.fpos, &ws.info->face_total, s);
     if (st != QF_OK) return st;
@@ -363,13 +354,11 @@ extern "C" int qf_mesh_compact_emit(const double *vertices, int64_t n_vertices, 
     Workspace ws = carve(workspace, J.V, J.F);
     if (workspace_bytes < ws.bytes) return QF_ERR_INVALID_ARGUMENT;
     if (n_out_vertices > 0) {
-        hipLaunchKernelGGL(vertex_emit_kernel, dim3(blocks(J.V)), dim3(kBlock), 0, s, J, ws,
-                           reinterpret_cast<uint64_t *>(out_vertices), n_out_vertices, vertex_map);
-        QF_LAUNCH_CHECK();
+        QF_MESH_LAUNCH(vertex_emit_kernel, J.V, J, ws, reinterpret_cast<uint64_t *>(out_vertices), n_out_vertices,
+                       vertex_map);
     }
     if (n_out_faces > 0) {
-        hipLaunchKernelGGL(face_emit_kernel, dim3(blocks(J.F)), dim3(kBlock), 0, s, J, ws, out_faces, n_out_faces, face_map);
-        QF_LAUNCH_CHECK();
+        QF_MESH_LAUNCH(face_emit_kernel, J.F, J, ws, out_faces, n_out_faces, face_map);
     }
     return QF_OK;
 }

@@ -814,12 +814,23 @@ int build_face_rows(const Mesh &M, Workspace &ws, hipStream_t s)
     QF_HIP_TRY(hipMemsetAsync(ws.fend, 0, 8 * (size_t)M.V, s));
     if (M.F == 0) return QF_OK;
     const int64_t n = 3 * M.F;
-    hipLaunchKernelGGL(face_key_kernel, dim3(blocks(n)), dim3(kBlock), 0, s, M, ws);
-    QF_LAUNCH_CHECK();
+    QF_MESH_LAUNCH(face_key_kernel, n, M, ws);
     size_t tb = ws.temp_bytes;
     QF_HIP_TRY(rocprim::radix_sort_keys(ws.temp, tb, ws.fkey_a, ws.fkey_b, (size_t)n, 0, 64, s));
-    hipLaunchKernelGGL(range_kernel, dim3(blocks(n)), dim3(kBlock), 0, s, ws.fkey_b, n, ws.fstart, ws.fend);
-    QF_LAUNCH_CHECK();
+    QF_MESH_LAUNCH(range_kernel, n, ws.fkey_b, n, ws.fstart, ws.fend);
+    return QF_OK;
+}
+
+// The CSR of vertex neighbours: the two keys `key_kernel` gives every edge, sort, runs.
+int build_neighbour_rows(const Mesh &M, Workspace &ws, void (*key_kernel)(Mesh, Workspace), hipStream_t s)
+{
+    QF_HIP_TRY(hipMemsetAsync(ws.nstart, 0, 8 * (size_t)M.V, s));
+    QF_HIP_TRY(hipMemsetAsync(ws.nend, 0, 8 * (size_t)M.V, s));
+    if (M.E == 0) return QF_OK;
+    QF_MESH_LAUNCH(key_kernel, M.E, M, ws);
+    size_t tb = ws.temp_bytes;
+    QF_HIP_TRY(rocprim::radix_sort_keys(ws.temp, tb, ws.nkey_a, ws.nkey_b, (size_t)(2 * M.E), 0, 64, s));
+    QF_MESH_LAUNCH(range_kernel, 2 * M.E, ws.nkey_b, 2 * M.E, ws.nstart, ws.nend);
     return QF_OK;
 }
 
@@ -849,12 +860,8 @@ extern "C" int qf_mesh_vertex_quadrics(const double *vertices, int64_t n_vertice
     QF_HIP_TRY(hipMemsetAsync(ws.info, 0, sizeof(Info), s));
     const int st = build_face_rows(M, ws, s);
     if (st != QF_OK) return st;
-    if (M.F > 0) {
-        hipLaunchKernelGGL(plane_kernel, dim3(blocks(M.F)), dim3(kBlock), 0, s, M, ws);
-        QF_LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(quadric_kernel, dim3(blocks(M.V)), dim3(kBlock), 0, s, M, ws, quadrics);
-    QF_LAUNCH_CHECK();
+    QF_MESH_LAUNCH(plane_kernel, M.F, M, ws);
+    QF_MESH_LAUNCH(quadric_kernel, M.V, M, ws, quadrics);
     hipLaunchKernelGGL(quadric_counts_kernel, dim3(1), dim3(1), 0, s, ws, counts);
     QF_LAUNCH_CHECK();
     return QF_OK;
@@ -878,37 +885,22 @@ extern "C" int qf_mesh_collapse_select(const double *vertices, int64_t n_vertice
     const int64_t V = M.V, F = M.F, E = M.E;
 
     QF_HIP_TRY(hipMemsetAsync(ws.info, 0, sizeof(Info), s));
-    QF_HIP_TRY(hipMemsetAsync(ws.nstart, 0, 8 * (size_t)V, s));
-    QF_HIP_TRY(hipMemsetAsync(ws.nend, 0, 8 * (size_t)V, s));
     QF_HIP_TRY(hipMemsetAsync(ws.m1, 0xff, 8 * (size_t)V, s));
-    const int st = build_face_rows(M, ws, s);
+    int st = build_face_rows(M, ws, s);
     if (st != QF_OK) return st;
-    hipLaunchKernelGGL(lock_init_kernel, dim3(blocks(V)), dim3(kBlock), 0, s, V, vertex_lock, ws);
-    QF_LAUNCH_CHECK();
+    QF_MESH_LAUNCH(lock_init_kernel, V, V, vertex_lock, ws);
+    st = build_neighbour_rows(M, ws, edge_key_kernel, s);
+    if (st != QF_OK) return st;
     if (E > 0) {
         QF_HIP_TRY(hipMemsetAsync(ws.uses, 0, 4 * (size_t)E, s));
-        hipLaunchKernelGGL(edge_key_kernel, dim3(blocks(E)), dim3(kBlock), 0, s, M, ws);
-        QF_LAUNCH_CHECK();
-        size_t tb = ws.temp_bytes;
-        QF_HIP_TRY(rocprim::radix_sort_keys(ws.temp, tb, ws.nkey_a, ws.nkey_b, (size_t)(2 * E), 0, 64, s));
-        hipLaunchKernelGGL(range_kernel, dim3(blocks(2 * E)), dim3(kBlock), 0, s, ws.nkey_b, 2 * E, ws.nstart, ws.nend);
-        QF_LAUNCH_CHECK();
-        if (F > 0) {
-            hipLaunchKernelGGL(uses_kernel, dim3(blocks(3 * F)), dim3(kBlock), 0, s, M, ws);
-            QF_LAUNCH_CHECK();
-        }
-        hipLaunchKernelGGL(lock_edge_kernel, dim3(blocks(E)), dim3(kBlock), 0, s, M, ws);
-        QF_LAUNCH_CHECK();
+        QF_MESH_LAUNCH(uses_kernel, 3 * F, M, ws);
+        QF_MESH_LAUNCH(lock_edge_kernel, E, M, ws);
     }
-    hipLaunchKernelGGL(lock_count_kernel, dim3(blocks(V)), dim3(kBlock), 0, s, V, ws);
-    QF_LAUNCH_CHECK();
+    QF_MESH_LAUNCH(lock_count_kernel, V, V, ws);
     if (E > 0) {
-        hipLaunchKernelGGL(candidate_kernel, dim3(blocks(E)), dim3(kBlock), 0, s, M, ws, max_cost, (uint64_t)round);
-        QF_LAUNCH_CHECK();
-        hipLaunchKernelGGL(min2_kernel, dim3(blocks(V)), dim3(kBlock), 0, s, V, ws);
-        QF_LAUNCH_CHECK();
-        hipLaunchKernelGGL(select_kernel, dim3(blocks(E)), dim3(kBlock), 0, s, M, ws);
-        QF_LAUNCH_CHECK();
+        QF_MESH_LAUNCH(candidate_kernel, E, M, ws, max_cost, (uint64_t)round);
+        QF_MESH_LAUNCH(min2_kernel, V, V, ws);
+        QF_MESH_LAUNCH(select_kernel, E, M, ws);
         size_t tb = ws.temp_bytes;
         QF_HIP_TRY(rocprim::radix_sort_pairs(ws.temp, tb, ws.skey_a, ws.skey_b, ws.sval_a, ws.sval_b, (size_t)E, 0, 64, s));
     }
@@ -933,20 +925,9 @@ extern "C" int qf_mesh_collapse_apply(double *vertices, int64_t n_vertices, int6
 
     QF_HIP_TRY(hipMemsetAsync(ws.remap, 0xff, 4 * (size_t)n_vertices, s));
     const int64_t n = max_take < n_edges ? max_take : n_edges;
-    if (n > 0) {
-        hipLaunchKernelGGL(apply_kernel, dim3(blocks(n)), dim3(kBlock), 0, s, vertices, quadrics, edges, n, ws);
-        QF_LAUNCH_CHECK();
-    }
-    if (n_faces > 0) {
-        hipLaunchKernelGGL(remap_kernel, dim3(blocks(3 * n_faces)), dim3(kBlock), 0, s, faces, 3 * n_faces, n_vertices,
-                           ws.remap);
-        QF_LAUNCH_CHECK();
-    }
-    if (n_targets > 0) {
-        hipLaunchKernelGGL(remap_kernel, dim3(blocks(n_targets)), dim3(kBlock), 0, s, vertex_target, n_targets, n_vertices,
-                           ws.remap);
-        QF_LAUNCH_CHECK();
-    }
+    QF_MESH_LAUNCH(apply_kernel, n, vertices, quadrics, edges, n, ws);
+    QF_MESH_LAUNCH(remap_kernel, 3 * n_faces, faces, 3 * n_faces, n_vertices, ws.remap);
+    QF_MESH_LAUNCH(remap_kernel, n_targets, vertex_target, n_targets, n_vertices, ws.remap);
     return QF_OK;
 }
 
@@ -966,21 +947,10 @@ extern "C" int qf_mesh_collapse_gather(const double *quadrics, const uint8_t *ve
     hipStream_t s = qf_stream(stream);
     int32_t *inverse = static_cast<int32_t *>(workspace);
     QF_HIP_TRY(hipMemsetAsync(inverse, 0xff, 4 * (size_t)n_vertices, s));
-    if (n_out_vertices > 0) {
-        hipLaunchKernelGGL(gather_vertex_kernel, dim3(blocks(n_out_vertices)), dim3(kBlock), 0, s, quadrics, vertex_lock,
-                           vertex_map, n_vertices, n_out_vertices, out_quadrics, out_lock, inverse);
-        QF_LAUNCH_CHECK();
-    }
-    if (n_out_faces > 0) {
-        hipLaunchKernelGGL(gather_face_kernel, dim3(blocks(n_out_faces)), dim3(kBlock), 0, s, face_map, compact_face_map,
-                           n_faces, n_out_faces, out_face_map);
-        QF_LAUNCH_CHECK();
-    }
-    if (n_targets > 0) {
-        hipLaunchKernelGGL(target_kernel, dim3(blocks(n_targets)), dim3(kBlock), 0, s, vertex_target, n_targets, n_vertices,
-                           inverse);
-        QF_LAUNCH_CHECK();
-    }
+    QF_MESH_LAUNCH(gather_vertex_kernel, n_out_vertices, quadrics, vertex_lock, vertex_map, n_vertices, n_out_vertices,
+                   out_quadrics, out_lock, inverse);
+    QF_MESH_LAUNCH(gather_face_kernel, n_out_faces, face_map, compact_face_map, n_faces, n_out_faces, out_face_map);
+    QF_MESH_LAUNCH(target_kernel, n_targets, vertex_target, n_targets, n_vertices, inverse);
     return QF_OK;
 }
 
@@ -1035,24 +1005,13 @@ extern "C" int qf_mesh_boundary_quadrics(const double *vertices, int64_t n_verti
     QF_HIP_TRY(hipMemsetAsync(ws.info, 0, sizeof(Info), s));
     QF_HIP_TRY(hipMemsetAsync(ox.info, 0, sizeof(OpenInfo), s));
     if (E > 0) {
-        QF_HIP_TRY(hipMemsetAsync(ws.nstart, 0, 8 * (size_t)V, s));
-        QF_HIP_TRY(hipMemsetAsync(ws.nend, 0, 8 * (size_t)V, s));
         QF_HIP_TRY(hipMemsetAsync(ws.uses, 0, 4 * (size_t)E, s));
         QF_HIP_TRY(hipMemsetAsync(ox.eplane, 0, 32 * (size_t)E, s));
-        if (F > 0) {
-            hipLaunchKernelGGL(uses_kernel, dim3(blocks(3 * F)), dim3(kBlock), 0, s, M, ws);
-            QF_LAUNCH_CHECK();
-            hipLaunchKernelGGL(boundary_plane_kernel, dim3(blocks(3 * F)), dim3(kBlock), 0, s, M, ws, ox);
-            QF_LAUNCH_CHECK();
-        }
-        hipLaunchKernelGGL(boundary_key_kernel, dim3(blocks(E)), dim3(kBlock), 0, s, M, ws);
-        QF_LAUNCH_CHECK();
-        size_t tb = ws.temp_bytes;
-        QF_HIP_TRY(rocprim::radix_sort_keys(ws.temp, tb, ws.nkey_a, ws.nkey_b, (size_t)(2 * E), 0, 64, s));
-        hipLaunchKernelGGL(range_kernel, dim3(blocks(2 * E)), dim3(kBlock), 0, s, ws.nkey_b, 2 * E, ws.nstart, ws.nend);
-        QF_LAUNCH_CHECK();
-        hipLaunchKernelGGL(boundary_sum_kernel, dim3(blocks(V)), dim3(kBlock), 0, s, V, ws, ox, boundary_weight, quadrics);
-        QF_LAUNCH_CHECK();
+        QF_MESH_LAUNCH(uses_kernel, 3 * F, M, ws);
+        QF_MESH_LAUNCH(boundary_plane_kernel, 3 * F, M, ws, ox);
+        const int st = build_neighbour_rows(M, ws, boundary_key_kernel, s);
+        if (st != QF_OK) return st;
+        QF_MESH_LAUNCH(boundary_sum_kernel, V, V, ws, ox, boundary_weight, quadrics);
     }
     hipLaunchKernelGGL(boundary_counts_kernel, dim3(1), dim3(1), 0, s, ws, ox, counts);
     QF_LAUNCH_CHECK();
@@ -1081,48 +1040,31 @@ extern "C" int qf_mesh_collapse_select_open(const double *vertices, int64_t n_ve
 
     QF_HIP_TRY(hipMemsetAsync(ws.info, 0, sizeof(Info), s));
     QF_HIP_TRY(hipMemsetAsync(ox.info, 0, sizeof(OpenInfo), s));
-    QF_HIP_TRY(hipMemsetAsync(ws.nstart, 0, 8 * (size_t)V, s));
-    QF_HIP_TRY(hipMemsetAsync(ws.nend, 0, 8 * (size_t)V, s));
     QF_HIP_TRY(hipMemsetAsync(ws.m1, 0xff, 8 * (size_t)V, s));
     QF_HIP_TRY(hipMemsetAsync(ox.nb, 0, 4 * (size_t)V, s));
     QF_HIP_TRY(hipMemsetAsync(ox.bad, 0, (size_t)V, s));
-    const int st = build_face_rows(M, ws, s);
+    int st = build_face_rows(M, ws, s);
+    if (st != QF_OK) return st;
+    st = build_neighbour_rows(M, ws, edge_key_kernel, s);
     if (st != QF_OK) return st;
     if (E > 0) {
         QF_HIP_TRY(hipMemsetAsync(ws.uses, 0, 4 * (size_t)E, s));
         QF_HIP_TRY(hipMemsetAsync(ox.iso, 0, (size_t)E, s));
-        hipLaunchKernelGGL(edge_key_kernel, dim3(blocks(E)), dim3(kBlock), 0, s, M, ws);
-        QF_LAUNCH_CHECK();
-        size_t tb = ws.temp_bytes;
-        QF_HIP_TRY(rocprim::radix_sort_keys(ws.temp, tb, ws.nkey_a, ws.nkey_b, (size_t)(2 * E), 0, 64, s));
-        hipLaunchKernelGGL(range_kernel, dim3(blocks(2 * E)), dim3(kBlock), 0, s, ws.nkey_b, 2 * E, ws.nstart, ws.nend);
-        QF_LAUNCH_CHECK();
-        if (F > 0) {
-            hipLaunchKernelGGL(uses_kernel, dim3(blocks(3 * F)), dim3(kBlock), 0, s, M, ws);
-            QF_LAUNCH_CHECK();
-            hipLaunchKernelGGL(isolated_kernel, dim3(blocks(F)), dim3(kBlock), 0, s, M, ws, ox);
-            QF_LAUNCH_CHECK();
-        }
-        hipLaunchKernelGGL(class_edge_kernel, dim3(blocks(E)), dim3(kBlock), 0, s, M, ws, ox);
-        QF_LAUNCH_CHECK();
+        QF_MESH_LAUNCH(uses_kernel, 3 * F, M, ws);
+        QF_MESH_LAUNCH(isolated_kernel, F, M, ws, ox);
+        QF_MESH_LAUNCH(class_edge_kernel, E, M, ws, ox);
     }
-    hipLaunchKernelGGL(class_vertex_kernel, dim3(blocks(V)), dim3(kBlock), 0, s, V, vertex_lock, ws, ox);
-    QF_LAUNCH_CHECK();
+    QF_MESH_LAUNCH(class_vertex_kernel, V, V, vertex_lock, ws, ox);
     if (E > 0) {
-        hipLaunchKernelGGL(candidate_open_kernel, dim3(blocks(E)), dim3(kBlock), 0, s, M, ws, ox, max_cost, (uint64_t)round);
-        QF_LAUNCH_CHECK();
-        hipLaunchKernelGGL(min2_kernel, dim3(blocks(V)), dim3(kBlock), 0, s, V, ws);
-        QF_LAUNCH_CHECK();
-        hipLaunchKernelGGL(select_kernel, dim3(blocks(E)), dim3(kBlock), 0, s, M, ws);
-        QF_LAUNCH_CHECK();
+        QF_MESH_LAUNCH(candidate_open_kernel, E, M, ws, ox, max_cost, (uint64_t)round);
+        QF_MESH_LAUNCH(min2_kernel, V, V, ws);
+        QF_MESH_LAUNCH(select_kernel, E, M, ws);
         size_t tb = ws.temp_bytes;
         QF_HIP_TRY(rocprim::radix_sort_pairs(ws.temp, tb, ws.skey_a, ws.skey_b, ws.sval_a, ws.sval_b, (size_t)E, 0, 64, s));
-        hipLaunchKernelGGL(weight_kernel, dim3(blocks(E)), dim3(kBlock), 0, s, E, ws, ox);
-        QF_LAUNCH_CHECK();
+        QF_MESH_LAUNCH(weight_kernel, E, E, ws, ox);
         size_t sb = ox.temp_bytes;
         QF_HIP_TRY(rocprim::exclusive_scan(ox.temp, sb, ox.weight, ox.before, (int32_t)0, (size_t)E, rocprim::plus<int32_t>(), s));
-        hipLaunchKernelGGL(budget_kernel, dim3(blocks(E)), dim3(kBlock), 0, s, E, faces_to_remove, ws, ox);
-        QF_LAUNCH_CHECK();
+        QF_MESH_LAUNCH(budget_kernel, E, E, faces_to_remove, ws, ox);
     }
     hipLaunchKernelGGL(open_counts_kernel, dim3(1), dim3(1), 0, s, ws, ox, counts);
     QF_LAUNCH_CHECK();
@@ -1148,20 +1090,8 @@ extern "C" int qf_mesh_collapse_apply_open(double *vertices, int64_t n_vertices,
     QF_HIP_TRY(hipMemsetAsync(ws.remap, 0xff, 4 * (size_t)n_vertices, s));
     // every taken edge removes at least one face, so no more than faces_to_remove are taken
     const int64_t n = faces_to_remove < n_edges ? faces_to_remove : n_edges;
-    if (n > 0) {
-        hipLaunchKernelGGL(apply_open_kernel, dim3(blocks(n)), dim3(kBlock), 0, s, vertices, quadrics, edges, n_edges, n_vertices,
-                           n, faces_to_remove, ws, sp.ox);
-        QF_LAUNCH_CHECK();
-    }
-    if (n_faces > 0) {
-        hipLaunchKernelGGL(remap_kernel, dim3(blocks(3 * n_faces)), dim3(kBlock), 0, s, faces, 3 * n_faces, n_vertices,
-                           ws.remap);
-        QF_LAUNCH_CHECK();
-    }
-    if (n_targets > 0) {
-        hipLaunchKernelGGL(remap_kernel, dim3(blocks(n_targets)), dim3(kBlock), 0, s, vertex_target, n_targets, n_vertices,
-                           ws.remap);
-        QF_LAUNCH_CHECK();
-    }
+    QF_MESH_LAUNCH(apply_open_kernel, n, vertices, quadrics, edges, n_edges, n_vertices, n, faces_to_remove, ws, sp.ox);
+    QF_MESH_LAUNCH(remap_kernel, 3 * n_faces, faces, 3 * n_faces, n_vertices, ws.remap);
+    QF_MESH_LAUNCH(remap_kernel, n_targets, vertex_target, n_targets, n_vertices, ws.remap);
     return QF_OK;
 }

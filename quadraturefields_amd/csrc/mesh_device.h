@@ -15,6 +15,16 @@ __device__ __forceinline__ int64_t gtid() { return (int64_t)blockIdx.x * blockDi
 
 inline unsigned blocks(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
+// One thread per item on the entry point's stream `s`; nothing is launched for no items.  Returns QF_ERR_HIP from the
+// enclosing function if the launch fails.
+#define QF_MESH_LAUNCH(kernel, count, ...)                                                         \
+    do {                                                                                           \
+        if ((count) > 0) {                                                                         \
+            hipLaunchKernelGGL(kernel, dim3(blocks(count)), dim3(kBlock), 0, s, __VA_ARGS__);      \
+            QF_LAUNCH_CHECK();                                                                     \
+        }                                                                                          \
+    } while (0)
+
 // Sum of `v` over the wave, added to *dst by one lane.  Every lane of the wave must call it.
 __device__ __forceinline__ void tally(unsigned long long *dst, int v)
 {

@@ -269,22 +269,14 @@ extern "C" int qf_mesh_manifold_count(const int64_t *faces, int64_t n_faces, int
     QF_HIP_TRY(hipMemsetAsync(ws.split, 0, (size_t)ws.zero_bytes, s));
     if (E > 0) QF_HIP_TRY(hipMemsetAsync(ws.lo, 0xff, 4 * (size_t)E, s));
     if (F > 0) {
-        hipLaunchKernelGGL(classify_kernel, dim3(blocks(F)), dim3(kBlock), 0, s, J, ws);
-        QF_LAUNCH_CHECK();
-        hipLaunchKernelGGL(uses_kernel, dim3(blocks(3 * F)), dim3(kBlock), 0, s, J, ws);
-        QF_LAUNCH_CHECK();
-        if (E > 0) {
-            hipLaunchKernelGGL(link_kernel, dim3(blocks(E)), dim3(kBlock), 0, s, J, ws);
-            QF_LAUNCH_CHECK();
-        }
-        hipLaunchKernelGGL(flatten_kernel, dim3(blocks(F)), dim3(kBlock), 0, s, J, ws);
-        QF_LAUNCH_CHECK();
-        hipLaunchKernelGGL(extras_kernel, dim3(blocks(3 * F)), dim3(kBlock), 0, s, J, ws);
-        QF_LAUNCH_CHECK();
+        QF_MESH_LAUNCH(classify_kernel, F, J, ws);
+        QF_MESH_LAUNCH(uses_kernel, 3 * F, J, ws);
+        QF_MESH_LAUNCH(link_kernel, E, J, ws);
+        QF_MESH_LAUNCH(flatten_kernel, F, J, ws);
+        QF_MESH_LAUNCH(extras_kernel, 3 * F, J, ws);
         const int st = scan_bytes(ws.flag, 3 * F, ItemNonZero{}, ws.part, ws.pos, &ws.info->extra_total, s);
         if (st != QF_OK) return st;
-        hipLaunchKernelGGL(split_count_kernel, dim3(blocks(V)), dim3(kBlock), 0, s, V, ws);
-        QF_LAUNCH_CHECK();
+        QF_MESH_LAUNCH(split_count_kernel, V, V, ws);
     }
     hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(1), 0, s, V, ws, counts);
     QF_LAUNCH_CHECK();
@@ -306,14 +298,8 @@ extern "C" int qf_mesh_manifold_emit(const double *vertices, const int64_t *face
     const uint64_t *src = reinterpret_cast<const uint64_t *>(vertices);
     uint64_t *out = reinterpret_cast<uint64_t *>(out_vertices);
     if (n_out_vertices > 0) {
-        hipLaunchKernelGGL(vertex_emit_kernel, dim3(blocks(V)), dim3(kBlock), 0, s, src, V, ws, out, n_out_vertices,
-                           vertex_map);
-        QF_LAUNCH_CHECK();
+        QF_MESH_LAUNCH(vertex_emit_kernel, V, src, V, ws, out, n_out_vertices, vertex_map);
     }
-    if (F > 0) {
-        hipLaunchKernelGGL(corner_emit_kernel, dim3(blocks(3 * F)), dim3(kBlock), 0, s, src, faces, V, F, ws, out,
-                           n_out_vertices, out_faces, vertex_map);
-        QF_LAUNCH_CHECK();
-    }
+    QF_MESH_LAUNCH(corner_emit_kernel, 3 * F, src, faces, V, F, ws, out, n_out_vertices, out_faces, vertex_map);
     return QF_OK;
 }

@@ -242,12 +242,9 @@ extern "C" int qf_mesh_sample_prepare(const double *vertices, int64_t n_vertices
     const Job J{vertices, faces, face_weight, V, F};
 
     QF_HIP_TRY(hipMemsetAsync(ws.info, 0, sizeof(Info), s));
-    hipLaunchKernelGGL(vertices_kernel, dim3(blocks(V)), dim3(kBlock), 0, s, J, ws);
-    QF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(measure_kernel, dim3(blocks(F)), dim3(kBlock), 0, s, J, ws);
-    QF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(quantise_kernel, dim3(blocks(F)), dim3(kBlock), 0, s, J, ws);
-    QF_LAUNCH_CHECK();
+    QF_MESH_LAUNCH(vertices_kernel, V, J, ws);
+    QF_MESH_LAUNCH(measure_kernel, F, J, ws);
+    QF_MESH_LAUNCH(quantise_kernel, F, J, ws);
     tb = ws.temp_bytes;
     QF_HIP_TRY(rocprim::inclusive_scan(ws.temp, tb, ws.q, ws.cum, (size_t)F, rocprim::plus<uint64_t>(), s));
     hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(1), 0, s, J, ws, counts);

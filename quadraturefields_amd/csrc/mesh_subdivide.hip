@@ -403,12 +403,9 @@ extern "C" int qf_mesh_edges_count(const int64_t *faces, int64_t n_faces, int64_
     if (F > 0) {
         QF_HIP_TRY(hipMemsetAsync(ws.table, 0xff, 4 * (size_t)ws.slots, s));
         QF_HIP_TRY(hipMemsetAsync(ws.uses, 0, 4 * (size_t)ws.slots, s));
-        hipLaunchKernelGGL(edge_classify_kernel, dim3(blocks(F)), dim3(kBlock), 0, s, faces, F, n_vertices, ws);
-        QF_LAUNCH_CHECK();
-        hipLaunchKernelGGL(edge_insert_kernel, dim3(blocks(H)), dim3(kBlock), 0, s, faces, H, ws);
-        QF_LAUNCH_CHECK();
-        hipLaunchKernelGGL(edge_flag_kernel, dim3(blocks(H)), dim3(kBlock), 0, s, H, ws);
-        QF_LAUNCH_CHECK();
+        QF_MESH_LAUNCH(edge_classify_kernel, F, faces, F, n_vertices, ws);
+        QF_MESH_LAUNCH(edge_insert_kernel, H, faces, H, ws);
+        QF_MESH_LAUNCH(edge_flag_kernel, H, H, ws);
     }
     const int st = scan_bytes(ws.first, H, ItemNonZero{}, ws.part, ws.pos, &ws.info->edge_total, s);
     if (st != QF_OK) return st;
@@ -427,11 +424,8 @@ extern "C" int qf_mesh_edges_emit(const int64_t *faces, int64_t n_faces, int64_t
     EdgeWorkspace ws = carve_edges(workspace, n_faces);
     if (workspace_bytes < ws.bytes) return QF_ERR_INVALID_ARGUMENT;
     hipStream_t s = qf_stream(stream);
-    if (n_faces > 0) {
-        const int64_t H = 3 * n_faces;
-        hipLaunchKernelGGL(edge_emit_kernel, dim3(blocks(H)), dim3(kBlock), 0, s, faces, H, ws, edges, n_edges, face_edges);
-        QF_LAUNCH_CHECK();
-    }
+    const int64_t H = 3 * n_faces;
+    QF_MESH_LAUNCH(edge_emit_kernel, H, faces, H, ws, edges, n_edges, face_edges);
     return QF_OK;
 }
 
@@ -454,10 +448,7 @@ extern "C" int qf_mesh_subdivide_count(const int64_t *faces, int64_t n_faces, in
 
     QF_HIP_TRY(hipMemsetAsync(ws.info, 0, sizeof(SplitInfo), s));
     if (J.E > 0) QF_HIP_TRY(hipMemsetAsync(ws.owner, 0x7f, 4 * (size_t)J.E, s));    // 0x7f7f7f7f: above every half-edge id
-    if (J.F > 0) {
-        hipLaunchKernelGGL(split_classify_kernel, dim3(blocks(J.F)), dim3(kBlock), 0, s, J, ws);
-        QF_LAUNCH_CHECK();
-    }
+    QF_MESH_LAUNCH(split_classify_kernel, J.F, J, ws);
     int st = scan_bytes(ws.children, J.F, ItemValue{}, ws.fpart, ws.fpos, &ws.info->face_total, s);
     if (st != QF_OK) return st;
     st = scan_bytes(edge_mark, J.E, ItemNonZero{}, ws.epart, ws.epos, &ws.info->mark_total, s);
@@ -483,15 +474,12 @@ extern "C" int qf_mesh_subdivide_emit(const double *vertices, const int64_t *fac
     if (workspace_bytes < ws.bytes) return QF_ERR_INVALID_ARGUMENT;
     hipStream_t s = qf_stream(stream);
     if (n_out_vertices > 0) {
-        hipLaunchKernelGGL(split_copy_vertices_kernel, dim3(blocks(J.V)), dim3(kBlock), 0, s,
-                           reinterpret_cast<const uint64_t *>(vertices), J.V, ws, reinterpret_cast<uint64_t *>(out_vertices),
-                           n_out_vertices, vertex_parents);
-        QF_LAUNCH_CHECK();
+        QF_MESH_LAUNCH(split_copy_vertices_kernel, J.V, reinterpret_cast<const uint64_t *>(vertices), J.V, ws,
+                       reinterpret_cast<uint64_t *>(out_vertices), n_out_vertices, vertex_parents);
     }
     if (J.F > 0 && (n_out_faces > 0 || n_out_vertices > J.V)) {
-        hipLaunchKernelGGL(split_emit_kernel, dim3(blocks(J.F)), dim3(kBlock), 0, s, J, ws, vertices, out_vertices,
-                           n_out_vertices, vertex_parents, out_faces, n_out_faces, face_map);
-        QF_LAUNCH_CHECK();
+        QF_MESH_LAUNCH(split_emit_kernel, J.F, J, ws, vertices, out_vertices, n_out_vertices, vertex_parents, out_faces,
+                       n_out_faces, face_map);
     }
     return QF_OK;
 }

@@ -329,28 +329,17 @@ extern "C" int qf_mesh_weld_count(const double *vertices, int64_t n_vertices, co
     QF_HIP_TRY(hipMemsetAsync(ws.info, 0, sizeof(Info), s));
     QF_HIP_TRY(hipMemsetAsync(ws.size, 0, 4 * (size_t)V, s));
     QF_HIP_TRY(hipMemsetAsync(ws.table, 0xff, 8 * (size_t)ws.slots, s));        // table and head
-    hipLaunchKernelGGL(cells_kernel, dim3(blocks(V)), dim3(kBlock), 0, s, J, ws);
-    QF_LAUNCH_CHECK();
-    if (F > 0) {
-        hipLaunchKernelGGL(faces_kernel, dim3(blocks(F)), dim3(kBlock), 0, s, J, ws);
-        QF_LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(insert_kernel, dim3(blocks(V)), dim3(kBlock), 0, s, J, ws);
-    QF_LAUNCH_CHECK();
+    QF_MESH_LAUNCH(cells_kernel, V, J, ws);
+    QF_MESH_LAUNCH(faces_kernel, F, J, ws);
+    QF_MESH_LAUNCH(insert_kernel, V, J, ws);
     if (cell > 0.0) {
-        hipLaunchKernelGGL(link_kernel, dim3(blocks(V)), dim3(kBlock), 0, s, J, ws);
-        QF_LAUNCH_CHECK();
+        QF_MESH_LAUNCH(link_kernel, V, J, ws);
     }
-    hipLaunchKernelGGL(flatten_kernel, dim3(blocks(V)), dim3(kBlock), 0, s, J, ws);
-    QF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(roots_kernel, dim3(blocks(V)), dim3(kBlock), 0, s, J, ws);
-    QF_LAUNCH_CHECK();
+    QF_MESH_LAUNCH(flatten_kernel, V, J, ws);
+    QF_MESH_LAUNCH(roots_kernel, V, J, ws);
     const int st = scan_bytes(ws.flag, V, ItemNonZero{}, ws.part, ws.pos, &ws.info->root_total, s);
     if (st != QF_OK) return st;
-    if (F > 0) {
-        hipLaunchKernelGGL(face_tally_kernel, dim3(blocks(F)), dim3(kBlock), 0, s, J, ws);
-        QF_LAUNCH_CHECK();
-    }
+    QF_MESH_LAUNCH(face_tally_kernel, F, J, ws);
     hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(1), 0, s, J, ws, counts);
     QF_LAUNCH_CHECK();
     return QF_OK;
@@ -368,14 +357,9 @@ extern "C" int qf_mesh_weld_emit(const double *vertices, int64_t n_vertices, con
     if (workspace_bytes < ws.bytes) return QF_ERR_INVALID_ARGUMENT;
     hipStream_t s = qf_stream(stream);
     if (n_out_vertices > 0 || vertex_class) {
-        hipLaunchKernelGGL(vertex_emit_kernel, dim3(blocks(V)), dim3(kBlock), 0, s,
-                           reinterpret_cast<const uint64_t *>(vertices), V, ws, reinterpret_cast<uint64_t *>(out_vertices),
-                           n_out_vertices, vertex_map, vertex_class);
-        QF_LAUNCH_CHECK();
+        QF_MESH_LAUNCH(vertex_emit_kernel, V, reinterpret_cast<const uint64_t *>(vertices), V, ws,
+                       reinterpret_cast<uint64_t *>(out_vertices), n_out_vertices, vertex_map, vertex_class);
     }
-    if (F > 0) {
-        hipLaunchKernelGGL(face_emit_kernel, dim3(blocks(3 * F)), dim3(kBlock), 0, s, faces, F, ws, out_faces);
-        QF_LAUNCH_CHECK();
-    }
+    QF_MESH_LAUNCH(face_emit_kernel, 3 * F, faces, F, ws, out_faces);
     return QF_OK;
 }

@@ -416,8 +416,7 @@ extern "C" int qf_uv_atlas_measure(const double *vertices, int64_t n_vertices, c
     QF_LAUNCH_CHECK();
     hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(1), 0, s, ws, counts);
     QF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(measure_kernel, dim3(blocks(n_faces)), dim3(kBlock), 0, s, M, ws, counts);
-    QF_LAUNCH_CHECK();
+    QF_MESH_LAUNCH(measure_kernel, n_faces, M, ws, counts);
     return QF_OK;
 }
 
@@ -452,16 +451,12 @@ extern "C" int qf_uv_atlas_emit(const double *vertices, int64_t n_vertices, cons
     const int64_t F = n_faces;
     const int status = probe(F, texels_per_unit, max_leg, texture_size, ws, result, class_counts, s);
     if (status != QF_OK) return status;
-    hipLaunchKernelGGL(key_kernel, dim3(blocks(F)), dim3(kBlock), 0, s, F, texels_per_unit, (int)max_leg, ws);
-    QF_LAUNCH_CHECK();
+    QF_MESH_LAUNCH(key_kernel, F, F, texels_per_unit, (int)max_leg, ws);
     size_t tb = ws.temp_bytes;
     QF_HIP_TRY(rocprim::radix_sort_pairs(ws.temp, tb, ws.key_a, ws.key_b, ws.fid_a, ws.fid_b, (size_t)F, 0, kKeyBits, s));
-    hipLaunchKernelGGL(rank_kernel, dim3(blocks(F)), dim3(kBlock), 0, s, F, ws);
-    QF_LAUNCH_CHECK();
+    QF_MESH_LAUNCH(rank_kernel, F, F, ws);
     const Mesh M = {vertices, faces, n_vertices, F};
     const Out out = {out_vertices, out_uv, face_class, face_origin, face_half};
-    hipLaunchKernelGGL(emit_kernel, dim3(blocks(F)), dim3(kBlock), 0, s, M, texels_per_unit, (int)max_leg,
-                       texture_size, ws, out);
-    QF_LAUNCH_CHECK();
+    QF_MESH_LAUNCH(emit_kernel, F, M, texels_per_unit, (int)max_leg, texture_size, ws, out);
     return QF_OK;
 }

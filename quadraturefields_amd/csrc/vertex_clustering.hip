@@ -546,30 +546,23 @@ extern "C" int qf_vertex_clustering_count(const double *vertices, int64_t n_vert
     QF_LAUNCH_CHECK();
     hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(1), 0, s, M, ws, counts);
     QF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(key_kernel, dim3(blocks(V)), dim3(kBlock), 0, s, M, ws);
-    QF_LAUNCH_CHECK();
+    QF_MESH_LAUNCH(key_kernel, V, M, ws);
     QF_HIP_TRY(rocprim::radix_sort_pairs(ws.temp, tb, ws.key_a, ws.key_b, ws.vid_a, ws.vid_b, (size_t)V, 0, 63, s));
-    hipLaunchKernelGGL(head_kernel, dim3(blocks(V)), dim3(kBlock), 0, s, V, ws);
-    QF_LAUNCH_CHECK();
+    QF_MESH_LAUNCH(head_kernel, V, V, ws);
     tb = ws.temp_bytes;
     QF_HIP_TRY(rocprim::inclusive_scan(ws.temp, tb, ws.head, ws.seg, (size_t)V, rocprim::plus<int32_t>(), s));
     tb = ws.temp_bytes;
     QF_HIP_TRY(rocprim::exclusive_scan(ws.temp, tb, ws.first, ws.rank, 0, (size_t)V, rocprim::plus<int32_t>(), s));
-    hipLaunchKernelGGL(segment_kernel, dim3(blocks(V)), dim3(kBlock), 0, s, V, ws);
-    QF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(vertex_cell_kernel, dim3(blocks(V)), dim3(kBlock), 0, s, V, ws, counts);
-    QF_LAUNCH_CHECK();
+    QF_MESH_LAUNCH(segment_kernel, V, V, ws);
+    QF_MESH_LAUNCH(vertex_cell_kernel, V, V, ws, counts);
     if (F == 0) return QF_OK;
-    hipLaunchKernelGGL(triple_kernel, dim3(blocks(F)), dim3(kBlock), 0, s, M, ws);
-    QF_LAUNCH_CHECK();
+    QF_MESH_LAUNCH(triple_kernel, F, M, ws);
     tb = ws.temp_bytes;
     QF_HIP_TRY(rocprim::radix_sort_pairs(ws.temp, tb, ws.fk_a, ws.fk_b, ws.fid_a, ws.fid_b, (size_t)F, 0, 62, s));
-    hipLaunchKernelGGL(gather_c0_kernel, dim3(blocks(F)), dim3(kBlock), 0, s, F, ws);
-    QF_LAUNCH_CHECK();
+    QF_MESH_LAUNCH(gather_c0_kernel, F, F, ws);
     tb = ws.temp_bytes;
     QF_HIP_TRY(rocprim::radix_sort_pairs(ws.temp, tb, ws.fk0_a, ws.fk0_b, ws.fid_b, ws.fid_a, (size_t)F, 0, 31, s));
-    hipLaunchKernelGGL(keep_kernel, dim3(blocks(F)), dim3(kBlock), 0, s, F, ws);
-    QF_LAUNCH_CHECK();
+    QF_MESH_LAUNCH(keep_kernel, F, F, ws);
     tb = ws.temp_bytes;
     QF_HIP_TRY(rocprim::exclusive_scan(ws.temp, tb, ws.keep, ws.fpos, 0, (size_t)F, rocprim::plus<int32_t>(), s));
     hipLaunchKernelGGL(face_total_kernel, dim3(1), dim3(1), 0, s, F, ws, counts);
@@ -600,31 +593,23 @@ extern "C" int qf_vertex_clustering_emit(const double *vertices, int64_t n_verti
 
     if (n_out_vertices > 0) {
         if (contraction == QF_CLUSTER_AVERAGE) {
-            hipLaunchKernelGGL(average_kernel, dim3(blocks(n_out_vertices)), dim3(kBlock), 0, s, M, ws, out_vertices,
-                               n_out_vertices);
-            QF_LAUNCH_CHECK();
+            QF_MESH_LAUNCH(average_kernel, n_out_vertices, M, ws, out_vertices, n_out_vertices);
         } else {
             QF_HIP_TRY(hipMemsetAsync(ws.inc_start, 0, 8 * V, s));
             QF_HIP_TRY(hipMemsetAsync(ws.inc_end, 0, 8 * V, s));
             if (F > 0) {
-                hipLaunchKernelGGL(plane_kernel, dim3(blocks(F)), dim3(kBlock), 0, s, M, ws);
-                QF_LAUNCH_CHECK();
-                hipLaunchKernelGGL(incidence_kernel, dim3(blocks(3 * F)), dim3(kBlock), 0, s, M, ws);
-                QF_LAUNCH_CHECK();
+                QF_MESH_LAUNCH(plane_kernel, F, M, ws);
+                QF_MESH_LAUNCH(incidence_kernel, 3 * F, M, ws);
                 size_t tb = ws.temp_bytes;
                 QF_HIP_TRY(rocprim::radix_sort_pairs(ws.temp, tb, ws.ik_a, ws.ik_b, ws.if_a, ws.if_b, (size_t)(3 * F),
                                                      0, 31, s));
-                hipLaunchKernelGGL(incidence_range_kernel, dim3(blocks(3 * F)), dim3(kBlock), 0, s, 3 * F, ws);
-                QF_LAUNCH_CHECK();
+                QF_MESH_LAUNCH(incidence_range_kernel, 3 * F, 3 * F, ws);
             }
-            hipLaunchKernelGGL(quadric_kernel, dim3(blocks(n_out_vertices)), dim3(kBlock), 0, s, M, ws, out_vertices,
-                               n_out_vertices, fb);
-            QF_LAUNCH_CHECK();
+            QF_MESH_LAUNCH(quadric_kernel, n_out_vertices, M, ws, out_vertices, n_out_vertices, fb);
         }
     }
     if (n_out_faces > 0) {
-        hipLaunchKernelGGL(face_emit_kernel, dim3(blocks(F)), dim3(kBlock), 0, s, F, ws, out_faces, n_out_faces);
-        QF_LAUNCH_CHECK();
+        QF_MESH_LAUNCH(face_emit_kernel, F, F, ws, out_faces, n_out_faces);
     }
     return QF_OK;
 }

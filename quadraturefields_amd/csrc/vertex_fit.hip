@@ -458,14 +458,6 @@ bool sizes_ok(int64_t V, int64_t F, int64_t N, int64_t C)
 
 }  // namespace
 
-#define QF_FIT_LAUNCH(kernel, count, ...)                                                          \
-    do {                                                                                           \
-        if ((count) > 0) {                                                                         \
-            hipLaunchKernelGGL(kernel, dim3(blocks(count)), dim3(kBlock), 0, s, __VA_ARGS__);      \
-            QF_LAUNCH_CHECK();                                                                     \
-        }                                                                                          \
-    } while (0)
-
 extern "C" int64_t qf_vertex_fit_workspace_bytes(int64_t n_vertices, int64_t n_faces, int64_t n_samples, int64_t n_columns)
 {
     if (!sizes_ok(n_vertices, n_faces, n_samples, n_columns)) return -1;
@@ -500,20 +492,20 @@ extern "C" int qf_vertex_fit_assemble(const int64_t *faces, int64_t n_faces, int
     QF_HIP_TRY(hipMemsetAsync(vertex_mass, 0, sizeof(double) * V, s));
     QF_HIP_TRY(hipMemsetAsync(rhs, 0, sizeof(double) * V * C, s));
     if (F > 0) QF_HIP_TRY(hipMemsetAsync(face_gram, 0, sizeof(double) * 9 * F, s));
-    QF_FIT_LAUNCH(validity_samples_kernel, N, J, ws);
-    QF_FIT_LAUNCH(validity_rows_kernel, N * C, targets, N, (int)C, y_stride, ws);
-    QF_FIT_LAUNCH(validity_rows_kernel, V * C, prior, V, (int)C, x0_stride, ws);
+    QF_MESH_LAUNCH(validity_samples_kernel, N, J, ws);
+    QF_MESH_LAUNCH(validity_rows_kernel, N * C, targets, N, (int)C, y_stride, ws);
+    QF_MESH_LAUNCH(validity_rows_kernel, V * C, prior, V, (int)C, x0_stride, ws);
     hipLaunchKernelGGL(verdict_kernel, dim3(1), dim3(1), 0, s, ws, prior_weight);
     QF_LAUNCH_CHECK();
     if (F > 0) {
-        QF_FIT_LAUNCH(corner_key_kernel, 3 * F, J, ws);
+        QF_MESH_LAUNCH(corner_key_kernel, 3 * F, J, ws);
         size_t tb = ws.temp_bytes;
         QF_HIP_TRY(rocprim::radix_sort_keys(ws.temp, tb, ws.key_a, ws.key_b, (size_t)(3 * F), 0, 64, s));
-        QF_FIT_LAUNCH(range_kernel, 3 * F, ws.key_b, 3 * F, ws.cstart, ws.cend);
-        QF_FIT_LAUNCH(gram_kernel, F, J, ws, face_gram);
+        QF_MESH_LAUNCH(range_kernel, 3 * F, ws.key_b, 3 * F, ws.cstart, ws.cend);
+        QF_MESH_LAUNCH(gram_kernel, F, J, ws, face_gram);
     }
-    QF_FIT_LAUNCH(vertex_kernel, V, J, ws, face_gram, vertex_mass);
-    QF_FIT_LAUNCH(rhs_kernel, V * C, J, ws, rhs);
+    QF_MESH_LAUNCH(vertex_kernel, V, J, ws, face_gram, vertex_mass);
+    QF_MESH_LAUNCH(rhs_kernel, V * C, J, ws, rhs);
     hipLaunchKernelGGL(counts_kernel, dim3(1), dim3(1), 0, s, ws, counts);
     QF_LAUNCH_CHECK();
     return QF_OK;
@@ -547,18 +539,18 @@ extern "C" int qf_vertex_fit_solve(const int64_t *faces, int64_t n_faces, int64_
 
     QF_HIP_TRY(hipMemsetAsync(&ws.info->clamped, 0, sizeof(unsigned long long), s));
     QF_HIP_TRY(hipMemsetAsync(stats, 0, sizeof(double) * 2 * C, s));
-    QF_FIT_LAUNCH(init_kernel, n, ws, rhs, V, Ci);
+    QF_MESH_LAUNCH(init_kernel, n, ws, rhs, V, Ci);
     QF_FIT_DOT(1, 0, ws.R, (const double *)nullptr);
     for (int64_t k = 0; k < iterations; ++k) {
-        QF_FIT_LAUNCH(operator_kernel, n, ws, faces, face_gram, V, Ci);
+        QF_MESH_LAUNCH(operator_kernel, n, ws, faces, face_gram, V, Ci);
         QF_FIT_DOT(0, 1, ws.P, ws.Q);
-        QF_FIT_LAUNCH(update_zr_kernel, n, ws, V, Ci);
+        QF_MESH_LAUNCH(update_zr_kernel, n, ws, V, Ci);
         QF_FIT_DOT(1, 2, ws.R, (const double *)nullptr);
-        QF_FIT_LAUNCH(update_p_kernel, n, ws, V, Ci);
+        QF_MESH_LAUNCH(update_p_kernel, n, ws, V, Ci);
     }
     QF_FIT_DOT(2, 3, rhs, (const double *)nullptr);
     QF_FIT_DOT(2, 4, ws.R, (const double *)nullptr);
-    QF_FIT_LAUNCH(finish_kernel, n, ws, prior, x0_stride, vertex_mass, clamp_mask, V, Ci, out, out_stride);
+    QF_MESH_LAUNCH(finish_kernel, n, ws, prior, x0_stride, vertex_mass, clamp_mask, V, Ci, out, out_stride);
     hipLaunchKernelGGL(counts_kernel, dim3(1), dim3(1), 0, s, ws, counts);
     QF_LAUNCH_CHECK();
 #undef QF_FIT_DOT

@@ -21,6 +21,8 @@ import torch
 import torch.nn.functional as F
 
 from . import _C
+from ._mesh_args import (counts_buffer, mask_u8, mesh_inputs, raise_invalid_faces, read_counts, to_numpy, trimesh_tensors,
+                         workspace, zero_counts)
 from .mesh_io import TriMesh
 from .parameterization_utils import concatenate_meshes
 
@@ -125,7 +127,7 @@ def normalise_vertices(verts: torch.Tensor, n: int) -> torch.Tensor:
 
 
 def _normalised_mesh(verts: torch.Tensor, faces: torch.Tensor, n: int) -> TriMesh:
-    return TriMesh(normalise_vertices(verts, n).cpu().numpy(), faces.cpu().numpy())
+    return TriMesh(*to_numpy(normalise_vertices(verts, n), faces))
 
 
 def quadrature_surface_mesh(grid, grads, binaries, *, sigma=100.0, include_grad=True, omega=100.0, thres=0.0,
@@ -168,40 +170,20 @@ def simplify_vertex_clustering(vertices: torch.Tensor, faces: torch.Tensor, voxe
     ``return_fallbacks=True`` the number of quadric cells whose vertex fell back to the mean is returned third.
     Raises ValueError for host tensors, a voxel size that is not positive and finite, non-finite vertices, face indices
     outside [0, V), V or F of 2^31 or more, or more than 2^21 cells along an axis."""
-    if not isinstance(vertices, torch.Tensor) or not isinstance(faces, torch.Tensor):
-        raise TypeError("vertices and faces must be torch.Tensors")
-    if not vertices.is_cuda or not faces.is_cuda:
-        raise ValueError("simplify_vertex_clustering needs device tensors (quadraturefields_amd has no CPU fallback)")
-    if vertices.device != faces.device:
-        raise ValueError(f"vertices on {vertices.device} and faces on {faces.device}")
-    if vertices.ndim != 2 or vertices.shape[1] != 3 or faces.ndim != 2 or faces.shape[1] != 3:
-        raise ValueError(f"vertices and faces must be [N,3], got {tuple(vertices.shape)} and {tuple(faces.shape)}")
-    if not vertices.is_floating_point():
-        raise TypeError(f"vertices must be floating point, got {vertices.dtype}")
-    if faces.dtype not in (torch.int64, torch.int32):
-        raise TypeError(f"faces must be int64 or int32, got {faces.dtype}")
     if contraction not in CONTRACTIONS:
         raise ValueError(f"contraction must be one of {sorted(CONTRACTIONS)}, got {contraction!r}")
     s = float(voxel_size)
     if not (math.isfinite(s) and s > 0):
         raise ValueError(f"voxel_size must be positive and finite, got {voxel_size}")
-    n_v, n_f = vertices.shape[0], faces.shape[0]
-    if n_v >= 2 ** 31 or n_f >= 2 ** 31:
-        raise ValueError(f"the mesh has {n_v} vertices and {n_f} faces; both must be < 2^31")
-    dev = vertices.device
+    v, f, dev, n_v, n_f = mesh_inputs(vertices, faces, "simplify_vertex_clustering", limit="F")
     if n_v == 0:
         if n_f:
-            raise ValueError(f"{n_f} faces index an empty vertex set")
+            raise_invalid_faces(n_f, 0)
         out = (torch.empty((0, 3), dtype=torch.float64, device=dev), torch.empty((0, 3), dtype=torch.int64, device=dev))
         return out + (0,) if return_fallbacks else out
-    v = vertices.to(torch.float64).contiguous()
-    f = faces.to(torch.int64).contiguous()
     lib = _C.lib()
     with torch.cuda.device(dev):
-        ws_bytes = int(lib.qf_vertex_clustering_workspace_bytes(n_v, n_f))
-        if ws_bytes < 0:
-            raise RuntimeError(f"qf_vertex_clustering_workspace_bytes refused V={n_v}, F={n_f}")
-        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+        ws, ws_bytes = workspace("qf_vertex_clustering_workspace_bytes", dev, V=n_v, F=n_f)
         counts = torch.empty((5,), dtype=torch.int64, device=dev)
         _C.check(lib.qf_vertex_clustering_count(_C.ptr(v), n_v, _C.ptr(f), n_f, s, _C.ptr(ws), ws_bytes,
                                                 _C.ptr(counts), _C.stream()), "qf_vertex_clustering_count")
@@ -230,12 +212,11 @@ def downsample_mesh(mesh: TriMesh, vx=0, device="cuda", merge_tolerance=None) ->
     if not vx > 0:
         return mesh
     dev = _C.resolve_device(device)
-    v, f = simplify_vertex_clustering(torch.from_numpy(np.asarray(mesh.vertices, np.float64)).to(dev),
-                                      torch.from_numpy(np.asarray(mesh.faces, np.int64)).to(dev), 1 / vx, "quadric")
+    v, f = simplify_vertex_clustering(*trimesh_tensors(mesh, dev), 1 / vx, "quadric")
     if merge_tolerance is not None:
         welded = weld_vertices_device(v, f, merge_tolerance)
         v, f = welded.vertices, welded.faces
-    return TriMesh(v.cpu().numpy(), f.cpu().numpy())
+    return TriMesh(*to_numpy(v, f))
 
 
 def mark_visited_cells(positions01: torch.Tensor, mask: torch.Tensor, out_of_range: torch.Tensor = None) -> None:
@@ -293,18 +274,26 @@ def transmittance_mask(radiance_field, estimator, views, *, max_samples=1024, ch
 CompactedMesh = namedtuple("CompactedMesh", ["vertices", "faces", "face_map", "vertex_map", "stats"])
 
 
-def _device_keep(keep, n_faces: int, device) -> torch.Tensor:
-    """A keep mask (tensor or array, bool or integer) as a contiguous device uint8 [F]; None stays None."""
-    if keep is None:
-        return None
-    k = keep if isinstance(keep, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(keep))
-    k = k.reshape(-1)
-    if k.shape[0] != n_faces:
-        raise ValueError(f"{k.shape[0]} keep flags for {n_faces} faces")
-    if k.is_floating_point() or k.is_complex():
-        raise TypeError(f"keep must be a bool or integer mask, got {k.dtype}")
-    k = k.to(device)
-    return (k if k.dtype == torch.uint8 else (k != 0).to(torch.uint8)).contiguous()
+def _compact_count(lib, dev, v, f, keep, flags: int, min_component_faces: int):
+    """Enqueue ``qf_mesh_compact_count``: ``(job, counts)``, the call's leading arguments with the workspace they point
+    into (for ``_compact_emit``) and the device counts, still unread."""
+    n_v, n_f = v.shape[0], f.shape[0]
+    ws, ws_bytes = workspace("qf_mesh_compact_workspace_bytes", dev, V=n_v, F=n_f)
+    counts = counts_buffer(_C.MESH_COMPACT_COUNTS, dev)
+    args = (_C.ptr(v), n_v, _C.ptr(f), n_f, _C.ptr(keep), flags, min_component_faces, _C.ptr(ws), ws_bytes)
+    _C.check(lib.qf_mesh_compact_count(*args, _C.ptr(counts), _C.stream()), "qf_mesh_compact_count")
+    return (args, ws), counts
+
+
+def _compact_emit(lib, dev, job, n_vertices: int, n_faces: int):
+    """``(vertices, faces, face_map, vertex_map)`` of the counted job, whose counts gave the two sizes."""
+    out_v = torch.empty((n_vertices, 3), dtype=torch.float64, device=dev)
+    out_f = torch.empty((n_faces, 3), dtype=torch.int64, device=dev)
+    face_map = torch.empty((n_faces,), dtype=torch.int64, device=dev)
+    vertex_map = torch.empty((n_vertices,), dtype=torch.int64, device=dev)
+    _C.check(lib.qf_mesh_compact_emit(*job[0], _C.ptr(out_v), n_vertices, _C.ptr(out_f), n_faces, _C.ptr(face_map),
+                                      _C.ptr(vertex_map), _C.stream()), "qf_mesh_compact_emit")
+    return out_v, out_f, face_map, vertex_map
 
 
 def compact_mesh_device(vertices: torch.Tensor, faces: torch.Tensor, keep=None, *, remove_degenerate: bool = False,
@@ -319,56 +308,25 @@ def compact_mesh_device(vertices: torch.Tensor, faces: torch.Tensor, keep=None, 
     [F',3], face_map int64 [F'], vertex_map int64 [V'], stats)``: the maps name the source face / vertex of every output
     row, ``stats`` is a dict of the eight counts (``_C.MESH_COMPACT_COUNTS``).  One host wait, for the counts.  Raises
     ValueError for host tensors, bad shapes and, with their number, faces that index outside [0, V)."""
-    if not isinstance(vertices, torch.Tensor) or not isinstance(faces, torch.Tensor):
-        raise TypeError("vertices and faces must be torch.Tensors")
-    if vertices.ndim != 2 or vertices.shape[1] != 3 or faces.ndim != 2 or faces.shape[1] != 3:
-        raise ValueError(f"vertices and faces must be [N,3], got {tuple(vertices.shape)} and {tuple(faces.shape)}")
-    if not vertices.is_floating_point():
-        raise TypeError(f"vertices must be floating point, got {vertices.dtype}")
-    if faces.dtype not in (torch.int64, torch.int32):
-        raise TypeError(f"faces must be int64 or int32, got {faces.dtype}")
     m = int(min_component_faces)
     if m != min_component_faces or m < 0 or m >= 2 ** 31:
         raise ValueError(f"min_component_faces must be an integer in [0, 2^31), got {min_component_faces}")
-    if not vertices.is_cuda or not faces.is_cuda:
-        raise ValueError("compact_mesh_device needs device tensors (quadraturefields_amd has no CPU fallback)")
-    if vertices.device != faces.device:
-        raise ValueError(f"vertices on {vertices.device} and faces on {faces.device}")
-    n_v, n_f = vertices.shape[0], faces.shape[0]
-    if n_v >= 2 ** 31 or n_f >= 2 ** 31:
-        raise ValueError(f"the mesh has {n_v} vertices and {n_f} faces; both must be < 2^31")
-    dev = vertices.device
-    k = _device_keep(keep, n_f, dev)
+    v, f, dev, n_v, n_f = mesh_inputs(vertices, faces, "compact_mesh_device", limit="F")
+    k = mask_u8(keep, n_f, dev, "keep flags")
     flags = ((_C.MESH_REMOVE_DEGENERATE if remove_degenerate else 0) | (_C.MESH_REMOVE_DUPLICATES if remove_duplicates else 0)
              | (_C.MESH_REMOVE_UNREFERENCED if remove_unreferenced else 0))
     if n_v == 0:
         if n_f:
-            raise ValueError(f"{n_f} faces have an index outside [0, 0)")
+            raise_invalid_faces(n_f, 0)
         empty = torch.empty((0,), dtype=torch.int64, device=dev)
-        return CompactedMesh(torch.empty((0, 3), dtype=torch.float64, device=dev), empty.reshape(0, 3), empty,
-                             empty.clone(), dict.fromkeys(_C.MESH_COMPACT_COUNTS, 0))
-    v = vertices.to(torch.float64).contiguous()
-    f = faces.to(torch.int64).contiguous()
+        return CompactedMesh(v.clone(), empty.reshape(0, 3), empty, empty.clone(), zero_counts(_C.MESH_COMPACT_COUNTS))
     lib = _C.lib()
     with torch.cuda.device(dev):
-        ws_bytes = int(lib.qf_mesh_compact_workspace_bytes(n_v, n_f))
-        if ws_bytes < 0:
-            raise RuntimeError(f"qf_mesh_compact_workspace_bytes refused V={n_v}, F={n_f}")
-        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-        counts = torch.empty((8,), dtype=torch.int64, device=dev)
-        _C.check(lib.qf_mesh_compact_count(_C.ptr(v), n_v, _C.ptr(f), n_f, _C.ptr(k), flags, m, _C.ptr(ws), ws_bytes,
-                                           _C.ptr(counts), _C.stream()), "qf_mesh_compact_count")
-        stats = dict(zip(_C.MESH_COMPACT_COUNTS, counts.tolist()))
+        job, counts = _compact_count(lib, dev, v, f, k, flags, m)
+        stats = read_counts(_C.MESH_COMPACT_COUNTS, counts)
         if stats["invalid_faces"]:
-            raise ValueError(f"{stats['invalid_faces']} faces have an index outside [0, {n_v})")
-        out_v = torch.empty((stats["vertices"], 3), dtype=torch.float64, device=dev)
-        out_f = torch.empty((stats["faces"], 3), dtype=torch.int64, device=dev)
-        face_map = torch.empty((stats["faces"],), dtype=torch.int64, device=dev)
-        vertex_map = torch.empty((stats["vertices"],), dtype=torch.int64, device=dev)
-        _C.check(lib.qf_mesh_compact_emit(_C.ptr(v), n_v, _C.ptr(f), n_f, _C.ptr(k), flags, m, _C.ptr(ws), ws_bytes,
-                                          _C.ptr(out_v), out_v.shape[0], _C.ptr(out_f), out_f.shape[0], _C.ptr(face_map),
-                                          _C.ptr(vertex_map), _C.stream()), "qf_mesh_compact_emit")
-    return CompactedMesh(out_v, out_f, face_map, vertex_map, stats)
+            raise_invalid_faces(stats["invalid_faces"], n_v)
+        return CompactedMesh(*_compact_emit(lib, dev, job, stats["vertices"], stats["faces"]), stats)
 
 
 def compact_mesh(mesh: TriMesh, keep=None, device="cuda", return_stats: bool = False, **options):
@@ -376,12 +334,10 @@ def compact_mesh(mesh: TriMesh, keep=None, device="cuda", return_stats: bool = F
     stats dict fourth with ``return_stats``).  Per-vertex ``visual.uv`` is carried through ``vertex_map``.  ``keep`` may
     be a device tensor: it then makes no round trip."""
     dev = keep.device if isinstance(keep, torch.Tensor) and keep.is_cuda else _C.resolve_device(device)
-    out = compact_mesh_device(torch.from_numpy(np.asarray(mesh.vertices, np.float64)).to(dev),
-                              torch.from_numpy(np.asarray(mesh.faces, np.int64)).to(dev), keep, **options)
-    vertex_map = out.vertex_map.cpu().numpy()
+    out = compact_mesh_device(*trimesh_tensors(mesh, dev), keep, **options)
+    vertices, faces, face_map, vertex_map = to_numpy(*out[:4])
     uv = None if mesh.visual.uv is None else np.asarray(mesh.visual.uv)[vertex_map]
-    cleaned = TriMesh(out.vertices.cpu().numpy(), out.faces.cpu().numpy(), uv)
-    res = (cleaned, out.face_map.cpu().numpy(), vertex_map)
+    res = (TriMesh(vertices, faces, uv), face_map, vertex_map)
     return res + (out.stats,) if return_stats else res
 
 
@@ -470,18 +426,6 @@ MeshEdges = namedtuple("MeshEdges", ["edges", "face_edges", "stats"])
 SubdividedMesh = namedtuple("SubdividedMesh", ["vertices", "faces", "face_map", "vertex_parents", "stats"])
 
 
-def _device_faces(faces, what: str) -> torch.Tensor:
-    if not isinstance(faces, torch.Tensor):
-        raise TypeError("faces must be a torch.Tensor")
-    if faces.ndim != 2 or faces.shape[1] != 3:
-        raise ValueError(f"faces must be [F,3], got {tuple(faces.shape)}")
-    if faces.dtype not in (torch.int64, torch.int32):
-        raise TypeError(f"faces must be int64 or int32, got {faces.dtype}")
-    if not faces.is_cuda:
-        raise ValueError(f"{what} needs device tensors (quadraturefields_amd has no CPU fallback)")
-    return faces.to(torch.int64).contiguous()
-
-
 def mesh_edges_device(faces: torch.Tensor, n_vertices: int) -> MeshEdges:
     """The undirected edges of a mesh, numbered on the device in the order of their first appearance (stage A of DESIGN.md
     section 3.9c).  ``faces``: device int64 or int32 [F,3] over ``n_vertices`` vertices.  Returns ``MeshEdges(edges int64
@@ -489,47 +433,26 @@ def mesh_edges_device(faces: torch.Tensor, n_vertices: int) -> MeshEdges:
     face f, -1 on a degenerate face (two equal indices), which contributes no edge; ``stats`` is a dict of the four
     counts (``_C.MESH_EDGES_COUNTS``).  One host wait, for the counts.  Raises ValueError for host tensors, bad shapes
     and, with their number, faces that index outside [0, n_vertices)."""
-    f = _device_faces(faces, "mesh_edges_device")
-    n_v, n_f = int(n_vertices), f.shape[0]
-    if n_v != n_vertices or n_v < 0 or n_v >= 2 ** 31 or 3 * n_f >= 2 ** 31:
-        raise ValueError(f"the mesh has {n_vertices} vertices and {n_f} faces; V and 3 F must be < 2^31")
-    dev = f.device
+    _, f, dev, n_v, n_f = mesh_inputs(None, faces, "mesh_edges_device", limit="3F", n_vertices=n_vertices)
     if n_v == 0:
         if n_f:
-            raise ValueError(f"{n_f} faces have an index outside [0, 0)")
+            raise_invalid_faces(n_f, 0)
         return MeshEdges(torch.empty((0, 2), dtype=torch.int64, device=dev), torch.empty((0, 3), dtype=torch.int64, device=dev),
-                         dict.fromkeys(_C.MESH_EDGES_COUNTS, 0))
+                         zero_counts(_C.MESH_EDGES_COUNTS))
     lib = _C.lib()
     with torch.cuda.device(dev):
-        ws_bytes = int(lib.qf_mesh_edges_workspace_bytes(n_v, n_f))
-        if ws_bytes < 0:
-            raise RuntimeError(f"qf_mesh_edges_workspace_bytes refused V={n_v}, F={n_f}")
-        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-        counts = torch.empty((len(_C.MESH_EDGES_COUNTS),), dtype=torch.int64, device=dev)
+        ws, ws_bytes = workspace("qf_mesh_edges_workspace_bytes", dev, V=n_v, F=n_f)
+        counts = counts_buffer(_C.MESH_EDGES_COUNTS, dev)
         _C.check(lib.qf_mesh_edges_count(_C.ptr(f), n_f, n_v, _C.ptr(ws), ws_bytes, _C.ptr(counts), _C.stream()),
                  "qf_mesh_edges_count")
-        stats = dict(zip(_C.MESH_EDGES_COUNTS, counts.tolist()))
+        stats = read_counts(_C.MESH_EDGES_COUNTS, counts)
         if stats["invalid_faces"]:
-            raise ValueError(f"{stats['invalid_faces']} faces have an index outside [0, {n_v})")
+            raise_invalid_faces(stats["invalid_faces"], n_v)
         edges = torch.empty((stats["edges"], 2), dtype=torch.int64, device=dev)
         face_edges = torch.empty((n_f, 3), dtype=torch.int64, device=dev)
         _C.check(lib.qf_mesh_edges_emit(_C.ptr(f), n_f, n_v, _C.ptr(ws), ws_bytes, _C.ptr(edges), edges.shape[0],
                                         _C.ptr(face_edges), _C.stream()), "qf_mesh_edges_emit")
     return MeshEdges(edges, face_edges, stats)
-
-
-def _device_marks(edge_mark, n_edges: int, device) -> torch.Tensor:
-    """Edge marks (tensor or array, bool or integer; None marks every edge) as a contiguous device uint8 [E]."""
-    if edge_mark is None:
-        return torch.ones((n_edges,), dtype=torch.uint8, device=device)
-    k = edge_mark if isinstance(edge_mark, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(edge_mark))
-    k = k.reshape(-1)
-    if k.shape[0] != n_edges:
-        raise ValueError(f"{k.shape[0]} edge marks for {n_edges} edges")
-    if k.is_floating_point() or k.is_complex():
-        raise TypeError(f"edge_mark must be a bool or integer mask, got {k.dtype}")
-    k = k.to(device)
-    return (k if k.dtype == torch.uint8 else (k != 0).to(torch.uint8)).contiguous()
 
 
 def subdivide_mesh_device(vertices: torch.Tensor, faces: torch.Tensor, edge_mark=None, edges: torch.Tensor = None,
@@ -545,21 +468,9 @@ def subdivide_mesh_device(vertices: torch.Tensor, faces: torch.Tensor, edge_mark
     parent, ``vertex_parents`` is (min, max) of the split edge for a new vertex and (v, v) for an old one, and the first
     V rows of the vertices are the input's, bit for bit; ``stats`` is a dict of the seven counts
     (``_C.MESH_SUBDIVIDE_COUNTS``).  One host wait per stage, for the counts."""
-    if not isinstance(vertices, torch.Tensor):
-        raise TypeError("vertices and faces must be torch.Tensors")
-    f = _device_faces(faces, "subdivide_mesh_device")
-    if vertices.ndim != 2 or vertices.shape[1] != 3:
-        raise ValueError(f"vertices must be [V,3], got {tuple(vertices.shape)}")
-    if not vertices.is_floating_point():
-        raise TypeError(f"vertices must be floating point, got {vertices.dtype}")
-    if not vertices.is_cuda:
-        raise ValueError("subdivide_mesh_device needs device tensors (quadraturefields_amd has no CPU fallback)")
-    if vertices.device != f.device:
-        raise ValueError(f"vertices on {vertices.device} and faces on {f.device}")
+    v, f, dev, n_v, n_f = mesh_inputs(vertices, faces, "subdivide_mesh_device", limit="subdivide")
     if (edges is None) != (face_edges is None):
         raise ValueError("pass both edges and face_edges (mesh_edges_device's) or neither")
-    n_v, n_f = vertices.shape[0], f.shape[0]
-    dev = vertices.device
     if edges is None:
         edges, face_edges, _ = mesh_edges_device(f, n_v)
     else:
@@ -569,23 +480,19 @@ def subdivide_mesh_device(vertices: torch.Tensor, faces: torch.Tensor, edge_mark
             raise ValueError("edges and face_edges must be mesh_edges_device's int64 tensors on the vertices' device")
         face_edges = face_edges.contiguous()
     n_e = edges.shape[0]
-    mark = _device_marks(edge_mark, n_e, dev)
-    if n_f >= 2 ** 29 or n_v + n_e >= 2 ** 31:
-        raise ValueError(f"the mesh has {n_v} vertices, {n_e} edges and {n_f} faces; V + E must be < 2^31 and F < 2^29")
-    v = vertices.to(torch.float64).contiguous()
+    mark = mask_u8(edge_mark, n_e, dev, "edge marks", none_is=1)
+    if n_v + n_e >= 2 ** 31:
+        raise ValueError(f"the mesh has {n_v} vertices and {n_e} edges; V + E must be < 2^31")
     if n_v == 0:
         empty = torch.empty((0,), dtype=torch.int64, device=dev)
-        return SubdividedMesh(v, empty.reshape(0, 3), empty, empty.reshape(0, 2), dict.fromkeys(_C.MESH_SUBDIVIDE_COUNTS, 0))
+        return SubdividedMesh(v, empty.reshape(0, 3), empty, empty.reshape(0, 2), zero_counts(_C.MESH_SUBDIVIDE_COUNTS))
     lib = _C.lib()
     with torch.cuda.device(dev):
-        ws_bytes = int(lib.qf_mesh_subdivide_workspace_bytes(n_v, n_f, n_e))
-        if ws_bytes < 0:
-            raise RuntimeError(f"qf_mesh_subdivide_workspace_bytes refused V={n_v}, F={n_f}, E={n_e}")
-        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-        counts = torch.empty((len(_C.MESH_SUBDIVIDE_COUNTS),), dtype=torch.int64, device=dev)
+        ws, ws_bytes = workspace("qf_mesh_subdivide_workspace_bytes", dev, V=n_v, F=n_f, E=n_e)
+        counts = counts_buffer(_C.MESH_SUBDIVIDE_COUNTS, dev)
         args = (_C.ptr(f), n_f, n_v, _C.ptr(face_edges), n_e, _C.ptr(mark), _C.ptr(ws), ws_bytes)
         _C.check(lib.qf_mesh_subdivide_count(*args, _C.ptr(counts), _C.stream()), "qf_mesh_subdivide_count")
-        stats = dict(zip(_C.MESH_SUBDIVIDE_COUNTS, counts.tolist()))
+        stats = read_counts(_C.MESH_SUBDIVIDE_COUNTS, counts)
         if stats["invalid_faces"]:
             raise ValueError(f"{stats['invalid_faces']} faces have a vertex index outside [0, {n_v}) or an edge id outside "
                              f"[0, {n_e})")
@@ -616,8 +523,7 @@ def subdivide_mesh(mesh: TriMesh, edge_mark=None, levels: int = 1, device="cuda"
     if levels < 1:
         raise ValueError(f"levels must be >= 1, got {levels}")
     dev = edge_mark.device if isinstance(edge_mark, torch.Tensor) and edge_mark.is_cuda else _C.resolve_device(device)
-    v = torch.from_numpy(np.asarray(mesh.vertices, np.float64)).to(dev)
-    f = torch.from_numpy(np.asarray(mesh.faces, np.int64)).to(dev)
+    v, f = trimesh_tensors(mesh, dev)
     uv = None if mesh.visual.uv is None else np.asarray(mesh.visual.uv, np.float64)
     face_map, parents = None, None
     for level in range(levels):
@@ -628,7 +534,7 @@ def subdivide_mesh(mesh: TriMesh, edge_mark=None, levels: int = 1, device="cuda"
         v, f = out.vertices, out.faces
         face_map = out.face_map if face_map is None else face_map[out.face_map]
         parents = out.vertex_parents if parents is None else chain_vertex_parents(parents, out.vertex_parents)
-    return TriMesh(v.cpu().numpy(), f.cpu().numpy(), uv), face_map.cpu().numpy(), parents.cpu().numpy()
+    return (TriMesh(*to_numpy(v, f), uv), *to_numpy(face_map, parents))
 
 
 def mark_edges_longer_than(vertices: torch.Tensor, edges: torch.Tensor, length: float) -> torch.Tensor:
@@ -687,30 +593,15 @@ def decimate_mesh_device(vertices: torch.Tensor, faces: torch.Tensor, target_fac
     locked.  The stats then gain the per-round list ``boundary_taken``; on a closed mesh the result is ``"lock"``'s, bit
     for bit."""
     collapse_mode, weight = _boundary_options(boundary, boundary_weight)
-    if not isinstance(vertices, torch.Tensor):
-        raise TypeError("vertices and faces must be torch.Tensors")
-    f = _device_faces(faces, "decimate_mesh_device")
-    if vertices.ndim != 2 or vertices.shape[1] != 3:
-        raise ValueError(f"vertices must be [V,3], got {tuple(vertices.shape)}")
-    if not vertices.is_floating_point():
-        raise TypeError(f"vertices must be floating point, got {vertices.dtype}")
-    if not vertices.is_cuda:
-        raise ValueError("decimate_mesh_device needs device tensors (quadraturefields_amd has no CPU fallback)")
-    if vertices.device != f.device:
-        raise ValueError(f"vertices on {vertices.device} and faces on {f.device}")
     target, max_rounds = int(target_faces), int(max_rounds)
     if target != target_faces or target < 0 or max_rounds < 0:
         raise ValueError(f"target_faces and max_rounds must be integers >= 0, got {target_faces} and {max_rounds}")
     cost_cap = math.inf if max_cost is None else float(max_cost)
     if not cost_cap >= 0.0:
         raise ValueError(f"max_cost must be >= 0, got {max_cost}")
-    dev = vertices.device
-    n_v0, n_f0 = vertices.shape[0], f.shape[0]
-    if n_v0 >= 2 ** 31 or 3 * n_f0 >= 2 ** 31:
-        raise ValueError(f"the mesh has {n_v0} vertices and {n_f0} faces; V and 3 F must be < 2^31")
-    lock = None if vertex_lock is None else _device_keep(vertex_lock, n_v0, dev)
-    v = vertices.to(torch.float64).contiguous().clone()
-    f = f.clone()
+    v, f, dev, n_v0, n_f0 = mesh_inputs(vertices, faces, "decimate_mesh_device", limit="3F")
+    lock = mask_u8(vertex_lock, n_v0, dev, "vertex locks")
+    v, f = v.clone(), f.clone()
     face_map = torch.arange(n_f0, dtype=torch.int64, device=dev)
     vertex_target = torch.arange(n_v0, dtype=torch.int64, device=dev)
     stats = {"rounds": 0, "faces": [], "candidates": [], "legal": [], "selected": [], "taken": [], "stop": None}
@@ -723,13 +614,6 @@ def decimate_mesh_device(vertices: torch.Tensor, faces: torch.Tensor, target_fac
     flags = _C.MESH_REMOVE_DEGENERATE | _C.MESH_REMOVE_UNREFERENCED
     quadrics = None
     ws_name = "qf_mesh_decimate_open_workspace_bytes" if collapse_mode else "qf_mesh_decimate_workspace_bytes"
-
-    def workspace(n_v, n_f, n_e):
-        n = int(getattr(lib, ws_name)(n_v, n_f, n_e))
-        if n < 0:
-            raise RuntimeError(f"{ws_name} refused V={n_v}, F={n_f}, E={n_e}")
-        return torch.empty((n,), dtype=torch.uint8, device=dev), n
-
     with torch.cuda.device(dev):
         while True:
             n_v, n_f = v.shape[0], f.shape[0]
@@ -740,11 +624,11 @@ def decimate_mesh_device(vertices: torch.Tensor, faces: torch.Tensor, target_fac
                 stats["stop"] = DECIMATE_STOP_MAX_ROUNDS
                 break
             if n_v == 0:
-                raise ValueError(f"{n_f} faces have an index outside [0, 0)")
+                raise_invalid_faces(n_f, 0)
             if quadrics is None:
                 quadrics = torch.empty((n_v, 10), dtype=torch.float64, device=dev)
-                quadric_counts = torch.empty((len(_C.MESH_QUADRIC_COUNTS),), dtype=torch.int64, device=dev)
-                ws, ws_bytes = workspace(n_v, n_f, 0)
+                quadric_counts = counts_buffer(_C.MESH_QUADRIC_COUNTS, dev)
+                ws, ws_bytes = workspace(ws_name, dev, V=n_v, F=n_f, E=0)
                 _C.check(lib.qf_mesh_vertex_quadrics(_C.ptr(v), n_v, _C.ptr(f), n_f, _C.ptr(quadrics), _C.ptr(ws), ws_bytes,
                                                      _C.ptr(quadric_counts), _C.stream()), "qf_mesh_vertex_quadrics")
                 edges, face_edges, _ = mesh_edges_device(f, n_v)          # raises for faces out of range
@@ -752,8 +636,8 @@ def decimate_mesh_device(vertices: torch.Tensor, faces: torch.Tensor, target_fac
                 if n_bad:
                     raise ValueError(f"{n_bad} vertices are not finite")
                 if collapse_mode:
-                    ws, ws_bytes = workspace(n_v, n_f, edges.shape[0])
-                    boundary_counts = torch.empty((len(_C.MESH_BOUNDARY_COUNTS),), dtype=torch.int64, device=dev)
+                    ws, ws_bytes = workspace(ws_name, dev, V=n_v, F=n_f, E=edges.shape[0])
+                    boundary_counts = counts_buffer(_C.MESH_BOUNDARY_COUNTS, dev)
                     _C.check(lib.qf_mesh_boundary_quadrics(_C.ptr(v), n_v, _C.ptr(f), n_f, _C.ptr(edges), edges.shape[0],
                                                            _C.ptr(face_edges), _C.ptr(quadrics), weight, _C.ptr(ws),
                                                            ws_bytes, _C.ptr(boundary_counts), _C.stream()),
@@ -762,8 +646,8 @@ def decimate_mesh_device(vertices: torch.Tensor, faces: torch.Tensor, target_fac
                 edges, face_edges, _ = mesh_edges_device(f, n_v)
             n_e = edges.shape[0]
             max_take = (n_f - target + 1) // 2
-            ws, ws_bytes = workspace(n_v, n_f, n_e)
-            counts = torch.empty((len(count_names),), dtype=torch.int64, device=dev)
+            ws, ws_bytes = workspace(ws_name, dev, V=n_v, F=n_f, E=n_e)
+            counts = counts_buffer(count_names, dev)
             if collapse_mode:
                 _C.check(lib.qf_mesh_collapse_select_open(_C.ptr(v), n_v, _C.ptr(f), n_f, _C.ptr(edges), n_e,
                                                           _C.ptr(face_edges), _C.ptr(quadrics), _C.ptr(lock), cost_cap,
@@ -780,13 +664,7 @@ def decimate_mesh_device(vertices: torch.Tensor, faces: torch.Tensor, target_fac
                 _C.check(lib.qf_mesh_collapse_apply(_C.ptr(v), n_v, _C.ptr(f), n_f, _C.ptr(edges), n_e, _C.ptr(quadrics),
                                                     max_take, _C.ptr(vertex_target), n_v0, _C.ptr(ws), ws_bytes,
                                                     _C.stream()), "qf_mesh_collapse_apply")
-            c_bytes = int(lib.qf_mesh_compact_workspace_bytes(n_v, n_f))
-            if c_bytes < 0:
-                raise RuntimeError(f"qf_mesh_compact_workspace_bytes refused V={n_v}, F={n_f}")
-            c_ws = torch.empty((c_bytes,), dtype=torch.uint8, device=dev)
-            c_counts = torch.empty((len(_C.MESH_COMPACT_COUNTS),), dtype=torch.int64, device=dev)
-            c_args = (_C.ptr(v), n_v, _C.ptr(f), n_f, None, flags, 0, _C.ptr(c_ws), c_bytes)
-            _C.check(lib.qf_mesh_compact_count(*c_args, _C.ptr(c_counts), _C.stream()), "qf_mesh_compact_count")
+            job, c_counts = _compact_count(lib, dev, v, f, None, flags, 0)
             both = torch.cat([c_counts, counts]).tolist()                 # the round's second host wait
             compacted = dict(zip(_C.MESH_COMPACT_COUNTS, both))
             collapse = dict(zip(count_names, both[len(_C.MESH_COMPACT_COUNTS):]))
@@ -798,12 +676,7 @@ def decimate_mesh_device(vertices: torch.Tensor, faces: torch.Tensor, target_fac
                 stats["stop"] = DECIMATE_STOP_NO_EDGE
                 break
             m_v, m_f = compacted["vertices"], compacted["faces"]
-            out_v = torch.empty((m_v, 3), dtype=torch.float64, device=dev)
-            out_f = torch.empty((m_f, 3), dtype=torch.int64, device=dev)
-            c_face_map = torch.empty((m_f,), dtype=torch.int64, device=dev)
-            c_vertex_map = torch.empty((m_v,), dtype=torch.int64, device=dev)
-            _C.check(lib.qf_mesh_compact_emit(*c_args, _C.ptr(out_v), m_v, _C.ptr(out_f), m_f, _C.ptr(c_face_map),
-                                              _C.ptr(c_vertex_map), _C.stream()), "qf_mesh_compact_emit")
+            out_v, out_f, c_face_map, c_vertex_map = _compact_emit(lib, dev, job, m_v, m_f)
             out_q = torch.empty((m_v, 10), dtype=torch.float64, device=dev)
             out_lock = None if lock is None else torch.empty((m_v,), dtype=torch.uint8, device=dev)
             out_face_map = torch.empty((m_f,), dtype=torch.int64, device=dev)
@@ -824,17 +697,15 @@ def decimate_mesh(mesh: TriMesh, target_faces: int, *, max_cost=None, vertex_loc
     ``decimate_mesh_device``'s."""
     _boundary_options(boundary, boundary_weight)
     dev = _C.resolve_device(device)
-    out = decimate_mesh_device(torch.from_numpy(np.asarray(mesh.vertices, np.float64)).to(dev),
-                               torch.from_numpy(np.asarray(mesh.faces, np.int64)).to(dev), target_faces,
-                               max_cost=max_cost, vertex_lock=vertex_lock, max_rounds=max_rounds, return_stats=True,
-                               boundary=boundary, boundary_weight=boundary_weight)
-    vertex_target = out.vertex_target.cpu().numpy()
+    out = decimate_mesh_device(*trimesh_tensors(mesh, dev), target_faces, max_cost=max_cost, vertex_lock=vertex_lock,
+                               max_rounds=max_rounds, return_stats=True, boundary=boundary, boundary_weight=boundary_weight)
+    vertices, faces, face_map, vertex_target = to_numpy(*out[:4])
     uv = None
     if mesh.visual.uv is not None:
         ends, first = np.unique(vertex_target, return_index=True)
         uv = np.zeros((out.vertices.shape[0], 2), dtype=np.asarray(mesh.visual.uv).dtype)
         uv[ends[ends >= 0]] = np.asarray(mesh.visual.uv)[first[ends >= 0]]
-    res = (TriMesh(out.vertices.cpu().numpy(), out.faces.cpu().numpy(), uv), out.face_map.cpu().numpy(), vertex_target)
+    res = (TriMesh(vertices, faces, uv), face_map, vertex_target)
     return res + (out.stats,) if return_stats else res
 
 
@@ -858,41 +729,23 @@ def make_manifold_device(vertices: torch.Tensor, faces: torch.Tensor, *, return_
     put three or more faces on their edges and get cut apart from their neighbours: run ``compact_mesh_device`` with
     ``remove_duplicates`` first.  Two host waits: the edge count of ``mesh_edges_device``, then V'.  Raises ValueError for
     host tensors, bad shapes and, with their number, faces that index outside [0, V)."""
-    if not isinstance(vertices, torch.Tensor):
-        raise TypeError("vertices and faces must be torch.Tensors")
-    f = _device_faces(faces, "make_manifold_device")
-    if vertices.ndim != 2 or vertices.shape[1] != 3:
-        raise ValueError(f"vertices must be [V,3], got {tuple(vertices.shape)}")
-    if not vertices.is_floating_point():
-        raise TypeError(f"vertices must be floating point, got {vertices.dtype}")
-    if not vertices.is_cuda:
-        raise ValueError("make_manifold_device needs device tensors (quadraturefields_amd has no CPU fallback)")
-    if vertices.device != f.device:
-        raise ValueError(f"vertices on {vertices.device} and faces on {f.device}")
-    dev = vertices.device
-    n_v, n_f = vertices.shape[0], f.shape[0]
-    if n_v >= 2 ** 31 or 3 * n_f >= 2 ** 31:
-        raise ValueError(f"the mesh has {n_v} vertices and {n_f} faces; V and 3 F must be < 2^31")
-    v = vertices.to(torch.float64).contiguous()
+    v, f, dev, n_v, n_f = mesh_inputs(vertices, faces, "make_manifold_device", limit="3F")
     if n_v == 0:
         if n_f:
-            raise ValueError(f"{n_f} faces have an index outside [0, 0)")
-        stats = dict.fromkeys(_C.MESH_MANIFOLD_COUNTS, 0) if return_stats else None
+            raise_invalid_faces(n_f, 0)
+        stats = zero_counts(_C.MESH_MANIFOLD_COUNTS) if return_stats else None
         return ManifoldMesh(v.clone(), f.clone(), torch.empty((0,), dtype=torch.int64, device=dev), stats)
     numbered = mesh_edges_device(f, n_v)                                  # raises for faces out of range
     face_edges, n_e = numbered.face_edges, numbered.stats["edges"]
     lib = _C.lib()
     with torch.cuda.device(dev):
-        ws_bytes = int(lib.qf_mesh_manifold_workspace_bytes(n_v, n_f, n_e))
-        if ws_bytes < 0:
-            raise RuntimeError(f"qf_mesh_manifold_workspace_bytes refused V={n_v}, F={n_f}, E={n_e}")
-        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-        counts = torch.empty((len(_C.MESH_MANIFOLD_COUNTS),), dtype=torch.int64, device=dev)
+        ws, ws_bytes = workspace("qf_mesh_manifold_workspace_bytes", dev, V=n_v, F=n_f, E=n_e)
+        counts = counts_buffer(_C.MESH_MANIFOLD_COUNTS, dev)
         _C.check(lib.qf_mesh_manifold_count(_C.ptr(f), n_f, n_v, _C.ptr(face_edges), n_e, _C.ptr(ws), ws_bytes,
                                             _C.ptr(counts), _C.stream()), "qf_mesh_manifold_count")
-        stats = dict(zip(_C.MESH_MANIFOLD_COUNTS, counts.tolist()))
+        stats = read_counts(_C.MESH_MANIFOLD_COUNTS, counts)
         if stats["invalid_faces"]:
-            raise ValueError(f"{stats['invalid_faces']} faces have an index outside [0, {n_v})")
+            raise_invalid_faces(stats["invalid_faces"], n_v)
         out_v = torch.empty((stats["vertices"], 3), dtype=torch.float64, device=dev)
         out_f = torch.empty((n_f, 3), dtype=torch.int64, device=dev)
         vertex_map = torch.empty((stats["vertices"],), dtype=torch.int64, device=dev)
@@ -906,11 +759,10 @@ def make_manifold(mesh: TriMesh, device="cuda", return_stats: bool = False):
     """``make_manifold_device`` on a ``TriMesh``: ``(TriMesh, vertex_map)`` with a numpy int64 map (and the stats dict
     third with ``return_stats``).  Per-vertex ``visual.uv`` is carried through ``vertex_map``."""
     dev = _C.resolve_device(device)
-    out = make_manifold_device(torch.from_numpy(np.asarray(mesh.vertices, np.float64)).to(dev),
-                               torch.from_numpy(np.asarray(mesh.faces, np.int64)).to(dev), return_stats=True)
-    vertex_map = out.vertex_map.cpu().numpy()
+    out = make_manifold_device(*trimesh_tensors(mesh, dev), return_stats=True)
+    vertices, faces, vertex_map = to_numpy(*out[:3])
     uv = None if mesh.visual.uv is None else np.asarray(mesh.visual.uv)[vertex_map]
-    res = (TriMesh(out.vertices.cpu().numpy(), out.faces.cpu().numpy(), uv), vertex_map)
+    res = (TriMesh(vertices, faces, uv), vertex_map)
     return res + (out.stats,) if return_stats else res
 
 
@@ -936,43 +788,25 @@ def weld_vertices_device(vertices: torch.Tensor, faces: torch.Tensor = None, tol
     search cell's population (``stats["largest_cell"]``, cells of edge ``2 h``).  One host wait, for V'.  Raises
     ValueError for host tensors, bad shapes, a negative or non-finite tolerance and, with their number, faces that index
     outside [0, V) and vertices whose search cell is out of range (``|x| / (2 h) >= 2^51``)."""
-    if not isinstance(vertices, torch.Tensor):
-        raise TypeError("vertices and faces must be torch.Tensors")
-    if vertices.ndim != 2 or vertices.shape[1] != 3:
-        raise ValueError(f"vertices must be [V,3], got {tuple(vertices.shape)}")
-    if not vertices.is_floating_point():
-        raise TypeError(f"vertices must be floating point, got {vertices.dtype}")
     h = float(tolerance)
     if not (h >= 0.0 and math.isfinite(h)):
         raise ValueError(f"tolerance must be finite and >= 0, got {tolerance}")
-    if not vertices.is_cuda:
-        raise ValueError("weld_vertices_device needs device tensors (quadraturefields_amd has no CPU fallback)")
-    dev = vertices.device
-    f = torch.empty((0, 3), dtype=torch.int64, device=dev) if faces is None else _device_faces(faces, "weld_vertices_device")
-    if vertices.device != f.device:
-        raise ValueError(f"vertices on {vertices.device} and faces on {f.device}")
-    n_v, n_f = vertices.shape[0], f.shape[0]
-    if n_v >= 2 ** 31 or n_f >= 2 ** 31:
-        raise ValueError(f"the mesh has {n_v} vertices and {n_f} faces; both must be < 2^31")
-    v = vertices.to(torch.float64).contiguous()
+    v, f, dev, n_v, n_f = mesh_inputs(vertices, faces, "weld_vertices_device", limit="F", faces_optional=True)
     if n_v == 0:
         if n_f:
-            raise ValueError(f"{n_f} faces have an index outside [0, 0)")
+            raise_invalid_faces(n_f, 0)
         empty = torch.empty((0,), dtype=torch.int64, device=dev)
-        stats = dict.fromkeys(_C.MESH_WELD_COUNTS, 0) if return_stats else None
+        stats = zero_counts(_C.MESH_WELD_COUNTS) if return_stats else None
         return WeldedMesh(v.clone(), f.clone(), empty, empty.clone(), stats)
     lib = _C.lib()
     with torch.cuda.device(dev):
-        ws_bytes = int(lib.qf_mesh_weld_workspace_bytes(n_v, n_f))
-        if ws_bytes < 0:
-            raise RuntimeError(f"qf_mesh_weld_workspace_bytes refused V={n_v}, F={n_f}")
-        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-        counts = torch.empty((len(_C.MESH_WELD_COUNTS),), dtype=torch.int64, device=dev)
+        ws, ws_bytes = workspace("qf_mesh_weld_workspace_bytes", dev, V=n_v, F=n_f)
+        counts = counts_buffer(_C.MESH_WELD_COUNTS, dev)
         _C.check(lib.qf_mesh_weld_count(_C.ptr(v), n_v, _C.ptr(f) if n_f else None, n_f, h, _C.ptr(ws), ws_bytes,
                                         _C.ptr(counts), _C.stream()), "qf_mesh_weld_count")
-        stats = dict(zip(_C.MESH_WELD_COUNTS, counts.tolist()))
+        stats = read_counts(_C.MESH_WELD_COUNTS, counts)
         if stats["invalid_faces"]:
-            raise ValueError(f"{stats['invalid_faces']} faces have an index outside [0, {n_v})")
+            raise_invalid_faces(stats["invalid_faces"], n_v)
         if stats["out_of_range_vertices"]:
             raise ValueError(f"{stats['out_of_range_vertices']} vertices have a search cell out of range at tolerance {h} "
                              "(a coordinate over twice the tolerance must stay below 2^51)")
@@ -996,11 +830,10 @@ def weld_vertices(mesh: TriMesh, tolerance: float = 0.0, device="cuda", return_s
     ``vertex_map`` the input root of every output vertex, and ``vertex_class`` the output vertex of every input vertex,
     -1 for those whose class no surviving face uses."""
     dev = _C.resolve_device(device)
-    out = weld_vertices_device(torch.from_numpy(np.asarray(mesh.vertices, np.float64)).to(dev),
-                               torch.from_numpy(np.asarray(mesh.faces, np.int64)).to(dev), tolerance, return_stats=True)
-    vertex_map, vertex_class = out.vertex_map.cpu().numpy(), out.vertex_class.cpu().numpy()
+    out = weld_vertices_device(*trimesh_tensors(mesh, dev), tolerance, return_stats=True)
+    vertices, faces, vertex_map, vertex_class = to_numpy(*out[:4])
     uv = None if mesh.visual.uv is None else np.asarray(mesh.visual.uv)[vertex_map]
-    welded = TriMesh(out.vertices.cpu().numpy(), out.faces.cpu().numpy(), uv)
+    welded = TriMesh(vertices, faces, uv)
     if not compact:
         res = (welded, vertex_map, vertex_class)
         return res + (out.stats,) if return_stats else res
@@ -1031,26 +864,14 @@ def sample_surface_device(vertices: torch.Tensor, faces: torch.Tensor, n_samples
     (``_C.MESH_SAMPLE_COUNTS``) second.  One host wait, for the counts, after both calls are enqueued.  Raises ValueError
     for host tensors, bad shapes and, naming the counts, a mesh with non-finite vertices, faces that index outside
     [0, V), bad weights, non-finite measures, or no measure at all."""
-    if not isinstance(vertices, torch.Tensor):
-        raise TypeError("vertices and faces must be torch.Tensors")
-    if vertices.ndim != 2 or vertices.shape[1] != 3:
-        raise ValueError(f"vertices must be [V,3], got {tuple(vertices.shape)}")
-    if not vertices.is_floating_point():
-        raise TypeError(f"vertices must be floating point, got {vertices.dtype}")
     n, seed = int(n_samples), int(seed)
     if not 0 <= n < 2 ** 31:
         raise ValueError(f"n_samples must be in [0, 2^31), got {n_samples}")
     if not 0 <= seed < 2 ** 64:
         raise ValueError(f"seed must be in [0, 2^64), got {seed}")
-    if not vertices.is_cuda:
-        raise ValueError("sample_surface_device needs device tensors (quadraturefields_amd has no CPU fallback)")
-    dev = vertices.device
-    f = _device_faces(faces, "sample_surface_device")
-    if f.device != dev:
-        raise ValueError(f"vertices on {dev} and faces on {f.device}")
-    n_v, n_f = vertices.shape[0], f.shape[0]
-    if not (1 <= n_v < 2 ** 31 and 1 <= n_f and 3 * n_f < 2 ** 31):
-        raise ValueError(f"the mesh has {n_v} vertices and {n_f} faces; it needs 1 <= V < 2^31 and 1 <= F < 2^31 / 3")
+    v, f, dev, n_v, n_f = mesh_inputs(vertices, faces, "sample_surface_device", limit="3F")
+    if n_v < 1 or n_f < 1:
+        raise ValueError(f"the mesh has {n_v} vertices and {n_f} faces; it needs 1 <= V and 1 <= F")
     w = None
     if face_weight is not None:
         if not isinstance(face_weight, torch.Tensor) or not face_weight.is_floating_point():
@@ -1060,14 +881,10 @@ def sample_surface_device(vertices: torch.Tensor, faces: torch.Tensor, n_samples
         if face_weight.device != dev:
             raise ValueError(f"vertices on {dev} and face_weight on {face_weight.device}")
         w = face_weight.to(torch.float64).contiguous()
-    v = vertices.to(torch.float64).contiguous()
     lib = _C.lib()
     with torch.cuda.device(dev):
-        ws_bytes = int(lib.qf_mesh_sample_workspace_bytes(n_v, n_f))
-        if ws_bytes < 0:
-            raise RuntimeError(f"qf_mesh_sample_workspace_bytes refused V={n_v}, F={n_f}")
-        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-        counts = torch.empty((len(_C.MESH_SAMPLE_COUNTS),), dtype=torch.int64, device=dev)
+        ws, ws_bytes = workspace("qf_mesh_sample_workspace_bytes", dev, V=n_v, F=n_f)
+        counts = counts_buffer(_C.MESH_SAMPLE_COUNTS, dev)
         points = torch.empty((n, 3), dtype=torch.float64, device=dev)
         face = torch.empty((n,), dtype=torch.int64, device=dev)
         bary = torch.empty((n, 3), dtype=torch.float64, device=dev)
@@ -1076,7 +893,7 @@ def sample_surface_device(vertices: torch.Tensor, faces: torch.Tensor, n_samples
         _C.check(lib.qf_mesh_sample_emit(_C.ptr(v), n_v, _C.ptr(f), n_f, _C.ptr(ws), ws_bytes, n, seed,
                                          _C.ptr(points) if n else None, _C.ptr(face) if n else None,
                                          _C.ptr(bary) if n else None, _C.stream()), "qf_mesh_sample_emit")
-        stats = dict(zip(_C.MESH_SAMPLE_COUNTS, counts.tolist()))        # the host wait
+        stats = read_counts(_C.MESH_SAMPLE_COUNTS, counts)              # the host wait
     if any(stats[k] for k in _C.MESH_SAMPLE_COUNTS[:4]) or stats["no_measure"]:
         raise ValueError("sample_surface_device: the mesh cannot be sampled: "
                          + ", ".join(f"{k}={stats[k]}" for k in _C.MESH_SAMPLE_COUNTS))
@@ -1089,10 +906,8 @@ def sample_surface(mesh: TriMesh, n_samples: int, seed: int = 0, face_weight=Non
     ``return_stats``).  ``face_weight``: array-like [F] or None."""
     dev = _C.resolve_device(device)
     w = None if face_weight is None else torch.from_numpy(np.ascontiguousarray(face_weight, dtype=np.float64)).to(dev)
-    out, stats = sample_surface_device(torch.from_numpy(np.asarray(mesh.vertices, np.float64)).to(dev),
-                                       torch.from_numpy(np.asarray(mesh.faces, np.int64)).to(dev), n_samples, seed,
-                                       face_weight=w, return_stats=True)
-    res = SurfaceSamples(out.points.cpu().numpy(), out.face.cpu().numpy(), out.bary.cpu().numpy())
+    out, stats = sample_surface_device(*trimesh_tensors(mesh, dev), n_samples, seed, face_weight=w, return_stats=True)
+    res = SurfaceSamples(*to_numpy(*out))
     return (res, stats) if return_stats else res
 
 
@@ -1103,22 +918,12 @@ MeshDistance = namedtuple("MeshDistance", ["a_to_b_mean", "a_to_b_rms", "a_to_b_
 
 
 def _distance_mesh(vertices, faces, what: str):
-    if not isinstance(vertices, torch.Tensor):
-        raise TypeError("vertices and faces must be torch.Tensors")
-    f = _device_faces(faces, "mesh_distance_device")
-    if vertices.ndim != 2 or vertices.shape[1] != 3:
-        raise ValueError(f"{what}: vertices must be [V,3], got {tuple(vertices.shape)}")
-    if not vertices.is_floating_point():
-        raise TypeError(f"{what}: vertices must be floating point, got {vertices.dtype}")
-    if not vertices.is_cuda:
-        raise ValueError("mesh_distance_device needs device tensors (quadraturefields_amd has no CPU fallback)")
-    if vertices.device != f.device:
-        raise ValueError(f"{what}: vertices on {vertices.device} and faces on {f.device}")
-    if f.shape[0] < 1 or vertices.shape[0] < 1:
+    v, f, _, n_v, n_f = mesh_inputs(vertices, faces, "mesh_distance_device", limit="3F", label=what)
+    if n_f < 1 or n_v < 1:
         raise ValueError(f"{what}: a mesh needs at least one vertex and one face")
-    if int(f.min()) < 0 or int(f.max()) >= vertices.shape[0]:
-        raise ValueError(f"{what}: faces index outside [0, {vertices.shape[0]})")
-    return vertices.to(torch.float64).contiguous(), f
+    if int(f.min()) < 0 or int(f.max()) >= n_v:
+        raise ValueError(f"{what}: faces index outside [0, {n_v})")
+    return v, f
 
 
 def _one_sided_distance(samples: torch.Tensor, vertices: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
@@ -1183,11 +988,7 @@ def mesh_distance_device(vertices_a: torch.Tensor, faces_a: torch.Tensor, vertic
 def mesh_distance(mesh_a: TriMesh, mesh_b: TriMesh, device="cuda", samples: int = None, seed: int = 0) -> MeshDistance:
     """``mesh_distance_device`` on two ``TriMesh``."""
     dev = _C.resolve_device(device)
-    args = []
-    for m in (mesh_a, mesh_b):
-        args += [torch.from_numpy(np.asarray(m.vertices, np.float64)).to(dev),
-                 torch.from_numpy(np.asarray(m.faces, np.int64)).to(dev)]
-    return mesh_distance_device(*args, samples=samples, seed=seed)
+    return mesh_distance_device(*trimesh_tensors(mesh_a, dev), *trimesh_tensors(mesh_b, dev), samples=samples, seed=seed)
 
 
 def down_sample_quadraic(mesh: TriMesh, agg=None, verbose: bool = False, device="cuda", boundary: str = "lock") -> TriMesh:

@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from . import _C
+from ._mesh_args import workspace
 from .mesh_io import TriMesh
 
 MAX_TEXTURE_SIDE = 16384
@@ -67,12 +68,9 @@ def per_triangle_atlas(mesh: TriMesh, texture_size: int, texels_per_unit=None, m
     dev = _C.resolve_device(device)
     lib = _C.lib()
     with torch.cuda.device(dev):
-        ws_bytes = int(lib.qf_uv_atlas_workspace_bytes(n_f))
-        if ws_bytes < 0:
-            raise RuntimeError(f"qf_uv_atlas_workspace_bytes refused F={n_f}")
+        ws, ws_bytes = workspace("qf_uv_atlas_workspace_bytes", dev, F=n_f)
         v_d = torch.from_numpy(vertices).to(dev)
         f_d = torch.from_numpy(faces).to(dev)
-        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
         counts = torch.empty((3,), dtype=torch.int64, device=dev)
         _C.check(lib.qf_uv_atlas_measure(_C.ptr(v_d), n_v, _C.ptr(f_d), n_f, _C.ptr(ws), ws_bytes, _C.ptr(counts),
                                          _C.stream()), "qf_uv_atlas_measure")
