@@ -825,10 +825,11 @@ def test_trimesh_separation_follows_the_mesh_on_refit(device):
 
 @pytest.mark.parametrize("k", [12, 16, 28, 32])
 def test_packed_samples_match_oracle_on_every_list_route(device, k):
-    """The packers read a ray's list straight into the sort network's registers (load_sort_row): rows as float4s when K is
-    a multiple of 4, a 16- or a 32-key network by the longest list of the wave.  K = 12 / 16: vector rows, 16 keys, lists
-    truncated to the K nearest; K = 28 / 32: vector rows, 32 keys (up to 20 crossings).  (K = 25, scalar rows, is every
-    other test's case.)  The six sample tensors against the oracle, bit for bit."""
+    """The packers read a ray's list straight into the sort network's registers (load_sort_row): whole quartets of a row as
+    float4s for any K, the row's last 1 .. 3 entries one by one, a 16- or a 32-key network by the longest list of the
+    wave.  K = 12 / 16: no scalar tail, 16 keys, lists truncated to the K nearest; K = 28 / 32: no scalar tail, 32 keys (up
+    to 20 crossings).  (K = 25, a tail of one, is every other test's case; tests/test_gpu_long_lists.py hands the kernels
+    unsorted rows at every tail length and lists longer than 32.)  The six sample tensors against the oracle, bit for bit."""
     from quadraturefields_amd.mesh_utils import MeshIntersection
     mesh = _scene(subdiv=2, shells=10)
     mi = MeshIntersection(mesh, simplify_mesh=False, scale=1.0, num_intersections=k)

@@ -422,11 +422,23 @@ def _oracle_samples(v, f, o, d, k, min_sep):
 def test_ray_major_pack_and_resort_on_tie_laden_lists(device, lib, name, which):
     """``qf_pack_samples`` behind the traversal (plain batches) and ``qf_resort_samples`` on its output, against
     ``sampling_raytrace_numpy`` / ``sampling_indexing``: sample order, ids, depths, positions."""
+    _pack_and_resort(device, name, which, 25)
+
+
+@pytest.mark.parametrize("which", ["0", "trimesh", "spacing"])
+@pytest.mark.parametrize("name", MESH_NAMES)
+def test_ray_major_pack_and_resort_on_tie_laden_lists_above_32(device, lib, name, which):
+    """The same at K = 40: above 32 the pack kernel sorts its rows by insertion in LDS, no longer in the register
+    networks, and these meshes have rays with up to 97 crossings, most of them tied (tests/test_gpu_long_lists.py has
+    long lists without natural ties)."""
+    _pack_and_resort(device, name, which, 40)
+
+
+def _pack_and_resort(device, name, which, k):
     from quadraturefields_amd.mesh_utils import MeshIntersection
     from quadraturefields_amd.mesh_io import TriMesh
     v, f, _ = sm.mesh(name, True)
     ms = _min_sep(name, which)
-    k = 25
     ri = _ri(name, "host", fresh=True, max_hits=k, min_separation=ms)
     exact = {}
     for family in ("axis", "diagonal", "surface", "tiny", "zero"):
